@@ -15,10 +15,15 @@ renders whole frames per rank (weak scaling, no collective).  At N = 1 the
 region (its device time is reported as build_ms; the reference rebuilds it
 every frame, Renderer.cpp:415-503 -- the "with_rebuild" leg times that).
 
-Single process:   python bench.py
+Single process:   python bench.py [--full]
 Multi-GPU:        python bench.py --gpus N        (starts the N ranks itself), or
                   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
-Rank 0 prints one JSON line.  Every per-call device buffer is sized before the
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times --steps
+frames (the headline) and prints its line; --full goes on to everything else
+(PMC traffic passes, roofline, side legs, configs C2/C4/C5, CPU baseline,
+oracle checks of what the timed calls wrote) and prints the long line.
+--dump-outputs DIR writes the last timed frame to DIR (either kind of run).
+Every per-call device buffer is sized before the
 timed region (bih_reserve) and the warm-up issues every call size the timed
 loop issues; the line reports the allocations the headline made
 (device_allocs_in_headline, expected 0).
@@ -113,8 +118,18 @@ def parse():
     ap.add_argument("--no-rebuild-leg", action="store_true",
                     help="skip the leg that rebuilds the BIH every frame (as the reference does)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="time the headline leg only (no side legs), e.g. under rocprofv3 so that "
+                    help="with --full: time the headline leg only (no side legs), e.g. under rocprofv3 so that "
                          "its kernel average is the headline's launches")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run everything else the benchmark measures and checks (PMC "
+                         "traffic passes, roofline, side legs, other configs, CPU baseline, oracle checks of "
+                         "the timed outputs).  Without it the run sets up, warms up, times the steps and "
+                         "prints the headline's line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the headline's last timed step rendered "
+                         "(as rank 0 holds it) to DIR/frame.npy: float32 (rows, width, 4), the bytes of "
+                         "each pixel word; at most 64 MB (a fixed, seeded sample of the rows of a larger "
+                         "frame, listed in DIR/frame_rows.npy)")
     ap.add_argument("--stub", action="store_true",
                     help="launcher test: ranks join a gloo group, check the world size and rank 0 prints "
                          "a JSON line; no GPU work")
@@ -443,7 +458,7 @@ def main():
     # PMC traffic passes run as child processes before this one initialises
     # the GPU (rocprofv3 must start the program itself)
     traffic = None
-    if world == 1 and args.traffic:
+    if args.full and world == 1 and args.traffic:
         traffic = measure_traffic(args)
 
     # rehearsal of the N > 1 path on a one-GPU box: all ranks on cuda:0 over gloo
@@ -508,6 +523,30 @@ def main():
     elapsed, kernel_ms, fps = wl.timed(mode, trav, 0)
     value = fps * rays_per_frame * args.steps / elapsed
     allocs_headline = wl.timed_allocs
+    # --dump-outputs: the last timed step's frame as its caller receives it,
+    # copied out before any other leg writes the output buffers
+    if args.dump_outputs:
+        last = wl.capture(-1, [-1])
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last[0])
+    if not args.full:
+        # the plain run: the headline's line alone (--full runs the rest)
+        if rank == 0:
+            print(json.dumps({
+                "metric": METRIC, "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+                "scaling": mode, "vs_baseline": None, "dtype": "f32", "full": False,
+                "config": {"tris": args.tris, "unique_codes": info.n_unique, "width": W, "height": H,
+                           "spp": SPP, "traverse": args.traverse,
+                           "parallelism": parallelism(mode, args.band, world),
+                           "frames_in_flight": F, "frames_per_call": G, "calls": call_sizes(args.steps, G)},
+                "world_size": world, "backend": backend, "device_allocs_in_headline": allocs_headline,
+                "build_ms": info.build_ms,
+                "dumped_outputs": args.dump_outputs}), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # the frames the headline's timed calls wrote: the first and last frame of
     # each call (N = 1: against the oracle -- the last frame of the first,
     # G-frame call on every row, the others on every 16th row; N > 1 strong:
@@ -991,6 +1030,7 @@ def main():
             "scaling": mode,
             "vs_baseline": None,
             "dtype": "f32",
+            "full": True,
             "data": "synthetic: 1M-triangle soup, splitmix64 seed 1, centroids U([0,2.667]x[-1,1]x[0,2]) "
                     "+ U(-0.02,0.02)^3 vertices (SURVEY.md 8d C3)",
             "config": {
@@ -1089,6 +1129,26 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path, cap):
+    """--dump-outputs: one captured frame (Workload.capture: frame index,
+    global rows, u32 pixel words) as DIR/frame.npy, float32 (rows, W, 4) --
+    the four bytes of each pixel word in memory order -- and the global row of
+    each stored row as DIR/frame_rows.npy (float64).  A frame over the size
+    limit is cut to a fixed sample of its rows (seed 0, ascending)."""
+    _, ys, img = cap
+    n, w = img.shape
+    keep = (DUMP_MAX_BYTES - 4096) // (w * 4 * 4 + 8)
+    pick = np.arange(n)
+    if keep < n:
+        pick = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frame.npy"), img[pick].view(np.uint8).reshape(pick.size, w, 4).astype(np.float32))
+    np.save(os.path.join(path, "frame_rows.npy"), np.asarray(ys)[pick].astype(np.float64))
 
 
 def whitted(args, bihrt, torch, arrays, SPP, sptr):

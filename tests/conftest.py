@@ -16,6 +16,17 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
+def load_golden(fname):
+    """The golden array `fname` of tests/golden.  An array too large to commit
+    as .npy (files stay under 1 MiB) is stored losslessly compressed, as
+    <stem>.npz holding the one array "a"; callers keep naming it .npy."""
+    path = os.path.join(GOLDEN, fname)
+    if os.path.exists(path):
+        return np.load(path)
+    with np.load(os.path.splitext(path)[0] + ".npz") as z:
+        return z["a"]
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a HIP device (MI355X); runs the HIP path")
 

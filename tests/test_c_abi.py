@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import ROOT, load_golden
 
 SRC = os.path.join(ROOT, "tests", "c", "abi_smoke.c")
 LIBDIR = os.path.join(ROOT, "bih-gpu-raytracer_amd", "lib")
@@ -46,7 +46,7 @@ def test_c_caller_renders_golden(fname, scene, w, h, frame, tmp_path, gpu, bihrt
     tris = np.ascontiguousarray(edge_scenes()[scene], np.float32)
     sp, gp = tmp_path / "scene.f32", tmp_path / "golden.u32"
     tris.tofile(sp)
-    np.ascontiguousarray(np.load(os.path.join(GOLDEN, fname)), np.uint32).tofile(gp)
+    np.ascontiguousarray(load_golden(fname), np.uint32).tofile(gp)
     r = subprocess.run([exe, str(sp), str(tris.shape[0]), str(w), str(h), str(frame), str(gp)],
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "abi_smoke OK" in r.stdout, r.stdout + r.stderr

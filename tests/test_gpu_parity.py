@@ -228,8 +228,8 @@ def test_1m_1080p_properties(gpu, bihrt_mod, oracle_mod):
          ("bih1_dodeca_640x480_f0.npy", "bih1_dodeca", 640, 480, 0)])
 def test_render_matches_golden_fixture(fname, scene, w, h, frame, gpu, bihrt_mod):
     """The committed golden framebuffers (tests/golden/make_golden.py)."""
-    from conftest import GOLDEN
-    ref = np.load(os.path.join(GOLDEN, fname))
+    from conftest import load_golden
+    ref = load_golden(fname)
     g = bihrt_mod.GPUArrayManager(SCENES[scene])
     for trav in (bihrt_mod.TRAVERSE_ANYHIT, bihrt_mod.TRAVERSE_REFERENCE):
         img = _device_render(bihrt_mod, g, w, h, 4, frame, trav)

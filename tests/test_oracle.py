@@ -7,7 +7,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, edge_scenes
+from conftest import GOLDEN, edge_scenes, load_golden
 
 F32 = np.float32
 
@@ -436,7 +436,7 @@ GOLDEN_CASES = [("cornell_256x256_f0.npy", "cornell", 256, 256, 0),
 
 @pytest.mark.parametrize("fname,scene,w,h,frame", GOLDEN_CASES)
 def test_oracle_reproduces_golden(oracle_mod, fname, scene, w, h, frame):
-    ref = np.load(os.path.join(GOLDEN, fname))
+    ref = load_golden(fname)
     img, _ = oracle_mod.OracleTree(edge_scenes()[scene]).render(w, h, frame=frame)
     assert np.array_equal(img, ref)
     img2, _ = oracle_mod.OracleTree(edge_scenes()[scene]).render(

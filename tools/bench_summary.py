@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One-screen summary of a bench.py JSON line (the file holds one line)."""
+"""One-screen summary of a `bench.py --full` JSON line (the file holds one line)."""
 import json
 import sys
 

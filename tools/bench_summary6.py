@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One-screen summary of a bench.py JSON line (round 6 fields)."""
+"""One-screen summary of a `bench.py --full` JSON line (round 6 fields)."""
 import json
 import sys
 

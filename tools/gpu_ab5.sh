@@ -2,8 +2,8 @@
 # camera, rebuild, band share, C2): bash tools/gpu_ab5.sh TAG ROUNDS VARIANT... (base = the in-tree library)
 set -u
 T=$1; N=$2; shift 2
-R=$GRAFT_REPO_ROOT
-O=$R/gpurun_out/$T
+R=$(cd "$(dirname "$0")/.." && pwd)
+O=$R/bench_out/$T
 mkdir -p $O
 cd $R
 V=$R/bih-gpu-raytracer_amd/lib/variants
@@ -11,7 +11,7 @@ for k in $(seq 1 $N); do
   for X in "$@"; do
     B=${X%%+*}; E=""; [ "$B" != "$X" ] && E=${X#*+}; E=${E//,/ }
     L=""; [ $B != base ] && L=$V/libbih_amd_$B.so
-    env $E BIH_LIB=$L timeout -k 10 300 python -u bench.py --c5 0 --whitted-frames 0 --cpu-baseline 0 --traffic 0 \
+    env $E BIH_LIB=$L timeout -k 10 300 python -u bench.py --full --c5 0 --whitted-frames 0 --cpu-baseline 0 --traffic 0 \
         --no-reference-leg > $O/bench_${X}_$k.json 2> $O/bench_${X}_$k.err || { tail -20 $O/bench_${X}_$k.err; exit 1; }
     python3 -c "
 import json,sys
