@@ -250,43 +250,30 @@ __device__ __forceinline__ double plane_lmin(double xmin, double xmax, double va
     const double r = 4.0 * 0x1p-24 * fabs(val);
     return plane_m((le ? val - xmax : xmin - val) - r, ramin, ramax);
 }
-// TAB: the per-axis values the walk picks by the node's axis (1 / min|X[a]|,
+// The per-axis values the walk picks by the node's axis (1 / min|X[a]|,
 // 1 / max|X[a]|, the corners' extent) come from a per-thread table in LDS
 // (tab[k * kThreads], k = 4 axis + field) -- one LDS read each instead of a
 // chain of selects over the three axes in registers.
-template <bool TAB>
 __device__ uint32_t triangle_plan(const double (*X)[3], uint32_t leaf, const TreeHeader *hdr,
                                   const float *o, const uint4 *node_prim, const int32_t *leaf_parent,
                                   const int32_t *parent, float *vals, double *tab) {
     constexpr uint32_t kFull = 3u;
-#ifndef BIH_PLAN_LEAN
-#define BIH_PLAN_LEAN 0   // 1: the corners' extent per axis recomputed per level, not kept (12 VGPRs; slower)
-#endif
     double amin[3], amax[3];
-#if !BIH_PLAN_LEAN
-    double xlo[3], xhi[3];
-#endif
     int sgn[3];
     bool finite_ok = true;   // no NaN corner coordinate: the one-value test is exact
     for (int ax = 0; ax < 3; ++ax) {
         const double lo = fmin(fmin(X[0][ax], X[1][ax]), X[2][ax]);
         const double hi = fmax(fmax(X[0][ax], X[1][ax]), X[2][ax]);
         finite_ok = finite_ok && X[0][ax] == X[0][ax] && X[1][ax] == X[1][ax] && X[2][ax] == X[2][ax];
-#if !BIH_PLAN_LEAN
-        xlo[ax] = lo;
-        xhi[ax] = hi;
-#endif
         const double mn = lo > 0.0 ? lo : (hi < 0.0 ? -hi : 0.0);
         const double mx = fmax(fabs(lo), fabs(hi));
         amin[ax] = mn > 0.0 ? 1.0 / mn : 0.0;   // reciprocals (plane_l)
         amax[ax] = mx > 0.0 ? 1.0 / mx : 0.0;
         sgn[ax] = lo > 0.0 ? 1 : (hi < 0.0 ? -1 : 0);
-        if (TAB) {
-            tab[(4 * ax + 0) * kThreads] = amin[ax];
-            tab[(4 * ax + 1) * kThreads] = amax[ax];
-            tab[(4 * ax + 2) * kThreads] = lo;
-            tab[(4 * ax + 3) * kThreads] = hi;
-        }
+        tab[(4 * ax + 0) * kThreads] = amin[ax];
+        tab[(4 * ax + 1) * kThreads] = amax[ax];
+        tab[(4 * ax + 2) * kThreads] = lo;
+        tab[(4 * ax + 3) * kThreads] = hi;
     }
     // slab faces: the smallest L over the faces that can be entries / exits
     PlanL slabE, slabX;
@@ -331,23 +318,10 @@ __device__ uint32_t triangle_plan(const double (*X)[3], uint32_t leaf, const Tre
         const float val = __uint_as_float(le ? r.x : r.y);
         if (sgn[ax] == 0 || val == 0.0f || !(val == val)) return kFull;
         const bool is_exit = le == (sgn[ax] > 0);
-        double am, aM, lmin;
-        if (TAB) {
-            am = tab[(4 * ax + 0) * kThreads];
-            aM = tab[(4 * ax + 1) * kThreads];
-            lmin = plane_lmin(tab[(4 * ax + 2) * kThreads], tab[(4 * ax + 3) * kThreads], (double)val, le, am, aM);
-        } else {
-            am = amin[ax];
-            aM = amax[ax];
-#if BIH_PLAN_LEAN
-        const double c0 = ax == 0u ? X[0][0] : (ax == 1u ? X[0][1] : X[0][2]);
-        const double c1 = ax == 0u ? X[1][0] : (ax == 1u ? X[1][1] : X[1][2]);
-        const double c2 = ax == 0u ? X[2][0] : (ax == 1u ? X[2][1] : X[2][2]);
-        lmin = plane_lmin(fmin(fmin(c0, c1), c2), fmax(fmax(c0, c1), c2), (double)val, le, am, aM);
-#else
-        lmin = plane_lmin(xlo[ax], xhi[ax], (double)val, le, am, aM);
-#endif
-        }
+        const double am = tab[(4 * ax + 0) * kThreads];
+        const double aM = tab[(4 * ax + 1) * kThreads];
+        const double lmin =
+            plane_lmin(tab[(4 * ax + 2) * kThreads], tab[(4 * ax + 3) * kThreads], (double)val, le, am, aM);
         bool ok = finite_ok && lmin + (is_exit ? lastEmin : lastXmin) > 0.0;
         if (!ok) {
             // the three corners: this plane and the partner (the last plane
@@ -362,8 +336,7 @@ __device__ uint32_t triangle_plan(const double (*X)[3], uint32_t leaf, const Tre
             } else {
                 const float qv = is_exit ? lastEv : lastXv;
                 const bool qle = is_exit ? sgn[qa] < 0 : sgn[qa] > 0;
-                q = TAB ? plane_l(X, qa, (double)qv, qle, tab[(4 * qa + 0) * kThreads], tab[(4 * qa + 1) * kThreads])
-                        : plane_l(X, qa, (double)qv, qle, amin[qa], amax[qa]);
+                q = plane_l(X, qa, (double)qv, qle, tab[(4 * qa + 0) * kThreads], tab[(4 * qa + 1) * kThreads]);
             }
             ok = true;
             for (int j = 0; j < 3; ++j) ok = ok && (l.L[j] + q.L[j] > 0.0);
@@ -419,31 +392,13 @@ __device__ void write_path(const uint4 *__restrict__ node_prim, uint32_t k, uint
     }
 }
 
-// BIH_FP_SPLIT: the verification plans (triangle_plan's f64 root-path walk,
-// a chain of dependent node loads) run in k_bin_plan, a kernel of their own
-// with fewer registers and so more waves to hide the chain's latency; k_bin_fp
-// leaves (a, b, cc, 1) of each triangle in front of the camera in its
-// record's plan slots (rec[12..15]; 0 = no plan).
-#ifndef BIH_FP_SPLIT
-#define BIH_FP_SPLIT 0   // 1: slower (0.027 + 0.073 ms with the LDS table vs 0.0965 in one kernel, r04y)
-#endif
-#ifndef BIH_FP_TAB
-#define BIH_FP_TAB 1      // k_bin_fp's plan walk with triangle_plan<true> (LDS per-axis table): 0.0865 vs 0.0963 ms (r04z)
-#endif
 // Footprint of alive triangle i = live[j]: bin rectangle brect[i] (bx0 |
 // bx1 << 16, by0 | by1 << 16; empty = bx0 > bx1) and its list entry
 // binrec[i]; the global list takes the rest.  leaf = the leaf of each sorted
-// triangle (DeviceTree::tri_leaf).
-#ifndef BIH_FP_WAVES_PER_EU
-#define BIH_FP_WAVES_PER_EU 0   // 0: the compiler's choice (128 VGPRs, 4 waves/SIMD)
-#endif
-#if BIH_FP_WAVES_PER_EU
-#define BIH_FP_OCC __attribute__((amdgpu_waves_per_eu(BIH_FP_WAVES_PER_EU, BIH_FP_WAVES_PER_EU)))
-#else
-#define BIH_FP_OCC
-#endif
-__global__ void __launch_bounds__(kThreads) BIH_FP_OCC k_bin_fp(const float *__restrict__ prim, uint32_t n,
-                                                     BinCamera c, const TreeHeader *__restrict__ hdr,
+// triangle (DeviceTree::tri_leaf).  The triangle's verification plan
+// (triangle_plan) is computed here too (128 VGPRs, 4 waves/SIMD).
+__global__ void __launch_bounds__(kThreads) k_bin_fp(const float *__restrict__ prim, uint32_t n, BinCamera c,
+                                                      const TreeHeader *__restrict__ hdr,
                                                      const uint4 *__restrict__ node_prim,
                                                      const uint32_t *__restrict__ tri_leaf,
                                                      const int32_t *__restrict__ leaf_parent,
@@ -454,9 +409,7 @@ __global__ void __launch_bounds__(kThreads) BIH_FP_OCC k_bin_fp(const float *__r
                                                      uint32_t *__restrict__ glist,
                                                      const uint32_t *__restrict__ live,
                                                      const uint32_t *__restrict__ live_count) {
-#if BIH_FP_TAB
     __shared__ double s_tab[12 * kThreads];
-#endif
     const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
     if (j >= *live_count) return;
     const uint32_t i = live[j];   // k_cam_tris
@@ -508,11 +461,7 @@ __global__ void __launch_bounds__(kThreads) BIH_FP_OCC k_bin_fp(const float *__r
             }
         };
         corners(a, b, cc);
-#ifndef BIH_FP_EXP
-#define BIH_FP_EXP 0   // timing experiments only (wrong plans): 1 no plan walk, 2 no det refinement,
-                       // 4 no edge pre-test, 8 no root paths
-#endif
-        if (front == 3 && !(BIH_FP_EXP & 2)) {
+        if (front == 3) {
             // the inflated triangle lies in front of the camera: the exact det
             // of an accepted ray has a geometric lower bound (det_lower_bound),
             // usually far above 1e-6 -- a much tighter inflation, a smaller
@@ -567,25 +516,9 @@ __global__ void __launch_bounds__(kThreads) BIH_FP_OCC k_bin_fp(const float *__r
             rect = make_uint2((x0 / c.tw) | ((x1 / c.tw) << 16), (y0 / c.th) | ((y1 / c.th) << 16));
         }
         // the edge pre-test now (rr, a, b, cc end here), the plan after
-        if (!(BIH_FP_EXP & 4)) edge_pretest(rr, a, b, cc, c, rec);
-#if BIH_FP_SPLIT
-        // the plan is k_bin_plan's: it recomputes the corners from (a, b, cc)
-        if (side == 1) {
-            plan_vals[0] = a;
-            plan_vals[1] = b;
-            plan_vals[2] = cc;
-            plan_vals[3] = 1.0f;
-        }
-#elif BIH_FP_EXP & 1
-        plan = 1u;
-#else
-#if BIH_FP_TAB
-        if (side == 1) plan = triangle_plan<true>(cx, leaf, hdr, c.o, node_prim, leaf_parent, parent, plan_vals,
-                                                  s_tab + threadIdx.x);
-#else
-        if (side == 1) plan = triangle_plan<false>(cx, leaf, hdr, c.o, node_prim, leaf_parent, parent, plan_vals, nullptr);
-#endif
-#endif
+        edge_pretest(rr, a, b, cc, c, rec);
+        if (side == 1)
+            plan = triangle_plan(cx, leaf, hdr, c.o, node_prim, leaf_parent, parent, plan_vals, s_tab + threadIdx.x);
         brect[i] = rect;
     } else {
         // no bound: the always-passing pre-test, every packet tests it
@@ -600,34 +533,23 @@ __global__ void __launch_bounds__(kThreads) BIH_FP_OCC k_bin_fp(const float *__r
     rec[9] = __uint_as_float(i);
     rec[10] = __uint_as_float(leaf | (plan == 0u ? 0x80000000u : 0u));
     rec[11] = __uint_as_float(plan);
-#ifndef BIH_FAST_COUNTERS
-#define BIH_FAST_COUNTERS 0
-#endif
     // counter builds check every plan against the root-path check: all paths
-    if (!BIH_FP_SPLIT && (plan == 3u || BIH_FAST_COUNTERS) && !(BIH_FP_EXP & 8)) write_path(node_prim, leaf, path);
+    if (plan == 3u || BIH_FAST_COUNTERS) write_path(node_prim, leaf, path);
     for (int k = 0; k < 4; ++k) rec[12 + k] = plan_vals[k];
     float4 *o = reinterpret_cast<float4 *>(binrec + 16ull * i);
     for (int k = 0; k < 4; ++k) o[k] = make_float4(rec[4 * k], rec[4 * k + 1], rec[4 * k + 2], rec[4 * k + 3]);
     if (side == 0) glist[atomicAdd(gcount, 1u)] = i;   // every packet tests it
 }
 
-// The verification plan of alive triangle i = live[j] (k_bin_fp's, split
-// off: BIH_FP_SPLIT): the inflated triangle's corners again from the record
-// and k_bin_fp's (a, b, cc) -- the same f64 expressions, the same corners --
-// then triangle_plan, the entry's leaf word and plan, and the root path of a
-// full-check leaf.
-#ifndef BIH_PLAN_TAB
-#define BIH_PLAN_TAB 1     // triangle_plan<true>: per-axis values from an LDS table
-#endif
-#ifndef BIH_PLAN_WAVES
-#define BIH_PLAN_WAVES 0   // waves per SIMD forced on k_bin_plan (0: the compiler's choice)
-#endif
-#if BIH_PLAN_WAVES
-#define BIH_PLAN_OCC __attribute__((amdgpu_waves_per_eu(BIH_PLAN_WAVES, BIH_PLAN_WAVES)))
-#else
-#define BIH_PLAN_OCC
-#endif
-__global__ void __launch_bounds__(kThreads) BIH_PLAN_OCC k_bin_plan(const float *__restrict__ prim, BinCamera c,
+// Not launched.  The verification plan of alive triangle i = live[j] as a
+// kernel of its own, for a k_bin_fp that leaves (a, b, cc, 1) in the record's
+// plan slots (rec[12..15]) instead of the plan: the inflated triangle's
+// corners again from the record and (a, b, cc) -- the same f64 expressions,
+// the same corners -- then triangle_plan, the entry's leaf word and plan, and
+// the root path of a full-check leaf.  The split was slower (DESIGN, "Retired
+// experiments"); the kernel stays until this file's device code next changes,
+// so that retiring the switch left the code object byte for byte the same.
+__global__ void __launch_bounds__(kThreads) k_bin_plan(const float *__restrict__ prim, BinCamera c,
                                                        const TreeHeader *__restrict__ hdr,
                                                        const uint4 *__restrict__ node_prim,
                                                        const uint32_t *__restrict__ tri_leaf,
@@ -636,9 +558,7 @@ __global__ void __launch_bounds__(kThreads) BIH_PLAN_OCC k_bin_plan(const float 
                                                        uint2 *__restrict__ path, float *__restrict__ binrec,
                                                        const uint32_t *__restrict__ live,
                                                        const uint32_t *__restrict__ live_count) {
-#if BIH_PLAN_TAB
     __shared__ double s_tab[12 * kThreads];
-#endif
     const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
     if (j >= *live_count) return;
     const uint32_t i = live[j];
@@ -658,11 +578,7 @@ __global__ void __launch_bounds__(kThreads) BIH_PLAN_OCC k_bin_plan(const float 
         for (int q = 0; q < 3; ++q)
             for (int ax = 0; ax < 3; ++ax)
                 cx[q][ax] = (cu[q] * (double)rr[ax] + cv[q] * (double)rr[3 + ax]) - (double)rr[6 + ax];
-#if BIH_PLAN_TAB
-        plan = triangle_plan<true>(cx, leaf, hdr, c.o, node_prim, leaf_parent, parent, vals, s_tab + threadIdx.x);
-#else
-        plan = triangle_plan<false>(cx, leaf, hdr, c.o, node_prim, leaf_parent, parent, vals, nullptr);
-#endif
+        plan = triangle_plan(cx, leaf, hdr, c.o, node_prim, leaf_parent, parent, vals, s_tab + threadIdx.x);
     }
     rec[10] = __uint_as_float(leaf | (plan == 0u ? 0x80000000u : 0u));
     rec[11] = __uint_as_float(plan);
@@ -1105,10 +1021,7 @@ constexpr uint32_t kQBands = 8, kQClasses = 65;   // live classes 0..63 (costlie
 constexpr uint32_t kQCount = 0, kQStart = kQBands * kQClasses, kQCur = 2 * kQBands * kQClasses,
                    kQHdr = 3 * kQBands * kQClasses, kQHeavy = kQHdr + 4 * kQBands, kQWords = 2048;
 static_assert(kQHeavy + kQBands <= kQWords, "queue words");
-#ifndef BIH_HEAVY_FACTOR
-#define BIH_HEAVY_FACTOR 2.0f
-#endif
-constexpr float kHeavyFactor = BIH_HEAVY_FACTOR;
+constexpr float kHeavyFactor = 2.0f;
 __device__ __forceinline__ uint32_t queue_bin(uint32_t t, uint32_t tiles_x, uint32_t row0,
                                               uint32_t band_h, uint32_t band_step, uint32_t th,
                                               uint32_t bins_x) {
@@ -1322,9 +1235,6 @@ int launch_bin_footprints(const float *tris, uint32_t n, const uint4 *nodes, uin
         hipLaunchKernelGGL(k_bin_fp, g, dim3(kThreads), 0, st, prim, n, c, hdr, node_prim, tri_leaf, leaf_parent,
                            parent, b.path, b.brect, b.binrec, b.gcount,
                            b.glist, b.live, b.gcount + 3);
-        if (BIH_FP_SPLIT)
-            hipLaunchKernelGGL(k_bin_plan, g, dim3(kThreads), 0, st, prim, c, hdr, node_prim, tri_leaf, leaf_parent,
-                               parent, b.path, b.binrec, b.live, b.gcount + 3);
         hipLaunchKernelGGL(k_bin_count, g, dim3(kThreads), 0, st, b.brect, b.live, b.gcount + 3, b.bins_x,
                            reinterpret_cast<const float4 *>(b.binrec), c.w, c.h, c.tw, c.th, b.cnt, b.cntq,
                            reinterpret_cast<unsigned long long *>(b.blkcnt),

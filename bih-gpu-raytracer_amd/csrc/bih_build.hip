@@ -955,39 +955,6 @@ __device__ __forceinline__ float seg_query(const float *__restrict__ seg, uint64
     return res;
 }
 
-// seg_query with every load issued before any is combined (the segment
-// nodes of a query follow from a, b and the level sizes alone, not from the
-// values loaded): one memory round trip per query instead of one per level.
-// Same nodes, and tmax / tmin are associative and commutative: the same
-// result bit for bit.  Levels: ceil(log2(nn)) + 1 <= 28 for nn <= 2^27.
-#ifndef BIH_FIT_PIPE
-#define BIH_FIT_PIPE 0   // 1: slower (k_fit 0.048 vs 0.032 ms, r04a: 122 VGPRs, 4 waves)
-#endif
-constexpr int kSegMaxLevels = 28;
-template <bool HI>
-__device__ __forceinline__ float seg_query_pipe(const float *__restrict__ seg, uint64_t nn, uint32_t a,
-                                                uint32_t b) {
-    const float ident = __uint_as_float(HI ? kMaxKeyBits : kMinKeyBits);
-    float x[2 * kSegMaxLevels];
-    uint32_t l = a, r = b + 1u;
-    uint64_t off = 0, size = nn;
-#pragma unroll
-    for (int lv = 0; lv < kSegMaxLevels; ++lv) {
-        const bool act = l < r;
-        const bool tl = act && (l & 1u), tr = act && (r & 1u);
-        x[2 * lv] = tl ? seg[off + l] : ident;
-        x[2 * lv + 1] = tr ? seg[off + r - 1u] : ident;
-        l = (l + (tl ? 1u : 0u)) >> 1;
-        r = (r - (tr ? 1u : 0u)) >> 1;
-        off += size;
-        size = (size + 1) / 2;
-    }
-    float res = ident;
-#pragma unroll
-    for (int k = 0; k < 2 * kSegMaxLevels; ++k) res = HI ? tmax(res, x[k]) : tmin(res, x[k]);
-    return res;
-}
-
 // The clip planes of node p and its 16-byte render record (k_pack_nodes'
 // layout, bih_internal.h) in one pass: the node's thread has every field.
 // A one-leaf tree has no node: the threads pack the sorted triangle records
@@ -1018,13 +985,8 @@ __global__ void __launch_bounds__(kThreads) k_fit(const TreeHeader *__restrict__
     const int2 rg = node_rng[p];
     const uint32_t split = (uint32_t)children[2 * p];
     const int ax = axis[p];
-#if BIH_FIT_PIPE
-    const float lhi = seg_query_pipe<true>(seg + (3 + ax) * cap, nn, (uint32_t)rg.x, split);
-    const float rlo = seg_query_pipe<false>(seg + ax * cap, nn, split + 1u, (uint32_t)rg.y);
-#else
     const float lhi = seg_query<true>(seg + (3 + ax) * cap, nn, (uint32_t)rg.x, split);
     const float rlo = seg_query<false>(seg + ax * cap, nn, split + 1u, (uint32_t)rg.y);
-#endif
     const float c0 = tmax(-FLT_MAX, lhi);          // initial values GPUArrayManager.cpp:79-80
     const float c1 = tmin(FLT_MAX, rlo);
     clip[2 * p] = c0;

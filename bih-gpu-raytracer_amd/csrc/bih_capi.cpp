@@ -19,10 +19,6 @@
 #include "../../include/bih.h"
 #include "bih_internal.h"
 
-#ifndef BIH_DEBUG_KNOBS
-#define BIH_DEBUG_KNOBS 0   // 1: honour BIH_DBG (timing experiments; changes pixels)
-#endif
-
 // Up to kSlots renders through one tree may be in flight together (issued
 // on as many streams): each launch takes one of kSlots {tile queue, spill
 // area, events} in turn, and reads its frame's XORWOW state from a ring of
@@ -2131,9 +2127,6 @@ int bih_sync(const bih_tree *tr, void *stream) {
             }
         }
     }
-#endif
-#ifndef BIH_PHASES
-#define BIH_PHASES BIH_FAST_COUNTERS
 #endif
 #if BIH_PHASES && !BIH_FAST_COUNTERS
     if (tr->work && tr->last_slot >= 0) {

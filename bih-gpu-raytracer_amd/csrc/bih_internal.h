@@ -53,8 +53,54 @@ constexpr uint32_t kBinBuckets = BIH_BUCKETS;     // list-order buckets per tile
 #define BIH_BLOCK_TILES 512
 #endif
 constexpr uint32_t kBinBlockTiles = BIH_BLOCK_TILES;   // tile rectangle of a bins block counted in LDS
+
+// Compile-time switches of diagnostic builds (-DNAME=1; all 0 in the library
+// that ships).  Each adds instrumentation and leaves the pixels alone, except
+// BIH_DEBUG_KNOBS.
+//   BIH_FAST_COUNTERS    work counters of the shortcut passes and of
+//                        k_render_bins (BIH_FC(x): x in counter builds only),
+//                        every plan's root path written for the cross-check;
+//                        bih_sync prints "fast-counters" / "bin-counters"
+//                        lines (tools/fast_counters.py, bench.py --full)
+//   BIH_PHASES           k_render_bins' wave cycles per phase (BIH_PH), on by
+//                        default in counter builds; bih_sync prints
+//                        "bin-phases"
+//   BIH_BINS_TIMELINE    per-item records of k_render_bins, appended to
+//                        $BIH_TIMELINE_OUT by bih_sync (tools/bins_timeline.py)
+//   BIH_WAVE_TIMELINE    per-wave records of k_render_packet_asm; bih_sync
+//                        prints "wave-timeline" (tools/wave_timeline.py)
+//   BIH_PACKET_COUNTERS  packet-level walk counters and histograms of
+//                        k_render_packet2; bih_sync prints "packet-counters"
+//                        (tools/packet_counters.py)
+//   BIH_WH_MAXDIAG       bih_whitted_work's triangles become the longest walk
+//                        per bounce (tools/whitted_maxwalk.py)
+//   BIH_DEBUG_KNOBS      the library honours BIH_DBG (timing experiments that
+//                        skip phases or checks: they change pixels)
+#ifndef BIH_FAST_COUNTERS
+#define BIH_FAST_COUNTERS 0
+#endif
+#ifndef BIH_PHASES
+#define BIH_PHASES BIH_FAST_COUNTERS
+#endif
+#ifndef BIH_BINS_TIMELINE
+#define BIH_BINS_TIMELINE 0
+#endif
+#ifndef BIH_WAVE_TIMELINE
+#define BIH_WAVE_TIMELINE 0
+#endif
 #ifndef BIH_PACKET_COUNTERS
 #define BIH_PACKET_COUNTERS 0
+#endif
+#ifndef BIH_WH_MAXDIAG
+#define BIH_WH_MAXDIAG 0
+#endif
+#ifndef BIH_DEBUG_KNOBS
+#define BIH_DEBUG_KNOBS 0
+#endif
+#if BIH_FAST_COUNTERS
+#define BIH_FC(x) x
+#else
+#define BIH_FC(x)
 #endif
 
 // Device-resident header written by the builder.

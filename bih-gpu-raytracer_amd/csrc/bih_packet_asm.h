@@ -18,8 +18,8 @@
 // requested with one s_load_dwordx8 into the other of two record buffers
 // (A = s[76:83], B = s[36:43]) before the node's decisions are computed;
 // descending to the left child continues at NB<buf>0, to the right at
-// NB<buf>1.  The root loads its record into A0 = s[76:79]; a pop reads it
-// there from the VGPR stack (BIH_STACK_REC) or loads it like the root.
+// NB<buf>1.  The root loads its record into A0 = s[76:79]; a pop loads it
+// there like the root.
 //
 // Register map (physical registers, listed as clobbers so hipcc keeps its own
 // values out of them; the stack lives only inside the statement).  Kept at or
@@ -36,8 +36,7 @@
 //   v24 inv  v25 t0  v26 t1  v27 sL  v28 sR  v29-v32 {lo,hi} of a stacked child
 //   (MT: v24, v27-v30 division temps; t0/t1 survive the leaf tests)
 //   v33-v38 temps (MT: v35-v37 p, v38 det then 1/det)  v39 stacked node ids
-//   (lane k = slot k; BIH_STACK_REC: v39/v65/v66/v67 lane k = the 4 dwords of
-//   slot k's record)  v40-v50 stacked lo (slot = gpr index)  v51-v61 stacked hi
+//   (lane k = slot k)  v40-v50 stacked lo (slot = gpr index)  v51-v61 stacked hi
 //   (11 slots)
 // Slots >= BIH_ASM_SLOTS go to the wave's HBM spill area, [slot - BIH_ASM_SLOTS]
 // x {lo[64], hi[64]} f32.  Lanes outside a stacked entry's mask hold the
@@ -311,35 +310,9 @@
     BIH_PUSH_NODE(NODE_SET, NODE, R)                                                  \
     "s_add_u32 s63, s63, 1\n\t"
 
-// The stacked node itself.  BIH_STACK_REC: its whole 16-byte record (already
-// in the pair buffer, R = its 4 SGPRs) goes to lane <slot> of v39/v65/v66/v67,
-// so a pop reads it back with v_readlane and starts the node step without a
-// load.  Else: its byte offset to lane <slot> of v39, and the pop loads it.
-#ifndef BIH_STACK_REC
-#define BIH_STACK_REC 0
-#endif
-#if BIH_STACK_REC
-#define BIH_PUSH_NODE(NODE_SET, NODE, R) R
-#define BIH_REC(R0, R1, R2, R3)                                                       \
-    "s_waitcnt lgkmcnt(0)\n\t"               /* the pair prefetch has landed */       \
-    "v_writelane_b32 v39, " R0 ", m0\n\t"                                             \
-    "v_writelane_b32 v65, " R1 ", m0\n\t"                                             \
-    "v_writelane_b32 v66, " R2 ", m0\n\t"                                             \
-    "v_writelane_b32 v67, " R3 ", m0\n\t"
-#define BIH_REC_CLOBBERS "v65", "v66", "v67",
-// Pop: EXEC = the entry's lanes, then its record straight into buffer A
-// (v_readlane ignores EXEC) and the node step A0.
-#define BIH_POP_NODE(ANY_TEXT)                                                        \
-    "s_nop 0\n\t"                                                                     \
-    "v_cmpx_ne_u32_e32 vcc, %[snan], %[tmin]\n\t"  /* EXEC = the entry's lanes */      \
-    ANY_TEXT                                                                          \
-    "v_readlane_b32 s76, v39, s63\n\t"                                                \
-    "v_readlane_b32 s77, v65, s63\n\t"                                                \
-    "v_readlane_b32 s78, v66, s63\n\t"                                                \
-    "v_readlane_b32 s79, v67, s63\n\t"                                                \
-    "s_nop 1\n\t"                                                                     \
-    "s_branch .LBIH_NBA0_%=\n\t"
-#else
+// The stacked node itself: its byte offset to lane <slot> of v39, and the pop
+// loads it.  (BIH_REC / BIH_REC_CLOBBERS: the hooks of a variant that stacked
+// the whole record; empty.)
 #define BIH_PUSH_NODE(NODE_SET, NODE, R) NODE_SET "v_writelane_b32 v39, " NODE ", m0\n\t"
 #define BIH_REC(R0, R1, R2, R3) ""
 #define BIH_REC_CLOBBERS
@@ -351,7 +324,6 @@
     ANY_TEXT                                                                          \
     "s_nop 1\n\t"                                                                     \
     "s_branch .LBIH_N_%=\n\t"
-#endif
 
 #define BIH_PUSH_SPILL(TAG, HI)                                                       \
     ".LBIH_SP" TAG "_%=:\n\t"                /* deep slot: wave spill area */         \

@@ -55,13 +55,6 @@ using dev::xorwow_uniform;
 constexpr int kThreads = 256;
 constexpr uint32_t kDone = 0xFFFFFFFFu;
 
-#ifndef BIH_MT_EARLY_OUT
-#define BIH_MT_EARLY_OUT 1      // return at the back-face test (else fully predicated MT)
-#endif
-#ifndef BIH_SPILL_NT
-#define BIH_SPILL_NT 0          // non-temporal loads/stores for the HBM stack slots
-#endif
-
 // ---------------------------------------------------------------------------
 // RNG: v = M^skip * J^pixel * seed_state (J = M^(2^67)), cuRAND XORWOW.
 // ---------------------------------------------------------------------------
@@ -87,10 +80,7 @@ __device__ __forceinline__ void gf2_apply(const uint32_t *__restrict__ m, uint32
 // each) are one J^64 step through the nibble table in LDS, and the 64 lanes
 // store 64 consecutive words per plane (coalesced: a lane-per-run layout
 // spread each store over 64 lines and was store-bound at 0.18 ms / 1080p).
-#ifndef BIH_RNG_RUN
-#define BIH_RNG_RUN 32
-#endif
-constexpr uint32_t kRngRun = BIH_RNG_RUN;
+constexpr uint32_t kRngRun = 32;
 __device__ __forceinline__ void jump_lds(const uint32_t *__restrict__ nib, uint32_t x[5]) {
     uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0, r4 = 0;
 #pragma unroll
@@ -297,24 +287,18 @@ __device__ __forceinline__ bool tri_hit(const float *__restrict__ tp, float ox, 
     float py = dz * e2x - e2z * dx;
     float pz = dx * e2y - e2x * dy;
     float det = (e1x * px + e1y * py) + e1z * pz;
-#if BIH_MT_EARLY_OUT
     // Coherent rays see a triangle from the same side: the back-face test is
     // usually uniform across the wave, and then skips the rest entirely.
     if (det <= kDetEps) return false;                // det < 0.000001 (double); NaN passes
-#endif
     float inv = 1.0f / det;
     float sx = ox - v0x, sy = oy - v0y, sz = oz - v0z;
     float u = ((sx * px + sy * py) + sz * pz) * inv;
-#if BIH_MT_EARLY_OUT
     if (u < 0.0f || u > 1.0f) return false;
-#endif
     float qx = sy * e1z - e1y * sz;                  // qvec = cross(tvec, e1)
     float qy = sz * e1x - e1z * sx;
     float qz = sx * e1y - e1x * sy;
     float v = ((dx * qx + dy * qy) + dz * qz) * inv;
-#if BIH_MT_EARLY_OUT
     if (v < 0.0f || u + v > 1.0f) return false;
-#endif
     float t = ((e2x * qx + e2y * qy) + e2z * qz) * inv;
     // det < 0.000001 (double compare) rejects; NaN det passes it
     const bool ok_det = !(det <= kDetEps);
@@ -379,15 +363,9 @@ struct Stack {
         if (__builtin_expect(__any(!in_lds), 0)) {
             if (!in_lds) {
                 uint32_t *q = spill + (uint64_t)(sp - kLdsStack) * 3 * gthreads + gtid;
-#if BIH_SPILL_NT
-                __builtin_nontemporal_store(n, q);
-                __builtin_nontemporal_store(__float_as_uint(lo), q + gthreads);
-                __builtin_nontemporal_store(__float_as_uint(hi), q + 2 * gthreads);
-#else
                 q[0] = n;
                 q[gthreads] = __float_as_uint(lo);
                 q[2 * gthreads] = __float_as_uint(hi);
-#endif
             }
         }
     }
@@ -401,15 +379,9 @@ struct Stack {
         if (__builtin_expect(__any(!in_lds), 0)) {
             if (!in_lds) {
                 const uint32_t *q = spill + (uint64_t)(sp - kLdsStack) * 3 * gthreads + gtid;
-#if BIH_SPILL_NT
-                n = __builtin_nontemporal_load(q);
-                lo = __uint_as_float(__builtin_nontemporal_load(q + gthreads));
-                hi = __uint_as_float(__builtin_nontemporal_load(q + 2 * gthreads));
-#else
                 n = q[0];
                 lo = __uint_as_float(q[gthreads]);
                 hi = __uint_as_float(q[2 * gthreads]);
-#endif
             }
         }
     }
@@ -639,10 +611,7 @@ __global__ void __launch_bounds__(kThreads) k_render_pixel(const RenderArgs a) {
 // VGPRs indexed by the uniform stack pointer (s_set_gpr_idx), entries past
 // kPacketRegs in a per-wave HBM area.
 // ---------------------------------------------------------------------------
-#ifndef BIH_PACKET_REGS
-#define BIH_PACKET_REGS 16
-#endif
-constexpr int kPacketRegs = BIH_PACKET_REGS;
+constexpr int kPacketRegs = 16;
 // child refs of the any-hit shortcut records (k_fast_refs)
 constexpr uint32_t kFastLeaf = 0x80000000u, kFastDead = 0xffffffffu;
 
@@ -1243,13 +1212,7 @@ constexpr uint32_t kRegions = 8;
 // 8x4 0.632, 16x2 0.632, 8x2 0.649, 8x8 0.662, 4x4 0.668, 16x4 0.678, 4x2
 // 0.86 ms per frame (3 in flight); with the exact walk 4x4 and 8x4 tied.
 // Chunks of fewer tiles than half a CU's waves refill too often.
-#ifndef BIH_CHUNK_W
-#define BIH_CHUNK_W 8
-#endif
-#ifndef BIH_CHUNK_H
-#define BIH_CHUNK_H 4
-#endif
-constexpr uint32_t kChunkW = BIH_CHUNK_W, kChunkH = BIH_CHUNK_H, kChunk = kChunkW * kChunkH;
+constexpr uint32_t kChunkW = 8, kChunkH = 4, kChunk = kChunkW * kChunkH;
 constexpr uint32_t kSlotWord = 64;                     // work[64..): CU slots, kSlotStrideWords apart
 constexpr unsigned long long kSlotDone = 0xFFFFFFFF00000000ull;
 
@@ -1386,45 +1349,7 @@ __device__ __forceinline__ sf32x16 prim_rec(const cprim_t *prims, uint32_t i) {
                  : "memory");
     return r;
 }
-// shortcut records through the vector memory path (every lane the same
-// address: one request per line) instead of scalar loads
-#ifndef BIH_FAST_VLOAD
-#define BIH_FAST_VLOAD 0
-#endif
-#ifndef BIH_FAST_NOEXACT
-#define BIH_FAST_NOEXACT 0
-#endif
-#ifndef BIH_FAST_SINGLE
-#define BIH_FAST_SINGLE 0
-#endif
-#ifndef BIH_FAST_MAJ
-#define BIH_FAST_MAJ 0   // near order: majority of the lanes entering both (else the lowest)
-#endif
-#ifndef BIH_FAST_ASM_A
-#define BIH_FAST_ASM_A 1   // child masks + near order as one asm sequence
-#endif
 __device__ __forceinline__ sf32x16 fast_rec(const float *boxes, uint32_t node) {
-#if BIH_FAST_VLOAD
-    float4 q0, q1, q2, q3;
-    const float *p = boxes + 16ull * node;
-    asm volatile("global_load_dwordx4 %0, %4, %5\n\t"
-                 "global_load_dwordx4 %1, %4, %5 offset:16\n\t"
-                 "global_load_dwordx4 %2, %4, %5 offset:32\n\t"
-                 "global_load_dwordx4 %3, %4, %5 offset:48\n\t"
-                 "s_waitcnt vmcnt(0)"
-                 : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3)
-                 : "v"(0u), "s"(p)
-                 : "memory");
-    sf32x16 r;
-    r[0] = q0.x; r[1] = q0.y; r[2] = q0.z; r[3] = q0.w;
-    r[4] = q1.x; r[5] = q1.y; r[6] = q1.z; r[7] = q1.w;
-    r[8] = q2.x; r[9] = q2.y; r[10] = q2.z; r[11] = q2.w;
-    r[12] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q3.x)));
-    r[13] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q3.y)));
-    r[14] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q3.z)));
-    r[15] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q3.w)));
-    return r;
-#else
     // one s_load with a 32-bit byte offset (no 64-bit address arithmetic);
     // loaded and waited for inside the statement
     sf32x16 r;
@@ -1434,18 +1359,9 @@ __device__ __forceinline__ sf32x16 fast_rec(const float *boxes, uint32_t node) {
                  : "s"(boxes), "s"(node << 6)
                  : "memory");
     return r;
-#endif
 }
 // BIH_FAST_COUNTERS builds: per-frame work of the shortcut passes in
 // work[16..32) and their cycles in work[32..38) (printed by bih_sync)
-#ifndef BIH_FAST_COUNTERS
-#define BIH_FAST_COUNTERS 0
-#endif
-#if BIH_FAST_COUNTERS
-#define BIH_FC(x) x
-#else
-#define BIH_FC(x)
-#endif
 __device__ __forceinline__ unsigned long long fast_walk(const float *boxes, bool cons,
                                                         const cprim_t *prims,
                                                         const cu32_t *dupc, float dx, float dy,
@@ -1472,37 +1388,23 @@ __device__ __forceinline__ unsigned long long fast_walk(const float *boxes, bool
         slab_t(r[6], r[7], r[8], r[9], r[10], r[11], ix, iy, iz, cl, tn1, tf1);
         // child masks and the near child (as the lowest lane entering both
         // sees it), one SALU/VALU sequence (EXEC is the full wave here)
-#if BIH_FAST_ASM_A
         unsigned long long m0, m1, lt, both;
-        uint32_t first1, cnt_both;
+        uint32_t first1, cnt_both;   // (cnt_both: an SGPR the sequence no longer writes; dropping
+                                     // the operand changes the kernel's register allocation)
         asm volatile("v_cmp_le_f32_e64 %[m0], %[tn0], %[tf0]\n\t"
                      "v_cmp_le_f32_e64 %[m1], %[tn1], %[tf1]\n\t"
                      "v_cmp_lt_f32_e64 %[lt], %[tn1], %[tn0]\n\t"
                      "s_and_b64 %[m0], %[m0], %[mask]\n\t"
                      "s_and_b64 %[m1], %[m1], %[mask]\n\t"
                      "s_and_b64 %[both], %[m0], %[m1]\n\t"
-#if BIH_FAST_MAJ
-                     "s_and_b64 %[lt], %[lt], %[both]\n\t"
-                     "s_bcnt1_i32_b64 %[f1], %[lt]\n\t"
-                     "s_bcnt1_i32_b64 %[c], %[both]\n\t"
-                     "s_lshl_b32 %[f1], %[f1], 1\n\t"
-                     "s_cmp_gt_u32 %[f1], %[c]\n\t"
-#else
                      "s_ff1_i32_b64 %[f1], %[both]\n\t"
                      "s_bitcmp1_b64 %[lt], %[f1]\n\t"
-#endif
                      "s_cselect_b32 %[f1], 1, 0"
                      : [m0] "=&s"(m0), [m1] "=&s"(m1), [lt] "=&s"(lt), [both] "=&s"(both),
                        [f1] "=&s"(first1), [c] "=&s"(cnt_both)
                      : [tn0] "v"(tn0), [tf0] "v"(tf0), [tn1] "v"(tn1), [tf1] "v"(tf1),
                        [mask] "s"(mask)
                      : "scc");
-#else
-        unsigned long long m0 = __ballot(tn0 <= tf0) & mask;
-        unsigned long long m1 = __ballot(tn1 <= tf1) & mask;
-        const unsigned long long both = m0 & m1;
-        const uint32_t first1 = (__ballot(tn1 < tn0) & both & (0ull - both)) != 0ull ? 1u : 0u;
-#endif
         if ((ref0 | ref1) & kFastLeaf) {
             // leaf children: test now (near one first)
 #pragma unroll
@@ -1649,66 +1551,13 @@ __device__ __forceinline__ unsigned long long prim_hits_pre(const sf32x16 r, flo
 // keeps the entry's leaf in `cand`; returns the lanes with a candidate.  A
 // lane of `live` without one has tested every triangle the exact intersector
 // could accept for its ray: a proven miss.
-#ifndef BIH_BINS
-#define BIH_BINS 1
-#endif
 // The list is streamed in chunks of 64 entries: lane j loads entry e + j
-// (48 bytes, coalesced vector loads), the next chunk is requested
-// before the current one is consumed, and each entry reaches the scalar unit
-// by v_readlane -- one memory round trip per 64 entries instead of one per
-// entry.
-#ifndef BIH_SKIP_TRACE
-#define BIH_SKIP_TRACE 0
-#endif
-#ifndef BIH_NO_VERIFY
-#define BIH_NO_VERIFY 0
-#endif
-#ifndef BIH_BIN_PREFETCH_AT
-#define BIH_BIN_PREFETCH_AT 16
-#endif
-#ifndef BIH_BIN_PREFETCH
-#define BIH_BIN_PREFETCH 1
-#endif
-#ifndef BIH_BIN_SETBITS
-#define BIH_BIN_SETBITS 1   // 0: the per-entry mask check (v_readlane + scalar test per entry)
-#endif
-#ifndef BIH_HIT_CACHE
-#define BIH_HIT_CACHE 1   // 0: every frame of an item walks the tile's list from its start (A/B)
-#endif
+// (48 bytes, coalesced vector loads), the next chunk is requested before the
+// current one is consumed, and the chunk's entries sit in the wave's LDS
+// slots (lent) -- one memory round trip per 64 entries instead of one per
+// entry.  The tile list's first chunk stays there across an item's frames.
 constexpr uint32_t kNoCache = 0xFFFFFFFFu;
-#ifndef BIH_ENT_LDS
-#define BIH_ENT_LDS 1   // bin_walk's pre-tests read their entry from LDS (broadcast), not by v_readlane
-#endif
-#ifndef BIH_ENT_KEEP
-#define BIH_ENT_KEEP BIH_ENT_LDS   // the tile list's first chunk stays in LDS across an item's frames
-#endif
-#if BIH_ENT_KEEP && !(BIH_ENT_LDS && BIH_BIN_PREFETCH)
-#error "BIH_ENT_KEEP needs BIH_ENT_LDS and BIH_BIN_PREFETCH"
-#endif
-#if BIH_ENT_LDS && !BIH_BIN_SETBITS
-#error "BIH_ENT_LDS writes the chunk where the set-bits walk ballots it"
-#endif
-#ifndef BIH_HC_EARLY
-#define BIH_HC_EARLY 0   // loads ahead of use: 1 stamp and entry together, 2 the record before the ray (A/B r06r-s: within noise)
-#endif
-#ifndef BIH_CACHE_MINLEN
-#define BIH_CACHE_MINLEN 16   // list entries from which a tile's items use the hit cache
-#endif
-#ifndef BIH_PATHV_SKIP
-#define BIH_PATHV_SKIP 0
-#endif
-#ifndef BIH_BIN_LOOP2
-#define BIH_BIN_LOOP2 1   // 0: the entry loop tests todo && rem every entry (A/B)
-#endif
-#ifndef BIH_REC_LDS
-#define BIH_REC_LDS 0   // multi-frame items: the records of the tile's first 64 entries in LDS
-#endif
-#ifndef BIH_REC_PREFETCH
-#define BIH_REC_PREFETCH 0   // 1: neutral to slightly slower (0.0964 vs 0.094 ms/frame)
-#endif
-__device__ __forceinline__ float lane_f(float v, uint32_t j) {
-    return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), j));
-}
+constexpr uint32_t kCacheMinLen = 16;   // list entries from which a tile's items use the hit cache
 __device__ __forceinline__ void bin_chunk_load(const float4 *ents, uint32_t e, uint32_t end,
                                                uint32_t lane, float4 &c0, float4 &c1, float4 &c2) {
     const uint32_t k = e + lane;
@@ -1735,9 +1584,7 @@ __device__ __forceinline__ unsigned long long bin_walk(const RenderArgs &a, cons
                                                       float dy, float dz, unsigned long long live,
                                                       uint32_t lane, uint32_t &cand, uint32_t &cmeta,
                                                       uint32_t &cent, uint32_t &fc_ent,
-                                                      uint32_t &fc_mt, uint32_t &pf,
-                                                      const float4 *lrec = nullptr, uint32_t lrec_n = 0,
-                                                      float4 *lent = nullptr, uint32_t *ltag = nullptr) {
+                                                      uint32_t &fc_mt, float4 *lent, uint32_t *ltag) {
     const cu32_t *off = (const cu32_t *)(const void *)a.bin_off;
     const float4 *ents = reinterpret_cast<const float4 *>(a.bin_list);
     uint32_t e = off[bin], end = off[bin + 1];
@@ -1749,48 +1596,21 @@ __device__ __forceinline__ unsigned long long bin_walk(const RenderArgs &a, cons
     // before its pre-test
     uint32_t rpix = PMASK ? pixels_of(rem) : 0xFFFFu;
     for (int part = 0; part < 2; ++part) {
-#if BIH_ENT_KEEP
         // the tile list's first chunk is still in the wave's LDS slots from
         // the previous frame of this tile (*ltag: the bin it belongs to)
         bool kept = part == 0 && *ltag == bin;
-#else
-        constexpr bool kept = false;
-#endif
-#if BIH_BIN_PREFETCH
         float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f), c1 = c0, c2 = c0;
         if (e < end && !kept) bin_chunk_load(ents, e, end, lane, c0, c1, c2);
-#endif
         while (e < end && rem) {
-#if BIH_BIN_PREFETCH
-            // the next chunk is requested once this one is a quarter done
+            // d: this chunk; c takes the next one below, before this one is consumed
             const float4 d0 = c0, d1 = c1, d2 = c2;
-#else
-            float4 d0 = make_float4(0.f, 0.f, 0.f, 0.f), d1 = d0, d2 = d0;
-            bin_chunk_load(ents, e, end, lane, d0, d1, d2);
-#endif
             const uint32_t n = end - e < 64u ? end - e : 64u;
-#if BIH_REC_PREFETCH
-            // touch every listed triangle's intersector record now (lane j:
-            // entry j's), so that the scalar loads below hit L2 instead of
-            // each paying a miss in turn; the value is folded into pf, which
-            // the caller consumes after the walk (keeps the load alive)
-            if (e + lane < end)
-                pf ^= *reinterpret_cast<const volatile uint32_t *>(
-                    reinterpret_cast<const uint32_t *>(a.tri_prim) + 16ull * __float_as_uint(d2.y));
-#endif
-#if BIH_BIN_SETBITS
             // the chunk's entries whose pixel mask meets a pixel that still
             // has a lane, as one ballot (lane j: entry j), walked in order by
-            // find-first-set; a hit shrinks rpix and re-filters the rest --
-            // the entries the per-entry mask check below would pre-test
-#if BIH_ENT_KEEP
+            // find-first-set; a hit shrinks rpix and re-filters the rest
             const uint32_t pm =
                 (kept ? reinterpret_cast<const uint32_t *>(lent + 3 * lane + 2)[3] : __float_as_uint(d2.w)) >> 16;
-#else
-            const uint32_t pm = __float_as_uint(d2.w) >> 16;
-#endif
             unsigned long long todo = __ballot(lane < n && (!PMASK || (pm & rpix)));
-#if BIH_ENT_LDS
             // the chunk's entries in the wave's LDS slots (lane j: entry j):
             // each pre-test then reads its entry's 9 plane words as one
             // broadcast instead of 9 v_readlane (12 fewer VALU per entry)
@@ -1801,48 +1621,20 @@ __device__ __forceinline__ unsigned long long bin_walk(const RenderArgs &a, cons
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#if BIH_ENT_KEEP
                 *ltag = (part == 0 && e == e_first) ? bin : ~0u;
-#endif
             }
-#endif
-#if BIH_BIN_PREFETCH
             if (e + 64u < end) bin_chunk_load(ents, e + 64u, end, lane, c0, c1, c2);
-#endif
-#if BIH_BIN_LOOP2
             // (the loop tests `todo` alone -- `rem` only after a hit, where it
             // can change -- and clears bit j with one s_bitset0: 6 scalar
             // instructions per rejected entry instead of 14)
             while (todo) {
                 const uint32_t j = (uint32_t)__builtin_ctzll(todo);
                 asm volatile("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(j));
-#else
-            while (todo && rem) {
-                const uint32_t j = (uint32_t)__builtin_ctzll(todo);
-                todo &= todo - 1ull;
-#endif
-#else
-            for (uint32_t j = 0; j < n && rem; ++j) {
-#if BIH_BIN_PREFETCH
-                if (j == BIH_BIN_PREFETCH_AT && e + 64u < end)
-                    bin_chunk_load(ents, e + 64u, end, lane, c0, c1, c2);
-#endif
-                if (PMASK && !((__builtin_amdgcn_readlane(__float_as_uint(d2.w), j) >> 16) & rpix)) continue;
-#endif
-#if BIH_ENT_LDS
                 const float4 q0 = lent[3 * j], q1 = lent[3 * j + 1];
                 const float q2x = reinterpret_cast<const float *>(lent + 3 * j + 2)[0];
                 const float f0 = __builtin_fmaf(q0.z, vf, __builtin_fmaf(q0.y, uf, q0.x));
                 const float f1 = __builtin_fmaf(q1.y, vf, __builtin_fmaf(q1.x, uf, q0.w));
                 const float f2 = __builtin_fmaf(q2x, vf, __builtin_fmaf(q1.w, uf, q1.z));
-#else
-                const float f0 = __builtin_fmaf(lane_f(d0.z, j), vf,
-                                                __builtin_fmaf(lane_f(d0.y, j), uf, lane_f(d0.x, j)));
-                const float f1 = __builtin_fmaf(lane_f(d1.y, j), vf,
-                                                __builtin_fmaf(lane_f(d1.x, j), uf, lane_f(d0.w, j)));
-                const float f2 = __builtin_fmaf(lane_f(d2.x, j), vf,
-                                                __builtin_fmaf(lane_f(d1.w, j), uf, lane_f(d1.z, j)));
-#endif
                 const unsigned long long in =
                     rem & __ballot(!(f0 < 0.0f) && !(f1 < 0.0f) && !(f2 < 0.0f));
                 BIH_FC(++fc_ent);
@@ -1850,63 +1642,27 @@ __device__ __forceinline__ unsigned long long bin_walk(const RenderArgs &a, cons
                 if (!in) continue;
                 BIH_FC(++fc_mt);
                 if (COUNT && !BIH_FAST_COUNTERS) ++fc_mt;
-#if BIH_ENT_LDS
                 // the entry's words 9-11 (triangle, leaf, plan | pixel mask), broadcast
                 const float4 q2 = lent[3 * j + 2];
                 const uint32_t ti = (a.dbg & 1024u) ? 0u : __builtin_amdgcn_readfirstlane(__float_as_uint(q2.y));
-#else
-                const uint32_t ti = (a.dbg & 1024u) ? 0u : __builtin_amdgcn_readlane(__float_as_uint(d2.y), j);
-#endif
-                sf32x16 r;
-                const uint32_t rel = e + j - e_first;          // (part 0: the tile's list)
-                if (BIH_REC_LDS && part == 0 && rel < lrec_n) {
-                    // the item's copy of the record in LDS (bin_rec_fill): an
-                    // LDS round trip instead of a scalar load from L2/MALL
-                    // one 16-byte read at a time straight into SGPRs (four
-                    // VGPRs live, not 13: the walk is at its register peak)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float4 q = lrec[4 * rel + k];
-                        r[4 * k] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.x)));
-                        if (k < 3) {
-                            r[4 * k + 1] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.y)));
-                            r[4 * k + 2] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.z)));
-                            r[4 * k + 3] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.w)));
-                        }
-                        asm volatile("" ::: "memory");
-                    }
-                } else {
-                    r = prim_rec(prims, ti);
-                }
-                const unsigned long long h = prim_hits_pre(r, dx, dy, dz, in);
+                const unsigned long long h = prim_hits_pre(prim_rec(prims, ti), dx, dy, dz, in);
                 if (h & me) {
-#if BIH_ENT_LDS
                     cand = __float_as_uint(q2.z);
                     cmeta = __float_as_uint(q2.w);
-#else
-                    cand = __builtin_amdgcn_readlane(__float_as_uint(d2.z), j);
-                    cmeta = __builtin_amdgcn_readlane(__float_as_uint(d2.w), j);
-#endif
                     cent = ti;
                 }
                 rem &= ~h;
                 if (PMASK && h) {
                     rpix = pixels_of(rem);
-#if BIH_BIN_SETBITS
                     todo &= __ballot((pm & rpix) != 0u);
-#endif
                 }
-#if BIH_BIN_SETBITS && BIH_BIN_LOOP2
                 // (no lane left: the loop ends on todo -- with PMASK rpix is then
                 // 0 and the ballot above already cleared it; one exit keeps the
                 // loop free of the structurizer's break flags)
                 if (!PMASK && !rem) todo = 0ull;
-#endif
             }
             e += 64u;
-#if BIH_ENT_KEEP
             kept = false;
-#endif
         }
         if (!rem) break;
         ents = reinterpret_cast<const float4 *>(a.bin_glist);
@@ -1920,49 +1676,11 @@ __device__ __forceinline__ unsigned long long bin_walk(const RenderArgs &a, cons
 // (bih_bins.hip: 32 steps {clip - O[axis] of the side taken, axis | side << 2}
 // root-first, end 8, 16 = never verified): the same decisions and intervals,
 // with every load's address known up front (no dependent chain).
-__device__ __forceinline__ bool path_step(uint32_t val, uint32_t meta, float ix, float iy, float iz,
-                                          float &lo, float &hi, bool &done, bool &ok) {
-    if (meta & 8u) {
-        done = true;
-        ok = (meta & 16u) == 0u;
-        return false;
-    }
-    const float inv = sel3(meta & 3u, ix, iy, iz);
-    const bool neg = 0.0f > inv;
-    const float t = __uint_as_float(val) * inv;
-    bool g;
-    float nlo, nhi;
-    if (!(meta & 4u)) {                       // left child
-        const float sL = neg ? hi : lo;
-        g = (t > sL) != neg;
-        nlo = neg ? t : lo;
-        nhi = neg ? hi : t;
-    } else {                                  // right child
-        const float sR = neg ? lo : hi;
-        g = (!(t > sR)) != neg;
-        nlo = neg ? lo : t;
-        nhi = neg ? t : hi;
-    }
-    if (!g) {
-        done = true;
-        ok = false;
-        return false;
-    }
-    lo = nlo;
-    hi = nhi;
-    return true;
-}
 // The first 24 steps are requested at once (one round trip for most
 // leaves), the last 8 only by lanes whose path is longer.
-#ifndef BIH_PATH_BATCH
-#define BIH_PATH_BATCH 8
-#endif
-#ifndef BIH_PATH_FLAT
-#define BIH_PATH_FLAT 1
-#endif
-#if BIH_PATH_FLAT
-// path_step without control flow: the same decisions and intervals for a
-// lane still walking (live); the compare bound and the updated end coincide
+constexpr int kPathBatch = 8;
+// One step, without control flow: fast_verify's decisions and intervals for
+// a lane still walking (live); the compare bound and the updated end coincide
 // (left: neg ? hi : lo, right: neg ? lo : hi -- the bound compared is the
 // one the child keeps, the other becomes t)
 __device__ __forceinline__ void path_step_flat(uint32_t val, uint32_t meta, float ix, float iy, float iz,
@@ -1985,15 +1703,15 @@ __device__ __forceinline__ bool path_verify(const uint2 *__restrict__ path, uint
     const uint4 *p = reinterpret_cast<const uint4 *>(path + 32ull * k);
     bool live = true, ok = false;
 #pragma unroll
-    for (int g = 0; g < 24 / BIH_PATH_BATCH; ++g) {
-        // BIH_PATH_BATCH steps per round trip (8: 3 rounds, 16 VGPRs of
+    for (int g = 0; g < 24 / kPathBatch; ++g) {
+        // kPathBatch steps per round trip (8: 3 rounds, 16 VGPRs of
         // steps live instead of 48 -- that was k_render_bins' register peak:
         // 98 VGPRs and 4 waves per SIMD, now 79 and 6)
-        uint4 q[BIH_PATH_BATCH / 2];
+        uint4 q[kPathBatch / 2];
 #pragma unroll
-        for (int j = 0; j < BIH_PATH_BATCH / 2; ++j) q[j] = p[g * (BIH_PATH_BATCH / 2) + j];
+        for (int j = 0; j < kPathBatch / 2; ++j) q[j] = p[g * (kPathBatch / 2) + j];
 #pragma unroll
-        for (int j = 0; j < BIH_PATH_BATCH; ++j) {
+        for (int j = 0; j < kPathBatch; ++j) {
             const uint4 w = q[j >> 1];
             path_step_flat((j & 1) ? w.z : w.x, (j & 1) ? w.w : w.y, ix, iy, iz, lo, hi, live, ok);
         }
@@ -2012,34 +1730,6 @@ __device__ __forceinline__ bool path_verify(const uint2 *__restrict__ path, uint
     }
     return ok;
 }
-#else
-__device__ __forceinline__ bool path_verify(const uint2 *__restrict__ path, uint32_t k, float ix,
-                                            float iy, float iz, float lo, float hi) {
-    const uint4 *p = reinterpret_cast<const uint4 *>(path + 32ull * k);
-    bool done = false, ok = false;
-    {
-        uint4 q[12];
-#pragma unroll
-        for (int j = 0; j < 12; ++j) q[j] = p[j];
-#pragma unroll
-        for (int j = 0; j < 24; ++j) {
-            const uint4 w = q[j >> 1];
-            if (!path_step((j & 1) ? w.z : w.x, (j & 1) ? w.w : w.y, ix, iy, iz, lo, hi, done, ok))
-                return ok;
-        }
-    }
-    uint4 q[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) q[j] = p[12 + j];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint4 w = q[j >> 1];
-        if (!path_step((j & 1) ? w.z : w.x, (j & 1) ? w.w : w.y, ix, iy, iz, lo, hi, done, ok))
-            return ok;
-    }
-    return false;
-}
-#endif
 
 // Ray::Ray (Ray.cu:3-10) + the scene-AABB slab test (CUDAKernels.cu:237-262):
 // the ray's inverse direction and [tMin, tMax]; true when the ray meets the box
@@ -2063,9 +1753,6 @@ __device__ __forceinline__ bool scene_slab(const SceneU &sc, float dx, float dy,
     if (tzmax < tMax) tMax = tzmax;
     return in_box;
 }
-#ifndef BIH_SLAB_AGAIN
-#define BIH_SLAB_AGAIN 0   // 1: 72 VGPRs, 7 waves, but 0.0420 vs 0.0413 ms per frame (A/B r04n)
-#endif
 
 // A plan's 1-2 critical comparisons (meta & 3 of them) on its values v
 __device__ __forceinline__ bool plan_values_check(uint32_t meta, const float4 v, float ix, float iy, float iz,
@@ -2096,26 +1783,10 @@ __device__ __forceinline__ bool plan_verify(const RenderArgs &a, uint32_t cand, 
     if (cand >> 31) return true;
     meta &= 0xFFFFu;                   // (bits 16-31: the entry's pixel mask)
     const uint32_t n = meta & 3u;
-#if BIH_PATHV_SKIP
-    if (n == 3u) return true;   // timing experiment only: wrong pixels
-#endif
     if (n == 3u) return path_verify(a.bin_path, cand, ix, iy, iz, tMin, tMax);
     // the triangle's plan values (its k_bin_fp record; the same in every list)
     return plan_values_check(meta, reinterpret_cast<const float4 *>(a.bin_rec)[4ull * cent + 3], ix, iy, iz,
                              tMin, tMax);
-}
-
-// plan_verify with the plan values already loaded (the hit cache's
-// candidate: loaded before the frame's ray is made)
-__device__ __forceinline__ bool plan_verify_v(const RenderArgs &a, uint32_t cand, uint32_t meta, const float4 v,
-                                              float ix, float iy, float iz, float tMin, float tMax) {
-    if (cand >> 31) return true;
-    meta &= 0xFFFFu;
-#if BIH_PATHV_SKIP
-    if ((meta & 3u) == 3u) return true;
-#endif
-    if ((meta & 3u) == 3u) return path_verify(a.bin_path, cand, ix, iy, iz, tMin, tMax);
-    return plan_values_check(meta, v, ix, iy, iz, tMin, tMax);
 }
 
 // ---------------------------------------------------------------------------
@@ -2139,9 +1810,6 @@ __device__ __forceinline__ bool plan_verify_v(const RenderArgs &a, uint32_t cand
 // the slot from a band head.  One device-wide atomic per batch instead of
 // one per item: a single head word saturates near 90 dequeues per us.
 // ---------------------------------------------------------------------------
-#ifndef BIH_BINS_TIMELINE
-#define BIH_BINS_TIMELINE 0   // diagnostic builds: per-item records of k_render_bins (bins_timeline_dump)
-#endif
 #if BIH_BINS_TIMELINE
 // {wave | xcc << 24 | kind << 28, start, duration, list length} per queue
 // item (s_memrealtime, 100 MHz); kind 0 live item, 1 background or advance
@@ -2161,28 +1829,8 @@ __device__ __forceinline__ void tl_rec(uint32_t lane, uint32_t kind, uint64_t t0
     }
 }
 #endif
-#ifndef BIH_BINS_WAVES_PER_EU
-#define BIH_BINS_WAVES_PER_EU 0   // 0: the compiler's choice (97 VGPRs, 4 waves: 0.048 vs 0.050 ms/frame forced to 5)
-#endif
-#if BIH_BINS_WAVES_PER_EU
-#define BIH_BINS_OCC __attribute__((amdgpu_waves_per_eu(BIH_BINS_WAVES_PER_EU, BIH_BINS_WAVES_PER_EU)))
-#else
-#define BIH_BINS_OCC
-#endif
 constexpr uint32_t kFbWords = 8;   // fallback record: tile, undecided lo/hi, hits lo/hi, pad
-#ifndef BIH_BIN_BATCH
-#define BIH_BIN_BATCH 8   // A/B (16 frames per call): 8 0.0464 ms per frame, 16 0.0471, 32 0.0482
-#endif
-#ifndef BIH_PHASES
-#define BIH_PHASES BIH_FAST_COUNTERS   // per-phase wave cycles (bih_sync prints them)
-#endif
-#ifndef BIH_QUEUE_STATIC
-#define BIH_QUEUE_STATIC 0
-#endif
-#ifndef BIH_QUEUE_AHEAD
-#define BIH_QUEUE_AHEAD 0   // 1: slower (0.112 vs 0.095 ms/frame): waves wait on refills held by busy waves
-#endif
-constexpr uint32_t kBinBatch = BIH_BIN_BATCH;
+constexpr uint32_t kBinBatch = 8;   // A/B (16 frames per call): 8 0.0464 ms per frame, 16 0.0471, 32 0.0482
 constexpr uint32_t kBinSlot0 = 16 * 32;   // words: heads at b * 32, fallback count at 8 * 32
 struct BinQueue {
     const uint4 *hdr;                  // per band {start, live, bg, items}
@@ -2190,8 +1838,6 @@ struct BinQueue {
     unsigned long long *slot;
     uint32_t band, left;
     uint4 hb;                          // header of the band of the item next() returned
-    unsigned long long pending;        // a position claimed ahead (claim()), lane 0
-    bool has_pending;
     // items per live tile: ns (RenderArgs::nsplit, frame ranges of a.fpi
     // frames); the band's first heavy[b] tiles take hs each instead
     // (RenderArgs::hsplit); a background item covers 64 tiles in every
@@ -2219,14 +1865,6 @@ struct BinQueue {
     }
     __device__ __forceinline__ uint32_t stat(uint32_t b) const { return rounds * band_waves(b); }
 
-    // Claims the slot position next() will use, so that its round trip
-    // overlaps the current item's loads (BIH_QUEUE_AHEAD).
-    __device__ void claim(uint32_t lane) {
-        pending = 0;
-        if (lane == 0) pending = atomicAdd(slot, 1ull);
-        has_pending = true;
-    }
-
     // next item: band (this->hb / band) and index within the band
     __device__ bool next(uint32_t lane, uint32_t &item) {
         if (round < rounds) {
@@ -2246,12 +1884,7 @@ struct BinQueue {
         }
         for (;;) {
             unsigned long long v = 0;
-            if (has_pending) {
-                v = pending;
-                has_pending = false;
-            } else if (lane == 0) {
-                v = atomicAdd(slot, 1ull);
-            }
+            if (lane == 0) v = atomicAdd(slot, 1ull);
             const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
             const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
             if (hi == 0xFFFFFFFFu) return false;
@@ -2298,49 +1931,17 @@ struct BinQueue {
 // (RenderArgs::stamps) -- separate instantiations, so the headline kernel
 // keeps its registers
 constexpr int kBinsStamped = 4;
-#ifndef BIH_STAMPED_WAVES
-#define BIH_STAMPED_WAVES 1   // 6: the stamped instance held to 6 waves per SIMD (scratch spills; one-frame calls 0.093 against 0.082 ms at its own 5)
-#endif
-// SGPR cap of k_render_bins (0: the compiler's choice, 106 + spills): below
-// ~100 a wave's SGPR block leaves room in each SIMD's file beside 6 render
-// waves for the waves of a concurrently dispatched kernel (the next call's
-// XORWOW advance), and the stamped instance fits 6 waves' VGPRs
-#ifndef BIH_BINS_SGPR
-#define BIH_BINS_SGPR 0
-#endif
-#if BIH_BINS_SGPR
-#define BIH_BINS_SGPR_ATTR __attribute__((amdgpu_num_sgpr(BIH_BINS_SGPR)))
-#else
-#define BIH_BINS_SGPR_ATTR
-#endif
 template <int LOG2SPP, int MODE = 0>
-__global__ void __launch_bounds__(kThreads, (MODE & kBinsStamped) ? BIH_STAMPED_WAVES : 1) BIH_BINS_OCC
-BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
+__global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a) {
     constexpr bool MASK = (MODE & 3) == 1, COST = (MODE & 3) == 2, STAMP = (MODE & kBinsStamped) != 0;
     constexpr uint32_t SPP = 1u << LOG2SPP;
     constexpr uint32_t TW = TileShape<LOG2SPP>::TW, TH = TileShape<LOG2SPP>::TH;
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     __shared__ uint32_t s_rs[5][kThreads];   // each lane's XORWOW state between the frames of an item
-#if BIH_HIT_CACHE
     __shared__ uint32_t s_hc[3][kThreads];   // each lane's hit of the item's previous frame: {record, leaf, plan}
-#endif
-#if BIH_ENT_LDS
     __shared__ float4 s_ent[kThreads / 64][64 * 3];   // per wave: the list chunk bin_walk pre-tests
     float4 *const lent = s_ent[tid >> 6];
-#else
-    float4 *const lent = nullptr;
-#endif
-    uint32_t ltag = ~0u;   // the bin whose list's first chunk is in lent (BIH_ENT_KEEP)
-#if BIH_REC_LDS
-    // per wave: the intersector records (tri_prim, 13 of 16 words) of its
-    // item's first 64 list entries, loaded once and read by every frame of
-    // the item (a multi-frame item walks the same list each frame; each
-    // record's scalar load was a dependent round trip to L2/MALL per frame)
-    __shared__ float4 s_rec[kThreads / 64][64 * 4];
-    const float4 *lrec = s_rec[tid >> 6];
-#else
-    const float4 *lrec = nullptr;
-#endif
+    uint32_t ltag = ~0u;   // the bin whose list's first chunk is in lent
     // the slot's next launch starts from a zeroed set: every one of the 1024
     // per-CU slot lines (cu_key() spans 0..1023 sparsely, whatever the grid)
     if (tid == 0)
@@ -2365,7 +1966,6 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
     // band's costliest first -- would start late)
     q.rounds = a.shared_grid ? 0u : a.static_rounds;
     q.round = 0;
-    q.has_pending = false;
     q.ns = a.nsplit;   // an item covers a tile in a.fpi consecutive frames of the launch
     q.hs = a.hsplit;
     q.hv = 0;
@@ -2389,12 +1989,6 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
     }
     const uint32_t fhv = (a.nframes + q.hs - 1u) / q.hs;   // frames per item of a heavy tile
     uint32_t it = 0;
-#if BIH_QUEUE_STATIC
-    // timing experiment: items dealt round-robin over the waves (no atomics)
-    const uint32_t nwv = gridDim.x * (kThreads / 64);
-    uint32_t g_next = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
-    g_next = __builtin_amdgcn_readfirstlane(g_next);
-#endif
 #if BIH_PHASES
     // per-phase wave cycles (s_memtime), summed over waves into work[64..75]
     unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};   // queue, background, setup, walk, verify, write
@@ -2403,27 +1997,11 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
 #else
 #define BIH_PH(k) do { } while (0)
 #endif
-#if BIH_QUEUE_STATIC
-    for (;;) {
-        {
-            uint32_t g = g_next, b = 0;
-            g_next += nwv;
-            uint4 h = q.hdr[0];
-            while (b < 8u && g >= h.w) {
-                g -= h.w;
-                if (++b < 8u) h = q.hdr[b];
-            }
-            if (b >= 8u) break;
-            q.hb = h;
-            it = g;
-        }
-#else
 #if BIH_BINS_TIMELINE
     const uint64_t tl_w0 = __builtin_amdgcn_s_memrealtime();
     tl_rec(lane, 2u, tl_w0, tl_w0, 0u);
 #endif
     while (q.next(lane, it)) {
-#endif
         BIH_PH(0);
 #if BIH_BINS_TIMELINE
         const uint64_t tl_t0 = __builtin_amdgcn_s_memrealtime();
@@ -2518,29 +2096,19 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
 #pragma unroll
             for (int i = 0; i < 5; ++i) s_rs[i][tid] = v[i];
         }
-#if BIH_HIT_CACHE
         s_hc[0][tid] = kNoCache;
         // (tiles with short lists: the walk finds a lane's triangle about as
         // fast as the cache test would -- a record gather and a full
         // intersector call per lane -- so they walk every frame)
         const bool use_cache = ((const uint32_t *)a.bin_off)[bin + 1] - ((const uint32_t *)a.bin_off)[bin] >=
-                               BIH_CACHE_MINLEN;
+                               kCacheMinLen;
         // the lane's hit of the tile's last item (an earlier launch of this
         // camera set's current queue, RenderArgs::hcache): valid while the
         // tile's stamp is the queue's sequence number; the triangle's leaf
         // word and plan come from its record (the words every list entry of
         // the triangle carries)
-#if BIH_HC_EARLY & 1
-        // (stamp and entry read together, the entry discarded unless the
-        // stamp matches: one round trip, not two)
-        if (use_cache && a.hcache && valid) {
-            const uint32_t st = a.hstamp[tile];
-            const uint32_t ti0 = a.hcache[(uint64_t)tile * 64 + lane];
-            const uint32_t ti = st == a.hseq ? ti0 : kNoCache;
-#else
         if (use_cache && a.hcache && valid && a.hstamp[tile] == a.hseq) {
             const uint32_t ti = a.hcache[(uint64_t)tile * 64 + lane];
-#endif
             if (ti < a.hdr_n_tris) {
                 const float4 m = reinterpret_cast<const float4 *>(a.bin_rec)[4ull * ti + 2];
                 s_hc[0][tid] = ti;
@@ -2548,30 +2116,6 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
                 s_hc[2][tid] = __float_as_uint(m.w);
             }
         }
-#endif
-        uint32_t lrec_n = 0;
-#if BIH_REC_LDS
-        if (nf - f0 >= 2u) {
-            const uint32_t e0 = ((const uint32_t *)a.bin_off)[bin];
-            const uint32_t len = ((const uint32_t *)a.bin_off)[bin + 1] - e0;
-            lrec_n = len < 64u ? len : 64u;
-            if (lane < lrec_n) {
-                const uint32_t ti = __float_as_uint(
-                    reinterpret_cast<const float4 *>(a.bin_list)[(uint64_t)kBinEntryF4 * (e0 + lane) + 2].y);
-                const float4 *src = reinterpret_cast<const float4 *>(a.tri_prim) + 4ull * ti;
-                const float4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-                float4 *dst = s_rec[tid >> 6] + 4 * lane;
-                dst[0] = q0;
-                dst[1] = q1;
-                dst[2] = q2;
-                dst[3] = q3;
-            }
-            // the wave's own LDS writes before its reads (lanes read other lanes' slots)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-#endif
         // (measuring launches) the item's work: entries pre-tested + 4 x
         // intersector calls -- each call a dependent scalar load of the
         // record, which is what makes a tile slow; wall time on a SIMD shared
@@ -2584,25 +2128,6 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
         for (uint32_t fj = f0; fj < nf; ++fj, dfr += 2u * SPP * kWeyl) {
             uint32_t *const fout = a.out + (uint64_t)fj * a.out_stride;
             float dx = 0.f, dy = 0.f, dz = 1.f, uf = 0.f, vf = 0.f;
-#if BIH_HIT_CACHE && (BIH_HC_EARLY & 2)
-            // the cached candidate's intersector record and plan values,
-            // requested before the ray is made (they depend on the lane's
-            // last hit only), so that their round trip overlaps the jitter
-            uint32_t cti = kNoCache;
-            float4 cr0 = make_float4(0.f, 0.f, 0.f, 0.f), cr1 = cr0, cr2 = cr0, cv = cr0;
-            float ctn = 0.f;
-            if (use_cache && valid) {
-                cti = s_hc[0][tid];
-                if (cti != kNoCache) {
-                    const float4 *rp = reinterpret_cast<const float4 *>(a.tri_prim) + 4ull * cti;
-                    cr0 = rp[0];
-                    cr1 = rp[1];
-                    cr2 = rp[2];
-                    ctn = reinterpret_cast<const float *>(rp)[12];
-                    cv = reinterpret_cast<const float4 *>(a.bin_rec)[4ull * cti + 3];
-                }
-            }
-#endif
             if (valid) {
                 // the frame's 2*SPP draws on every lane (uniform control
                 // flow); rs ends at the next frame's state
@@ -2646,7 +2171,7 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
             // bins_ok: the lists were built (k_bin_status); else the exact walk decides
             const bool bins_ok = *a.bin_gstat != kBinsUnusable;
             if (live && sc.U > 1 && bins_ok && !(a.dbg & 8u)) {
-                uint32_t cand = 0, cmeta = 0, cent = 0, fc_ent = 0, fc_mt = 0, pf = 0;
+                uint32_t cand = 0, cmeta = 0, cent = 0, fc_ent = 0, fc_mt = 0;
                 // Hit cache (frames after an item's first): a lane first tests
                 // the triangle it hit in the item's previous frame -- the exact
                 // intersector on the new ray, then that candidate's verification
@@ -2657,12 +2182,7 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
                 // full walk proves a miss.  The jitter moves a sample within its
                 // pixel, so most lanes hit the same small triangle again.
                 unsigned long long chit = 0ull;
-#if BIH_HIT_CACHE
                 if (use_cache && !(a.dbg & 20u)) {
-#if BIH_HC_EARLY & 2
-                    const bool okc = in_box && cti != kNoCache && prim_hit_lane(cr0, cr1, cr2, ctn, dx, dy, dz) &&
-                                     plan_verify_v(a, s_hc[1][tid], s_hc[2][tid], cv, ix, iy, iz, tMin, tMax);
-#else
                     const uint32_t cti = s_hc[0][tid];
                     bool okc = false;
                     if (in_box && cti != kNoCache) {
@@ -2672,14 +2192,12 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
                         okc = prim_hit_lane(r0, r1, r2, tn, dx, dy, dz) &&
                               plan_verify(a, s_hc[1][tid], s_hc[2][tid], cti, ix, iy, iz, tMin, tMax);
                     }
-#endif
                     chit = __ballot(okc);
                 }
-#endif
                 const unsigned long long wlive = live & ~chit;
                 const unsigned long long found = wlive ? bin_walk<LOG2SPP == 2, COST || BIH_BINS_TIMELINE>(
-                    a, prims, bin, uf, vf, dx, dy, dz, wlive, lane, cand, cmeta, cent, fc_ent, fc_mt, pf, lrec,
-                    lrec_n, lent, &ltag) : 0ull;
+                    a, prims, bin, uf, vf, dx, dy, dz, wlive, lane, cand, cmeta, cent, fc_ent, fc_mt, lent,
+                    &ltag) : 0ull;
                 if (COST) work += fc_ent + 4u * fc_mt;
 #if BIH_BINS_TIMELINE
                 tl_ent += fc_ent;
@@ -2687,22 +2205,11 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
                 tl_pv += (uint32_t)__popcll(__ballot(((found >> lane) & 1ull) && !(cand >> 31) && (cmeta & 3u) == 3u));
                 tl_pl += (uint32_t)__popcll(__ballot(((found >> lane) & 1ull) && !(cand >> 31) && (cmeta & 3u) != 3u));
 #endif
-                if (pf == 0x7f7f7f7fu && a.dbg == 0xdeadbeefu) a.out[0] = pf;   // (never: keeps the touches)
                 BIH_PH(3);
-#if BIH_SLAB_AGAIN
-                // the slab test's values again for the verification, not kept
-                // live across the walk (the walk's register peak)
-                {
-                    float ex = dx, ey = dy, ez = dz;
-                    asm volatile("" : "+v"(ex), "+v"(ey), "+v"(ez));
-                    scene_slab(sc, ex, ey, ez, ix, iy, iz, tMin, tMax);
-                }
-#endif
                 const bool ok = ((found >> lane) & 1ull) &&
                                 ((a.dbg & 16u) || plan_verify(a, cand, cmeta, cent, ix, iy, iz, tMin, tMax));
                 hits = __ballot(ok) | chit;
                 undecided = wlive & found & ~hits;
-#if BIH_HIT_CACHE
                 // the next frame of the item tries this one first (also a hit
                 // among the list's first entries: every lane the cache settles
                 // leaves the walk, whose pixel masks then skip more entries --
@@ -2712,7 +2219,6 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
                     s_hc[1][tid] = cand;
                     s_hc[2][tid] = cmeta;
                 }
-#endif
                 BIH_PH(4);
 #if BIH_FAST_COUNTERS
                 {   // bin counters (bih_sync prints them): candidates decided by a
@@ -2762,12 +2268,10 @@ BIH_BINS_SGPR_ATTR k_render_bins(const RenderArgs a) {
             BIH_PH(5);
         }
         if (COST && lane == 0) a.bin_cost[bin] = (work << 8) / (nf - f0);
-#if BIH_HIT_CACHE
         if (use_cache && a.hcache) {   // for the tile's next item (a later launch)
             if (valid) a.hcache[(uint64_t)tile * 64 + lane] = s_hc[0][tid];
             if (lane == 0) a.hstamp[tile] = a.hseq;
         }
-#endif
         if (STAMP && nf == a.nframes && lane == 0) {
             // (the item ending at the launch's last frame) the tile's new stamp
             const StampBase sb = stamp_base(a.stamps[tile], a.st_seq);
@@ -2851,12 +2355,10 @@ __global__ void __launch_bounds__(kThreads) k_render_fallback(const RenderArgs a
 // loop (bih_packet_asm.h); ray setup and writeback stay in HIP.  Triangle
 // offsets are 32-bit in the loop: used for scenes of < 2^26 triangles.
 // ---------------------------------------------------------------------------
-#ifndef BIH_ASM_WAVES_PER_EU
-#define BIH_ASM_WAVES_PER_EU 7
-#endif
+constexpr int kAsmWavesPerEu = 7;
 template <bool ANYHIT, bool STATS, int LOG2SPP>
 __global__ void __launch_bounds__(kThreads)
-__attribute__((amdgpu_waves_per_eu(BIH_ASM_WAVES_PER_EU, BIH_ASM_WAVES_PER_EU)))
+__attribute__((amdgpu_waves_per_eu(kAsmWavesPerEu, kAsmWavesPerEu)))
 k_render_packet_asm(const RenderArgs a) {
     constexpr uint32_t SPP = 1u << LOG2SPP;
     constexpr uint32_t TW = TileShape<LOG2SPP>::TW, TH = TileShape<LOG2SPP>::TH;
@@ -2916,12 +2418,7 @@ k_render_packet_asm(const RenderArgs a) {
         if (tzmin > tMin) tMin = tzmin;
         if (tzmax < tMax) tMax = tzmax;
         uint32_t c_nodes = 0, c_leaves = 0, c_tris = 0;
-#if BIH_SKIP_TRACE   // timing experiments only: the kernel without any traversal
-        unsigned long long live = 0ull;
-        (void)in_box;
-#else
         unsigned long long live = sc.U > 0 ? __ballot(in_box) : 0ull;
-#endif
         unsigned long long hits = 0ull, shortcut = 0ull;
 #if BIH_FAST_COUNTERS
         uint64_t fc_walk0 = __builtin_amdgcn_s_memtime();
@@ -2934,16 +2431,9 @@ k_render_packet_asm(const RenderArgs a) {
             BIH_FC(const uint64_t fc_t0 = __builtin_amdgcn_s_memtime());
             const unsigned long long fin =
                 __ballot(__builtin_isfinite(ix) && __builtin_isfinite(iy) && __builtin_isfinite(iz));
-#if BIH_FAST_SINGLE
-            // one conservative pass: hits and miss proofs together
-            const bool single = a.fast2 != nullptr;
-#else
-            const bool single = false;
-#endif
-            const unsigned long long m1 = single ? live & fin : live;
             const unsigned long long found =
-                fast_walk(single ? a.fast2 : a.fast, single, prims, (const cu32_t *)dupc, dx, dy,
-                          dz, ix, iy, iz, m1, lane, cand, s1, n1);
+                fast_walk(a.fast, false, prims, (const cu32_t *)dupc, dx, dy, dz, ix, iy, iz, live,
+                          lane, cand, s1, n1);
             BIH_FC(const uint64_t fc_tw = __builtin_amdgcn_s_memtime());
             const bool ok = ((found >> lane) & 1ull) &&
                             fast_verify(a.node_prim, cand, ix, iy, iz, tMin, tMax);
@@ -2951,11 +2441,10 @@ k_render_packet_asm(const RenderArgs a) {
             BIH_FC(const unsigned long long fc_live0 = live);
             BIH_FC(const uint32_t fc_v1 = (uint32_t)__popcll(shortcut));
             live &= ~shortcut;
-            if (single) live &= ~(m1 & ~found);   // proven misses
             BIH_FC(const uint64_t fc_t1 = __builtin_amdgcn_s_memtime());
             // miss proof for the rest (lanes with an infinite 1/D component
             // keep the exact walk: 0 * inf in a slab test)
-            const unsigned long long m2 = a.fast2 && !single ? live & fin : 0ull;
+            const unsigned long long m2 = a.fast2 ? live & fin : 0ull;
             if (m2) {
                 const unsigned long long found2 =
                     fast_walk(a.fast2, true, prims, (const cu32_t *)dupc, dx, dy, dz, ix, iy, iz,
@@ -3012,9 +2501,6 @@ k_render_packet_asm(const RenderArgs a) {
             }
         } else if (live) {
             if constexpr (ANYHIT && !STATS) {
-#if BIH_FAST_NOEXACT
-                // timing experiments only (wrong for unresolved lanes)
-#else
                 asm volatile(BIH_PACKET_WALK(BIH_ANY_ON, BIH_CLR_ON,
                                              BIH_POP_ANY,
                                              "", "", "", "", "")
@@ -3025,7 +2511,6 @@ k_render_packet_asm(const RenderArgs a) {
                                [lane4] "v"(lane4), [dx] "v"(dx), [dy] "v"(dy), [dz] "v"(dz),
                                [ix] "v"(ix), [iy] "v"(iy), [iz] "v"(iz), [sgn] "v"(sg)
                              : BIH_PACKET_CLOBBERS);
-#endif
             } else if constexpr (ANYHIT && STATS) {
                 asm volatile(BIH_PACKET_WALK(BIH_ANY_ON, BIH_CLR_ON,
                                              BIH_POP_ANY,
@@ -3720,9 +3205,7 @@ int launch_chunk_order(const uint32_t *cost, uint32_t chunks_x, uint32_t nchunks
 // launch is slower with fewer waves (4: 0.0494 ms per frame against 0.0454
 // with all 6), so it takes every slot.  One-frame launches keep every slot
 // (4 per CU: 0.087 -> 0.093 ms alone).
-#ifndef BIH_BINS_MULTI_PER_CU
-#define BIH_BINS_MULTI_PER_CU 4
-#endif
+constexpr int kBinsMultiPerCU = 4;
 uint32_t bins_grid_blocks(int device, uint32_t nframes, bool stamped) {
     static std::mutex mu;
     static uint32_t cache[64][2][2] = {{{0}}};
@@ -3736,7 +3219,7 @@ uint32_t bins_grid_blocks(int device, uint32_t nframes, bool stamped) {
                           : reinterpret_cast<const void *>(k_render_bins<2, 0>), kThreads, 0);
         if (cus <= 0) cus = 256;
         if (per <= 0) per = 1;
-        int multi = BIH_BINS_MULTI_PER_CU < per ? BIH_BINS_MULTI_PER_CU : per;
+        int multi = kBinsMultiPerCU < per ? kBinsMultiPerCU : per;
         if (const char *e = getenv("BIH_BINS_BLOCKS_PER_CU")) {
             const int v = atoi(e);
             if (v > 0 && v <= 32) per = v;

@@ -40,23 +40,19 @@ using dev::xorwow_uniform;
 
 constexpr uint32_t kWT = 64;            // threads per block: one wave
 constexpr int kWStack = kStackDepth;    // Karras path length <= 30 (bih_internal.h)
-#ifndef BIH_WH_LDS
-#define BIH_WH_LDS 10   // (A/B r04r/s, ms per C4 frame: 6 958, 8 725, 10 683, 12 752, 16 877)
-#endif
-constexpr int kWLds = BIH_WH_LDS;       // stack slots per lane in LDS; deeper ones in HBM
+// stack slots per lane in LDS; deeper ones in HBM
+// (A/B r04r/s, ms per C4 frame: 6 958, 8 725, 10 683, 12 752, 16 877)
+constexpr int kWLds = 10;
 constexpr uint32_t kWBlocksPerCU = 32;  // persistent grid of k_wh_trace
 constexpr uint32_t kNoHit = 0xFFFFFFFFu;
 constexpr float kBounceTLo = 1e-4f;     // t_lo of secondary rays (oracle: 1e-4f)
 constexpr uint32_t kWCounts = 32;       // counter words: [0..9] rays per queue, [16..25] rays taken (k_wh_trace_dyn)
 constexpr uint32_t kWFetch = 16;
-#ifndef BIH_WH_SORT_BITS
-#define BIH_WH_SORT_BITS 5   // origin cells per axis 2^bits (3: LDS-aggregated counts; more: global atomics;
-                             // A/B r04zo per 4K frame: 3 0.636 s, 4 0.644, 5 0.620, 6 0.623)
-#endif
-#ifndef BIH_WH_SORT_DIR
-#define BIH_WH_SORT_DIR 0    // 1: the direction's dominant axis joins the key (x 4 buckets; r04zp: 0.617 vs 0.621 s, noise)
-#endif
-constexpr uint32_t kWSortBucketsGen = (8u << (3 * BIH_WH_SORT_BITS)) << (BIH_WH_SORT_DIR ? 2 : 0);   // = kWSortBuckets
+// the bounce queues' sort key (wh_sort_key): origin cells per axis 2^bits (3:
+// LDS-aggregated counts; more: global atomics; A/B r04zo per 4K frame: 3
+// 0.636 s, 4 0.644, 5 0.620, 6 0.623) x 8 direction octants (3 bits: 4096)
+constexpr uint32_t kWSortBits = 5;
+constexpr uint32_t kWSortBuckets = 8u << (3 * kWSortBits);
 constexpr uint32_t kWWorkWords = 18;    // work counters: {nodes, triangles} per bounce, u64 (k_wh_trace_dyn<true>)
 
 struct WScene {
@@ -261,7 +257,7 @@ __global__ void __launch_bounds__(kWT) k_wh_gen(const RenderArgs a, WQueue q, ui
     const uint64_t rays = P * a.spp;
     const uint64_t gid = (uint64_t)blockIdx.x * kWT + threadIdx.x;
     // k_wh_sort_*'s histogram (zeroed again by each scan), whatever the grid
-    for (uint64_t k = gid; k < kWSortBucketsGen; k += (uint64_t)gridDim.x * kWT) sort_hist[k] = 0u;
+    for (uint64_t k = gid; k < kWSortBuckets; k += (uint64_t)gridDim.x * kWT) sort_hist[k] = 0u;
     if (gid == 0 && !hit_mask) {
         counts[0] = (uint32_t)rays;
         for (uint32_t k = 1; k < kWCounts; ++k) counts[k] = 0u;
@@ -379,33 +375,22 @@ __global__ void __launch_bounds__(kWT) k_wh_trace(const RenderArgs a, uint32_t d
 // its loop per wave iteration, the same decisions, intervals, stack and (t, i)
 // rule -- the same hit.  Idle lanes are refilled with one atomic per wave
 // when a quarter of the wave is idle (or all of it).
-#ifndef BIH_WH_REFILL
-#define BIH_WH_REFILL 16   // idle lanes of a wave that trigger a refill
-#endif
-#ifndef BIH_WH_STEPS
-#define BIH_WH_STEPS 256   // walk steps per lane between refill checks (A/B r03: 1 1.792 s, 2 1.777, 4 1.755 per 4K frame;
-                           // r04y-zg after the one-round-trip step: 2 0.698, 4 0.680, 8 0.669, 16 0.660, 32 0.653,
-                           // 64 0.645, 128 0.639, 256 0.635, 512 0.636, 1024 0.647: a refill stalls the whole wave
-                           // on the new rays' loads, so fewer, larger refills pay until idle lanes wait too long)
-#endif
-// BIH_WH_PREFETCH: a step requests the next node's record before it tests
+constexpr int kWRefill = 16;   // idle lanes of a wave that trigger a refill
+// walk steps per lane between refill checks (A/B r03: 1 1.792 s, 2 1.777, 4 1.755 per 4K frame;
+// r04y-zg after the one-round-trip step: 2 0.698, 4 0.680, 8 0.669, 16 0.660, 32 0.653,
+// 64 0.645, 128 0.639, 256 0.635, 512 0.636, 1024 0.647: a refill stalls the whole wave
+// on the new rays' loads, so fewer, larger refills pay until idle lanes wait too long)
+constexpr int kWSteps = 256;
+// A step requests the next node's record before it tests
 // the leaves it decided to visit, so the node load and the leaves' triangle
 // loads are in flight together (one memory round trip per step instead of
 // two); the record waits in the ray state for the next step.  The leaves are
 // still tested before the next node's decisions read the best hit: the same
 // decisions, the same hit.
-#ifndef BIH_WH_MAXDIAG
-#define BIH_WH_MAXDIAG 0   // diagnostic build: bih_whitted_work's triangles = the longest walk per bounce
-#endif
-#ifndef BIH_WH_PREFETCH
-#define BIH_WH_PREFETCH 1
-#endif
 struct WRay {
     float o[3], d[3], ix, iy, iz, tMin, tMax, bt;
     uint32_t sg, cur, sp, bi, sid;
-#if BIH_WH_PREFETCH
     uint4 nd;                  // the record of node cur (requested by the previous step)
-#endif
 };
 __device__ __forceinline__ bool wray_start(const WScene &s, WRay &r, float t_lo) {
     r.bt = FLT_MAX;
@@ -432,9 +417,7 @@ __device__ __forceinline__ bool wray_start(const WScene &s, WRay &r, float t_lo)
     if (t_lo > 0.0f && tMin < t_lo) tMin = t_lo;   // a bounce's walk starts at its origin (oracle)
     r.tMin = tMin;
     r.tMax = tMax;
-#if BIH_WH_PREFETCH
     r.nd = s.nodes[0];
-#endif
     return true;
 }
 // one iteration of closest_walk's loop; true when the walk has ended.
@@ -458,18 +441,12 @@ __device__ __forceinline__ bool wray_step(const WScene &s, WRay &r, float t_lo, 
         if (r.sp == 0) return true;
         --r.sp;
         stk.pop(r.sp, r.cur, r.tMin, r.tMax);
-#if BIH_WH_PREFETCH
         r.nd = s.nodes[r.cur];
-#endif
         return false;
     }
     if (best < r.tMax) r.tMax = best;
     if (COUNT) ++cn;
-#if BIH_WH_PREFETCH
     const uint4 nd = r.nd;
-#else
-    const uint4 nd = s.nodes[r.cur];
-#endif
     const uint32_t ax = (nd.z >> 27) & 3u;
     const float org = pick3(ax, r.o[0], r.o[1], r.o[2]), inv = pick3(ax, r.ix, r.iy, r.iz);
     const uint32_t nr = (r.sg >> ax) & 1u;
@@ -523,23 +500,13 @@ __device__ __forceinline__ bool wray_step(const WScene &s, WRay &r, float t_lo, 
             stk.pop(r.sp, r.cur, r.tMin, r.tMax);
         }
     }
-#if BIH_WH_PREFETCH
     if (!fin) r.nd = s.nodes[r.cur];
-#endif
     leaf(l0b, l0e);
     leaf(l1b, l1e);
     return fin;
 }
 template <bool COUNT>
-#ifndef BIH_WH_WAVES
-#define BIH_WH_WAVES 0   // waves per SIMD forced on k_wh_trace_dyn (0: the compiler's choice)
-#endif
-#if BIH_WH_WAVES
-#define BIH_WH_OCC __attribute__((amdgpu_waves_per_eu(BIH_WH_WAVES, BIH_WH_WAVES)))
-#else
-#define BIH_WH_OCC
-#endif
-__global__ void __launch_bounds__(kWT) BIH_WH_OCC k_wh_trace_dyn(const RenderArgs a, uint32_t depth, WQueue qin, WQueue qout,
+__global__ void __launch_bounds__(kWT) k_wh_trace_dyn(const RenderArgs a, uint32_t depth, WQueue qin, WQueue qout,
                                                       uint32_t *counts, uint8_t *hits, uint32_t *spill,
                                                       unsigned long long *work) {
     uint32_t cn = 0, ct = 0;   // COUNT: nodes entered, triangles tested by this lane
@@ -566,7 +533,7 @@ __global__ void __launch_bounds__(kWT) BIH_WH_OCC k_wh_trace_dyn(const RenderArg
     bool more = true;          // (wave-uniform) the queue may still hold rays
     for (;;) {
         const unsigned long long idle = __ballot(!has);
-        if (more && (__popcll(idle) >= BIH_WH_REFILL || idle == ~0ull)) {
+        if (more && (__popcll(idle) >= kWRefill || idle == ~0ull)) {
             const uint32_t k = (uint32_t)__popcll(idle);
             uint32_t first = 0;
             if (lane == 0) first = atomicAdd(fetch, k);
@@ -595,7 +562,7 @@ __global__ void __launch_bounds__(kWT) BIH_WH_OCC k_wh_trace_dyn(const RenderArg
         }
         bool fin = false;
         if (has)
-            for (int k = 0; k < BIH_WH_STEPS && !fin; ++k) fin = wray_step<COUNT>(sc, r, t_lo, stk, cn, ct);
+            for (int k = 0; k < kWSteps && !fin; ++k) fin = wray_step<COUNT>(sc, r, t_lo, stk, cn, ct);
 #if BIH_WH_MAXDIAG
         if (fin && cn - cn_ray0 > cmax) cmax = cn - cn_ray0;
 #endif
@@ -670,8 +637,6 @@ __global__ void __launch_bounds__(kWT) BIH_WH_OCC k_wh_trace_dyn(const RenderArg
 // k_wh_sort_scan, k_wh_sort_scatter); the order within a bucket is arbitrary.
 // No result depends on the queue order (each ray carries its sample id and
 // its walk is its own), so the pixels and hit counts are unchanged.
-constexpr uint32_t kWSortBits = BIH_WH_SORT_BITS;              // cells per axis: 2^bits
-constexpr uint32_t kWSortBuckets = (8u << (3 * kWSortBits)) << (BIH_WH_SORT_DIR ? 2 : 0);   // x 8 octants (3 bits: 4096)
 constexpr bool kWSortLds = kWSortBuckets == 4096;               // counts aggregated in LDS per block
 constexpr uint32_t kWSortChunk = 4096;                          // rays per sort block (16 per thread)
 __device__ __forceinline__ uint32_t wh_cell(float o, float lo, float hi) {
@@ -687,13 +652,7 @@ __device__ __forceinline__ uint32_t wh_sort_key(const WScene &s, const WQueue &q
     }
     const float dx = q.p[3 * q.cap + i], dy = q.p[4 * q.cap + i], dz = q.p[5 * q.cap + i];
     const uint32_t oct = (dx < 0.0f ? 1u : 0u) | (dy < 0.0f ? 2u : 0u) | (dz < 0.0f ? 4u : 0u);
-#if BIH_WH_SORT_DIR
-    const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
-    const uint32_t dom = (ax >= ay && ax >= az) ? 0u : (ay >= az ? 1u : 2u);
-    return (((cell << 3) | oct) << 2) | dom;
-#else
     return (cell << 3) | oct;
-#endif
 }
 // Per-block bucket counts of queue q's rays [blockIdx.x * chunk, +chunk) into
 // LDS; SCATTER = false adds them to the global histogram, true reserves each
@@ -789,7 +748,6 @@ __global__ void __launch_bounds__(1024) k_wh_sort_scan(uint32_t *hist) {
     }
 }
 static_assert(kWSortBuckets % 1024 == 0, "k_wh_sort_scan: 1024 threads x kWSortPer buckets");
-static_assert(kWSortBuckets == kWSortBucketsGen, "k_wh_gen zeroes every bucket");
 
 // shade of a sample with h hits (oracle whitted_shade), f32
 __device__ __forceinline__ void wh_shade(uint32_t h, float &r, float &g, float &b) {
