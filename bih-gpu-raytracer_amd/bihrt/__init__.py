@@ -20,8 +20,8 @@ import numpy as np
 
 from . import scenes  # noqa: F401
 from ._lib import (PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_STATIC_SOUP,
-                   PARAM_TEST_ALLOC_FAIL, PARAM_WHITTED_COUNTERS,
-                   TRAVERSE_ANYHIT,
+                   PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS,
+                   NO_HIT, QUERY_CLOSEST, QUERY_OCCLUDED, Hit, Ray, TRAVERSE_ANYHIT,
                    TRAVERSE_REFERENCE, BihError, Camera, Framebuffer, Rows, Scene, TreeInfo, check, load)
 from . import _lib
 
@@ -44,6 +44,23 @@ def camera_ray_bound(cam: Camera) -> np.ndarray:
     out = (C.c_float * 3)()
     check(load().bih_camera_ray_bound(C.byref(cam), out), "bih_camera_ray_bound")
     return np.array(out[:], np.float32)
+
+
+# numpy views of bih_ray / bih_hit arrays
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_lo", np.float32), ("d", np.float32, 3), ("reserved", np.float32)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("prim", np.uint32)])
+
+
+def pack_rays(orig, dirs, t_lo=0.0) -> np.ndarray:
+    """(n,) RAY_DTYPE array (bih_ray records) of origins, directions and t_lo."""
+    orig = np.asarray(orig, np.float32).reshape(-1, 3)
+    dirs = np.asarray(dirs, np.float32).reshape(-1, 3)
+    if orig.shape != dirs.shape:
+        raise ValueError("orig and dirs must hold the same number of rays")
+    rays = np.zeros(orig.shape[0], RAY_DTYPE)
+    rays["o"], rays["d"] = orig, dirs
+    rays["t_lo"] = np.broadcast_to(np.asarray(t_lo, np.float32), (orig.shape[0],))
+    return rays
 
 
 class GPUArrayManager:
@@ -101,6 +118,31 @@ class GPUArrayManager:
         out = np.zeros(n.value // np.dtype(dtype).itemsize, dtype)
         check(load().bih_tree_export(self._tree, which, out.ctypes.data, C.byref(n)), "bih_tree_export")
         return out
+
+    def trace(self, orig, dirs, t_lo=0.0, query: int = QUERY_CLOSEST):
+        """Ray queries for host rays (bih_trace; synchronous).  orig, dirs: (n, 3)
+        float32; t_lo: a scalar or (n,).  QUERY_CLOSEST returns a dict of `t`, `u`,
+        `v` (float32) and `prim` (uint32 file-order triangle, NO_HIT on a miss);
+        QUERY_OCCLUDED a uint8 array (1: some triangle is hit)."""
+        rays = pack_rays(orig, dirs, t_lo)
+        n = rays.shape[0]
+        out = np.zeros(n, HIT_DTYPE if query == QUERY_CLOSEST else np.uint8)
+        check(load().bih_trace(self._tree, C.c_void_p(rays.ctypes.data), n, query,
+                               C.c_void_p(out.ctypes.data)), "bih_trace")
+        if query != QUERY_CLOSEST:
+            return out
+        return {k: np.ascontiguousarray(out[k]) for k in ("t", "u", "v", "prim")}
+
+    def trace_device(self, rays_ptr: int, n: int, out_ptr: int, query: int = QUERY_CLOSEST,
+                     stream: int | None = None):
+        """Asynchronous ray queries on device memory (bih_trace_device): n bih_ray
+        (32 bytes each, see pack_rays) at rays_ptr, results to out_ptr (16-byte
+        bih_hit per ray, or one byte per ray for QUERY_OCCLUDED)."""
+        check(load().bih_trace_device(self._tree, C.c_void_p(rays_ptr), n, query, C.c_void_p(out_ptr),
+                                      C.c_void_p(stream or 0)), "bih_trace_device")
+
+    def sync(self, stream: int | None = None):
+        check(load().bih_sync(self._tree, C.c_void_p(stream or 0)), "bih_sync")
 
     def arrays(self) -> dict:
         """Canonical arrays under the oracle's names (OracleTree attributes)."""
@@ -302,4 +344,5 @@ def write_ppm(path: str, img: np.ndarray):
 __all__ = ["GPUArrayManager", "Renderer", "Model", "load_obj", "host_register", "host_unregister", "Camera", "Rows", "BihError", "camera_reference",
            "camera_ray_bound", "device_count", "unpack_rgba", "write_ppm", "scenes", "TRAVERSE_ANYHIT",
            "TRAVERSE_REFERENCE", "PARAM_ITEM_TILES", "PARAM_PAIR_CAP", "PARAM_BINS_CAP", "PARAM_FORCE_FALLBACK",
-           "PARAM_WHITTED_COUNTERS", "PARAM_STATIC_SOUP", "PARAM_TEST_ALLOC_FAIL"]
+           "PARAM_WHITTED_COUNTERS", "PARAM_STATIC_SOUP", "PARAM_TEST_ALLOC_FAIL", "PARAM_TRACE_LDS_SLOTS",
+           "QUERY_CLOSEST", "QUERY_OCCLUDED", "NO_HIT", "Ray", "Hit", "RAY_DTYPE", "HIT_DTYPE", "pack_rays"]

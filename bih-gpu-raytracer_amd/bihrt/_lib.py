@@ -25,6 +25,10 @@ TRAVERSE_ANYHIT, TRAVERSE_REFERENCE = 0, 1
 PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_WHITTED_COUNTERS = 1, 2, 3, 4, 5   # bih_tree_set_param
 PARAM_STATIC_SOUP = 6
 PARAM_TEST_ALLOC_FAIL = 7   # tests: the next allocating build fails at its k-th allocation
+PARAM_TRACE_LDS_SLOTS = 8   # tests: 2 = ray queries keep only 2 stack slots per lane on chip
+QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1   # bih_trace / bih_trace_device
+NO_HIT = 0xFFFFFFFF
+MAX_RAYS = 1 << 30
 (ARR_MORTON_SORTED, ARR_TRI_INDEX, ARR_UNIQUE_MC, ARR_DUP_COUNT, ARR_FIRST_IDX, ARR_LEAF_PARENT,
  ARR_CLIP, ARR_AXIS, ARR_CHILDREN, ARR_IS_LEAF, ARR_PARENT, ARR_TRI_LO, ARR_TRI_HI) = range(13)
 
@@ -66,6 +70,16 @@ class Framebuffer(C.Structure):
 class Rows(C.Structure):
     _fields_ = [("row0", C.c_uint32), ("nrows", C.c_uint32), ("band_h", C.c_uint32),
                 ("band_step", C.c_uint32)]
+
+
+class Ray(C.Structure):
+    """bih_ray (32 bytes)."""
+    _fields_ = [("o", C.c_float * 3), ("t_lo", C.c_float), ("d", C.c_float * 3), ("reserved", C.c_float)]
+
+
+class Hit(C.Structure):
+    """bih_hit (16 bytes)."""
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_uint32)]
 
 
 class BinsStats(C.Structure):
@@ -143,12 +157,14 @@ def load():
     L.bih_host_register.argtypes = [vp, C.c_size_t]
     L.bih_host_unregister.argtypes = [vp]
     L.bih_render_history.argtypes = [vp, u32, C.POINTER(C.c_double)]
+    L.bih_trace_device.argtypes = [vp, vp, u64, u32, vp, vp]
+    L.bih_trace.argtypes = [vp, vp, u64, u32, vp]
     for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
                  "bih_render_whitted_device", "bih_render_whitted", "bih_render_device_frames",
                  "bih_bins_get_stats", "bih_reserve", "bih_tree_set_param", "bih_whitted_work",
-                 "bih_host_register", "bih_host_unregister", "bih_render_history"):
+                 "bih_host_register", "bih_host_unregister", "bih_render_history", "bih_trace_device", "bih_trace"):
         getattr(L, name).restype = i32
     _lib = L
     return L

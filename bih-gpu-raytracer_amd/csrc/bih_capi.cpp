@@ -34,6 +34,7 @@ constexpr int kRngBufs = kSlots + 1;
 // one-frame renders also take the shared grid while another render is in flight
 constexpr bool kShareOneFrame = BIH_SHARE_ONE_FRAME != 0;
 constexpr size_t kEntryBytes = 16 * bih::kBinEntryF4;   // frustum-bin list entry
+constexpr size_t kTraceCursorBytes = 256;               // the trace cursor's allocation (one u32 used)
 
 // Per-camera structures (bih_render.hip / bih_bins.hip): primary-ray records,
 // frustum bins and the tile queue of one camera.  A tree keeps kCamSets of
@@ -118,6 +119,7 @@ struct TreeParams {
     uint32_t wh_counters = 0;         // BIH_PARAM_WHITTED_COUNTERS
     uint32_t static_soup = 0;         // BIH_PARAM_STATIC_SOUP
     uint32_t test_alloc_fail = 0;     // BIH_PARAM_TEST_ALLOC_FAIL (one-shot)
+    uint32_t trace_lds = 0;           // BIH_PARAM_TRACE_LDS_SLOTS (0: bih::kTraceLds)
 };
 static const TreeParams &env_params() {
     static const TreeParams p = [] {
@@ -241,6 +243,20 @@ struct bih_tree {
     int wh_prev_slot = -1;           // the last Whitted launch's slot (its evd orders the next mask render)
     unsigned long long *wh_mask = nullptr;   // primary samples' hit masks per tile (bounce 0 through the bins)
     size_t wh_mask_cap = 0;                  // tiles
+    // ray queries (bih_trace.hip).  They use none of the render slots (whose
+    // rotation is tied to the XORWOW ring's) and no RNG state.  The cursor and
+    // the stack spill area are sized by the persistent grid, allocated by the
+    // first trace, and shared: a trace orders after the one before it
+    // (ev_trace), whatever streams they run on, and a (re)build that
+    // overwrites a tree buffer orders after the last trace.
+    uint32_t *tq_cursor = nullptr;
+    uint32_t *tq_spill = nullptr;
+    size_t tq_spill_words = 0;
+    uint32_t tq_blocks = 0;          // the persistent grid's cap (bih::trace_grid_blocks)
+    hipEvent_t ev_trace = nullptr;   // after the last trace
+    bool trace_used = false;
+    char *tq_stage = nullptr;        // bih_trace's device copies of the rays and results
+    size_t tq_stage_cap = 0;         // bytes
 };
 
 namespace {
@@ -290,6 +306,13 @@ int wait_renders(bih_tree *tr, hipStream_t st) {
             if (e != hipSuccess) return map_hip((int)e);
         }
     return BIH_OK;
+}
+
+// Orders `st` after the traces in flight (each orders after the one before
+// it, so the last one's event covers them all).
+int wait_traces(bih_tree *tr, hipStream_t st) {
+    if (!tr->trace_used || hipEventQuery(tr->ev_trace) == hipSuccess) return BIH_OK;
+    return map_hip((int)hipStreamWaitEvent(st, tr->ev_trace, 0));
 }
 
 // Orders `st` after every render in flight that read camera set `c`.
@@ -378,7 +401,8 @@ int wait_tree_buffer(bih_tree *tr, const bih::DeviceTree &b, hipStream_t st) {
         hipError_t e = hipStreamWaitEvent(st, b.ev1, 0);
         if (e != hipSuccess) return map_hip((int)e);
     }
-    return BIH_OK;
+    // (traces do not record the generation they read: any one in flight)
+    return wait_traces(tr, st);
 }
 
 int finish_build(bih_tree *tr) {
@@ -400,6 +424,7 @@ int finish_build(bih_tree *tr) {
         // first build (or after a failed one): in place, after every render
         // launched through this tree (it may run on another stream)
         int rc = wait_renders(tr, tr->stream);
+        if (rc == BIH_OK) rc = wait_traces(tr, tr->stream);
         if (rc) return rc;
         arm_fail(tr->t);
         e = bih::build_tree_device(tr->t, tr->stream, &ms);
@@ -494,6 +519,7 @@ int create_tree(int device, void *stream, bih_tree **out) {
     }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&tr->ev_rng, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&tr->ev_tree, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&tr->ev_trace, hipEventDisableTiming);
     for (CamSet &c : tr->cs) {
         if (e == hipSuccess) e = hipEventCreateWithFlags(&c.ev_bins, hipEventDisableTiming);
         if (e == hipSuccess) e = hipHostMalloc((void **)&c.bins_host, 4 * sizeof(uint32_t), hipHostMallocDefault);
@@ -527,7 +553,7 @@ const char *bih_strerror(int code) {
     case BIH_ERR_HIP: return "HIP runtime error";
     case BIH_ERR_OOM: return "out of memory";
     case BIH_ERR_NONFINITE: return "scene holds a non-finite coordinate";
-    case BIH_ERR_TOO_LARGE: return "too many triangles";
+    case BIH_ERR_TOO_LARGE: return "too many triangles, samples or rays";
     case BIH_ERR_MISMATCH: return "scene does not match the tree";
     case BIH_ERR_IO: return "file could not be opened or read";
     case BIH_ERR_PARSE: return "malformed scene file";
@@ -640,6 +666,7 @@ void bih_free(bih_tree *tr) {
     // a bins readback into bins_host may still be in flight (a failed render)
     for (CamSet &c : tr->cs)
         if (c.bins_pending) (void)hipEventSynchronize(c.ev_bins);
+    if (tr->trace_used) (void)hipEventSynchronize(tr->ev_trace);
     if (tr->bstream) (void)hipStreamSynchronize(tr->bstream);
     bih::free_tree_device(tr->t);
     bih::free_tree_device(tr->back[0]);   // (the soup is freed by whichever buffer owns it)
@@ -664,6 +691,10 @@ void bih_free(bih_tree *tr) {
     if (tr->stamps) (void)hipFree(tr->stamps);
     if (tr->wh_mem) (void)hipFree(tr->wh_mem);
     if (tr->wh_mask) (void)hipFree(tr->wh_mask);
+    if (tr->tq_cursor) (void)hipFree(tr->tq_cursor);
+    if (tr->tq_spill) (void)hipFree(tr->tq_spill);
+    if (tr->tq_stage) (void)hipFree(tr->tq_stage);
+    if (tr->ev_trace) (void)hipEventDestroy(tr->ev_trace);
     for (int k = 0; k < kSlots; ++k) {
         if (tr->ev0[k]) (void)hipEventDestroy(tr->ev0[k]);
         if (tr->evd[k]) (void)hipEventDestroy(tr->evd[k]);
@@ -721,7 +752,8 @@ int bih_tree_get_info(const bih_tree *tr, bih_tree_info *info) {
                           (size_t)kSlots * 2 * tr->chunk_cap +
                           (tr->q_count ? (size_t)kSlots * 2 * bih::kBinSetWords : 0) +
                           (size_t)kSlots * tr->fbq_cap * 8) * 4 +
-                         (tr->wh_mem ? bih::whitted_bytes(tr->wh_rays) : 0) + tr->wh_mask_cap * 8 + tr->stamp_cap * 8;
+                         (tr->wh_mem ? bih::whitted_bytes(tr->wh_rays) : 0) + tr->wh_mask_cap * 8 + tr->stamp_cap * 8 +
+                         (tr->tq_cursor ? kTraceCursorBytes : 0) + tr->tq_spill_words * 4 + tr->tq_stage_cap;
     info->build_ms = tr->build_ms;
     info->device_allocs = tr->allocs + tr->t.allocs + tr->back[0].allocs + tr->back[1].allocs;
     return BIH_OK;
@@ -1856,6 +1888,10 @@ int bih_tree_set_param(bih_tree *tr, int param, uint64_t value) {
         if (value > 64) return BIH_ERR_INVALID;
         tr->prm.test_alloc_fail = (uint32_t)value;
         return BIH_OK;
+    case BIH_PARAM_TRACE_LDS_SLOTS:
+        if (value != 0 && value != (uint64_t)bih::kTraceLdsTest) return BIH_ERR_INVALID;
+        tr->prm.trace_lds = (uint32_t)value;
+        return BIH_OK;
     default:
         return BIH_ERR_INVALID;
     }
@@ -2056,6 +2092,95 @@ int bih_render_whitted(const bih_scene *scene, const bih_tree *ctr, const bih_ca
     hipError_t e = hipMemcpyAsync(fb->rgba, tr->fb, P * 4, hipMemcpyDeviceToHost, tr->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(tr->stream);
     return map_hip((int)e);
+}
+
+// The trace's cursor and stack spill area (sized by the persistent grid, not
+// by the ray count: allocated once).
+static int ensure_trace(bih_tree *tr) {
+    if (tr->tq_cursor && tr->tq_spill) return BIH_OK;
+    if (!tr->tq_blocks) tr->tq_blocks = bih::trace_grid_blocks(tr->t.device);
+    const size_t words = bih::trace_spill_words(tr->tq_blocks);
+    hipError_t e = hipSuccess;
+    if (!tr->tq_cursor) e = tree_malloc(tr, &tr->tq_cursor, kTraceCursorBytes);
+    if (e == hipSuccess && !tr->tq_spill) {
+        e = tree_malloc(tr, &tr->tq_spill, words * sizeof(uint32_t));
+        if (e == hipSuccess) tr->tq_spill_words = words;
+    }
+    return map_hip((int)e);
+}
+
+// bih_trace_device under the tree's lock, arguments checked.
+static int trace_locked(bih_tree *tr, const void *d_rays, uint32_t n, uint32_t query, void *d_out, hipStream_t st) {
+    if (!tr->t.hdr) return BIH_ERR_INVALID;   // no tree was ever built into this buffer
+    int rc = ensure_trace(tr);
+    if (rc) return rc;
+    // after the last (re)build, as renders; no RNG state is read or waited for
+    if (tr->tree_pending && hipEventQuery(tr->ev_tree) == hipSuccess) tr->tree_pending = false;
+    if (tr->tree_pending) {
+        const hipError_t e = hipStreamWaitEvent(st, tr->ev_tree, 0);
+        if (e != hipSuccess) return map_hip((int)e);
+    }
+    // the cursor and the spill area are shared: after the trace before this one
+    rc = wait_traces(tr, st);
+    if (rc) return rc;
+    rc = map_hip(bih::launch_trace(tr->t, d_rays, n, query == BIH_QUERY_OCCLUDED, d_out, tr->prm.trace_lds,
+                                   tr->tq_cursor, tr->tq_spill, tr->tq_blocks, st));
+    // (a failed launch may have left work on st that uses the cursor: the event covers it)
+    const hipError_t e = hipEventRecord(tr->ev_trace, st);
+    if (e == hipSuccess) tr->trace_used = true;
+    if (rc) return rc;
+    return map_hip((int)e);
+}
+
+// Argument checks of both entries, in the header's order; none touches the
+// tree or a device.
+static int trace_check(const bih_tree *tr, const void *rays, uint64_t n_rays, uint32_t query, const void *out) {
+    if (!tr) return BIH_ERR_INVALID;
+    if (query != BIH_QUERY_CLOSEST && query != BIH_QUERY_OCCLUDED) return BIH_ERR_INVALID;
+    if (n_rays > BIH_MAX_RAYS) return BIH_ERR_TOO_LARGE;
+    if (n_rays > 0 && (!rays || !out)) return BIH_ERR_INVALID;
+    return BIH_OK;
+}
+
+int bih_trace_device(const bih_tree *ctr, const bih_ray *d_rays, uint64_t n_rays, uint32_t query, void *d_out,
+                     void *stream) {
+    const int rc = trace_check(ctr, d_rays, n_rays, query, d_out);
+    if (rc || n_rays == 0) return rc;
+    // the kernel moves rays and hits as 16-byte words
+    if (((uintptr_t)d_rays & 15u) || (query == BIH_QUERY_CLOSEST && ((uintptr_t)d_out & 15u))) return BIH_ERR_INVALID;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    return trace_locked(tr, d_rays, (uint32_t)n_rays, query, d_out, stream ? (hipStream_t)stream : tr->stream);
+}
+
+int bih_trace(const bih_tree *ctr, const bih_ray *rays, uint64_t n_rays, uint32_t query, void *out) {
+    int rc = trace_check(ctr, rays, n_rays, query, out);
+    if (rc || n_rays == 0) return rc;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    const size_t in_bytes = (size_t)n_rays * sizeof(bih_ray);
+    const size_t out_bytes = (size_t)n_rays * (query == BIH_QUERY_CLOSEST ? sizeof(bih_hit) : 1);
+    if (tr->tq_stage_cap < in_bytes + out_bytes) {
+        // (its only users are calls of this function, which wait for their work)
+        if (tr->tq_stage) (void)hipFree(tr->tq_stage);
+        tr->tq_stage = nullptr;
+        tr->tq_stage_cap = 0;
+        const hipError_t e = tree_malloc(tr, &tr->tq_stage, in_bytes + out_bytes);
+        if (e != hipSuccess) return map_hip((int)e);
+        tr->tq_stage_cap = in_bytes + out_bytes;
+    }
+    char *d_in = tr->tq_stage, *d_res = tr->tq_stage + in_bytes;   // (in_bytes: a multiple of 32)
+    hipError_t e = hipMemcpyAsync(d_in, rays, in_bytes, hipMemcpyHostToDevice, tr->stream);
+    if (e != hipSuccess) return map_hip((int)e);
+    rc = trace_locked(tr, d_in, (uint32_t)n_rays, query, d_res, tr->stream);
+    if (rc == BIH_OK) {
+        e = hipMemcpyAsync(out, d_res, out_bytes, hipMemcpyDeviceToHost, tr->stream);
+        if (e != hipSuccess) rc = map_hip((int)e);
+    }
+    e = hipStreamSynchronize(tr->stream);
+    return rc ? rc : map_hip((int)e);
 }
 
 int bih_sync(const bih_tree *tr, void *stream) {

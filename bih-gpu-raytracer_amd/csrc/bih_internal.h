@@ -318,6 +318,18 @@ size_t whitted_bytes(uint64_t rays);
 int launch_whitted(const RenderArgs &a, void *mem, uint64_t rays, uint32_t *d_hits, void *stream, void *ev_k0,
                    void *ev_k1, bool count, const unsigned long long *hit_mask = nullptr, uint32_t tiles_x = 0);
 int whitted_work(const void *mem, uint64_t rays, uint32_t ray_counts[9], unsigned long long work[18], void *stream);
+// ray queries (bih_trace.hip): n caller rays (bih_ray) against tree t, results
+// (bih_hit, or one byte per ray when occluded) to d_out in caller order.
+// cursor: one u32, zeroed by the launch; spill: trace_spill_words(max_blocks)
+// u32, max_blocks = trace_grid_blocks(device), the persistent grid's cap.
+// lds_slots: kTraceLdsTest selects the instantiation that keeps only that many
+// stack slots per lane on chip (BIH_PARAM_TRACE_LDS_SLOTS), anything else kTraceLds.
+constexpr int kTraceLds = 10;       // as kWLds (bih_whitted.hip)
+constexpr int kTraceLdsTest = 2;
+uint32_t trace_grid_blocks(int device);
+size_t trace_spill_words(uint32_t blocks);
+int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, bool occluded, void *d_out,
+                 uint32_t lds_slots, uint32_t *cursor, uint32_t *spill, uint32_t max_blocks, void *stream);
 int launch_rng_init(uint32_t *rng, uint32_t w, uint32_t row0, uint32_t nrows, uint32_t band_h,
                     uint32_t band_step, uint64_t seed, uint64_t skip, int device, void *stream);
 // dst = src's per-pixel state advanced by `steps` draws (planes of `pixels`; dst may be src)

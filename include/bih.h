@@ -234,7 +234,74 @@ int bih_reserve(bih_tree *tree, uint32_t w, uint32_t h, uint32_t spp, const bih_
                                         allocation (1..64; BIH_ERR_OOM); the tree
                                         frees what it had allocated and stays
                                         usable (0 = off)                       */
+#define BIH_PARAM_TRACE_LDS_SLOTS 8  /* tests: 2 = ray queries (bih_trace*) run
+                                        the kernel instantiation that keeps only
+                                        2 stack slots per lane on chip, so that
+                                        the memory part of the stack is used;
+                                        0 = the default; no result changes     */
 int bih_tree_set_param(bih_tree *tree, int param, uint64_t value);
+
+/* Ray queries: closest hit and occlusion for the caller's own rays (what
+ * Embree calls rtcIntersect / rtcOccluded; the reference stops at Color()).
+ *
+ * Semantics: config C4's closest hit below, the
+ * oracle's traverse_closest, not a new rule.
+ *  - Closest: the hit is min (t, sorted position) over the triangles the
+ *    reference walk tests (TraverseTree, CUDAKernels.cu:227-368), with
+ *    t_lo < t < FLT_MAX.  Once a hit is known, a node entered beyond it is
+ *    popped unvisited and tMax is clamped to it.  With t_lo > 0 the walk
+ *    interval starts at max(scene-box entry, t_lo).  Every f32 expression is in
+ *    the oracle's order, separately rounded.  This is the WALK's closest hit:
+ *    the walk culls with f32 plane distances, so in rare plane-rounding cases
+ *    it differs from a brute-force minimum over all triangles
+ *    (tests/test_whitted.py::test_oracle_closest_equals_brute_force shows the
+ *    size of that effect).
+ *  - Hit record: t = hit distance (in units of |d|: P = o + t*d); prim = the
+ *    triangle's index in file order (BIH_ARR_TRI_INDEX[sorted position]; of
+ *    equal t the lower sorted position wins); u, v = the Moeller-Trumbore
+ *    barycentrics of the accepted triangle as the reference's test computes
+ *    them (e1 = v1-v0, e2 = v2-v0, p = cross(d, e2), det = e1.p,
+ *    inv = 1.0f/det, s = o-v0, u = (s.p)*inv, q = cross(s, e1), v = (d.q)*inv,
+ *    dot = (x+y)+z), so P = (1-u-v) v0 + u v1 + v v2.  A miss is
+ *    {FLT_MAX, 0, 0, BIH_NO_HIT}.
+ *  - Occluded: 1 exactly when the closest query of the same ray has
+ *    prim != BIH_NO_HIT, else 0.  The walk stops at the first accepted
+ *    triangle; until then it is the closest walk (same visit order, interval
+ *    clamp and accept test).
+ *  - Rays: d need not be normalised.  `reserved` is not read; set it to 0.
+ *    Like the reference's test, triangles are one-sided (det > 1e-6 only).
+ *    Non-finite or zero directions and origins are legal: the result is
+ *    whatever the arithmetic above gives (the walk descends or pops on every
+ *    step, so it ends).
+ * Errors, checked in this order before the tree or a device is touched: NULL
+ * tree -> BIH_ERR_INVALID; unknown query -> BIH_ERR_INVALID; n_rays >
+ * BIH_MAX_RAYS -> BIH_ERR_TOO_LARGE; n_rays > 0 with NULL rays or out ->
+ * BIH_ERR_INVALID; n_rays == 0 -> BIH_OK, nothing launched.
+ * Ordering: a trace runs after the last bih_build / bih_rebuild, and a
+ * rebuild runs after the traces in flight.  No RNG state is read, and renders
+ * are not ordered against traces.  The tree owns one ray cursor and one stack
+ * spill area, sized by the kernel's persistent grid (not by n_rays; allocated
+ * by the first trace, counted in bih_tree_info): two traces of one tree on
+ * two streams are both right because the second is ordered after the first
+ * with an event -- they do not overlap on the device. */
+#define BIH_NO_HIT      0xFFFFFFFFu
+#define BIH_MAX_RAYS    (1u << 30)
+#define BIH_QUERY_CLOSEST   0u
+#define BIH_QUERY_OCCLUDED  1u
+
+typedef struct bih_ray { float o[3]; float t_lo; float d[3]; float reserved; } bih_ray; /* 32 B */
+typedef struct bih_hit { float t, u, v; uint32_t prim; } bih_hit;                       /* 16 B */
+
+/* d_rays, d_out: device memory on the tree's device, 16-byte aligned (else
+ * BIH_ERR_INVALID).  Asynchronous on `stream` (NULL = the tree's stream);
+ * bih_sync waits.  d_out: bih_hit[n_rays] (CLOSEST) or uint8_t[n_rays]
+ * (OCCLUDED: 1 / 0), in the rays' order. */
+int bih_trace_device(const bih_tree *tree, const bih_ray *d_rays, uint64_t n_rays,
+                     uint32_t query, void *d_out, void *stream);
+/* Host rays in, host results out; synchronous.  Stages through device buffers
+ * the tree owns (grown on demand). */
+int bih_trace(const bih_tree *tree, const bih_ray *rays, uint64_t n_rays,
+              uint32_t query, void *out);
 
 /* Config C4 (BASELINE.json configs[3]): 8 bounces of mirror (Whitted)
  * reflection per primary ray.  The reference has primary rays only
