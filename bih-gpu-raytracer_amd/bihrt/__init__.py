@@ -20,8 +20,8 @@ import numpy as np
 
 from . import scenes  # noqa: F401
 from ._lib import (PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_STATIC_SOUP,
-                   PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS,
-                   NO_HIT, QUERY_CLOSEST, QUERY_OCCLUDED, Hit, Ray, TRAVERSE_ANYHIT,
+                   PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS, PARAM_GBUFFER_MASK,
+                   NO_HIT, QUERY_CLOSEST, QUERY_OCCLUDED, GBuffer, Hit, Ray, TRAVERSE_ANYHIT,
                    TRAVERSE_REFERENCE, BihError, Camera, Framebuffer, Rows, Scene, TreeInfo, check, load)
 from . import _lib
 
@@ -49,6 +49,11 @@ def camera_ray_bound(cam: Camera) -> np.ndarray:
 # numpy views of bih_ray / bih_hit arrays
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_lo", np.float32), ("d", np.float32, 3), ("reserved", np.float32)])
 HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("prim", np.uint32)])
+
+
+# G-buffer pixel planes (bih_gbuffer): name -> (dtype, components per pixel)
+GBUFFER_PLANES = {"depth": (np.float32, 1), "prim": (np.uint32, 1), "bary": (np.float32, 2),
+                  "normal": (np.float32, 3), "coverage": (np.uint32, 1)}
 
 
 def pack_rays(orig, dirs, t_lo=0.0) -> np.ndarray:
@@ -250,6 +255,42 @@ class Renderer:
                                                C.c_void_p(out_ptr), C.c_void_p(hits_ptr or 0),
                                                C.c_void_p(stream or 0)), "bih_render_whitted_device")
 
+    def render_gbuffer(self, frame: int | None = None, rows: Rows | None = None,
+                       planes=("depth", "prim", "bary", "normal", "coverage"), hits: bool = False) -> dict:
+        """One frame's G-buffer into host arrays (bih_render_gbuffer; synchronous):
+        a dict of the pixel planes asked for (GBUFFER_PLANES), shaped (nrows, w) or
+        (nrows, w, k), from each pixel's hit sample of smallest (t, s); with
+        `hits` also "hits", (nrows*w*spp,) HIT_DTYPE, sample = local pixel * spp + s.
+        A pixel without a hit holds FLT_MAX, NO_HIT, zeros and coverage 0."""
+        f = self.frame if frame is None else frame
+        nrows = rows.nrows if rows is not None else self.h
+        out, gb = {}, GBuffer()
+        for name in planes:
+            dt, k = GBUFFER_PLANES[name]
+            out[name] = np.zeros((nrows, self.w) + ((k,) if k > 1 else ()), dt)
+            setattr(gb, name, out[name].ctypes.data)
+        if hits:
+            out["hits"] = np.zeros(nrows * self.w * self.spp, HIT_DTYPE)
+            gb.hits = out["hits"].ctypes.data
+        check(load().bih_render_gbuffer(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
+                                        self.seed, C.byref(rows) if rows is not None else None, C.byref(gb)),
+              "bih_render_gbuffer")
+        self.frame = f + 1
+        return out
+
+    def render_gbuffer_device(self, ptrs: dict, frame: int, rows: Rows | None = None, stream: int | None = None):
+        """Asynchronous G-buffer render into device memory (bih_render_gbuffer_device):
+        ptrs maps plane names ("hits", "depth", "prim", "bary", "normal", "coverage")
+        to device pointers; planes left out are not written."""
+        gb = GBuffer()
+        for name, ptr in ptrs.items():
+            if name != "hits" and name not in GBUFFER_PLANES:
+                raise KeyError(name)
+            setattr(gb, name, ptr or None)
+        check(load().bih_render_gbuffer_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
+                                               frame, self.seed, C.byref(rows) if rows is not None else None,
+                                               C.byref(gb), C.c_void_p(stream or 0)), "bih_render_gbuffer_device")
+
     def whitted_work(self) -> dict:
         """Per bounce d = 0..8 of the last Whitted render (run with
         PARAM_WHITTED_COUNTERS on): rays traced, BIH nodes entered, triangles
@@ -345,4 +386,4 @@ __all__ = ["GPUArrayManager", "Renderer", "Model", "load_obj", "host_register", 
            "camera_ray_bound", "device_count", "unpack_rgba", "write_ppm", "scenes", "TRAVERSE_ANYHIT",
            "TRAVERSE_REFERENCE", "PARAM_ITEM_TILES", "PARAM_PAIR_CAP", "PARAM_BINS_CAP", "PARAM_FORCE_FALLBACK",
            "PARAM_WHITTED_COUNTERS", "PARAM_STATIC_SOUP", "PARAM_TEST_ALLOC_FAIL", "PARAM_TRACE_LDS_SLOTS",
-           "QUERY_CLOSEST", "QUERY_OCCLUDED", "NO_HIT", "Ray", "Hit", "RAY_DTYPE", "HIT_DTYPE", "pack_rays"]
+           "PARAM_GBUFFER_MASK", "GBuffer", "GBUFFER_PLANES", "QUERY_CLOSEST", "QUERY_OCCLUDED", "NO_HIT", "Ray", "Hit", "RAY_DTYPE", "HIT_DTYPE", "pack_rays"]

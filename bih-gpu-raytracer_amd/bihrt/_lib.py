@@ -26,6 +26,7 @@ PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_WH
 PARAM_STATIC_SOUP = 6
 PARAM_TEST_ALLOC_FAIL = 7   # tests: the next allocating build fails at its k-th allocation
 PARAM_TRACE_LDS_SLOTS = 8   # tests: 2 = ray queries keep only 2 stack slots per lane on chip
+PARAM_GBUFFER_MASK = 9      # tests / A-B: 0 = G-buffer renders walk every sample (no bins hit mask)
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1   # bih_trace / bih_trace_device
 NO_HIT = 0xFFFFFFFF
 MAX_RAYS = 1 << 30
@@ -80,6 +81,12 @@ class Ray(C.Structure):
 class Hit(C.Structure):
     """bih_hit (16 bytes)."""
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_uint32)]
+
+
+class GBuffer(C.Structure):
+    """bih_gbuffer: six plane pointers, any of them NULL (not written)."""
+    _fields_ = [("hits", C.c_void_p), ("depth", C.c_void_p), ("prim", C.c_void_p), ("bary", C.c_void_p),
+                ("normal", C.c_void_p), ("coverage", C.c_void_p)]
 
 
 class BinsStats(C.Structure):
@@ -159,12 +166,17 @@ def load():
     L.bih_render_history.argtypes = [vp, u32, C.POINTER(C.c_double)]
     L.bih_trace_device.argtypes = [vp, vp, u64, u32, vp, vp]
     L.bih_trace.argtypes = [vp, vp, u64, u32, vp]
+    L.bih_render_gbuffer_device.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                            C.POINTER(GBuffer), vp]
+    L.bih_render_gbuffer.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                     C.POINTER(GBuffer)]
     for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
                  "bih_render_whitted_device", "bih_render_whitted", "bih_render_device_frames",
                  "bih_bins_get_stats", "bih_reserve", "bih_tree_set_param", "bih_whitted_work",
-                 "bih_host_register", "bih_host_unregister", "bih_render_history", "bih_trace_device", "bih_trace"):
+                 "bih_host_register", "bih_host_unregister", "bih_render_history", "bih_trace_device", "bih_trace",
+                 "bih_render_gbuffer_device", "bih_render_gbuffer"):
         getattr(L, name).restype = i32
     _lib = L
     return L

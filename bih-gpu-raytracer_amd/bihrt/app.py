@@ -14,6 +14,7 @@ Mirrors the reference application shell without windowing or GL interop:
 
 usage:  python -m bihrt --mesh sponza --resources path/to/resources --frames 10 \
             --out frames/f%04d.ppm [--width 640 --height 480 --no-rebuild]
+            [--gbuffer frames/g%04d.npz]   (depth, prim, bary, normal, coverage per written frame)
         python -m bihrt --obj file.obj ...     (explicit path)
         python -m bihrt --scene cornell|torus|soup[:N] ...   (built-in scenes)
 """
@@ -70,9 +71,11 @@ class App:
         return tris.shape[0]
 
     def run(self, frames: int, out_pattern: str | None = None, rebuild: bool = True,
-            every: int = 1):
+            every: int = 1, gbuffer_pattern: str | None = None):
         """App::Run for a fixed number of frames: Renderer::Render each frame
-        (BIH rebuild + render), optional PPM output; returns the frames."""
+        (BIH rebuild + render), optional PPM output; returns the frames.
+        gbuffer_pattern: one .npz of the frame's G-buffer planes
+        (Renderer.render_gbuffer) per written frame."""
         assert self.renderer is not None, "load_models first"
         imgs = []
         last = time.perf_counter()
@@ -90,6 +93,12 @@ class App:
                 if d:
                     os.makedirs(d, exist_ok=True)
                 write_ppm(path, img)
+            if gbuffer_pattern and f % every == 0:
+                path = gbuffer_pattern % f if "%" in gbuffer_pattern else gbuffer_pattern
+                d = os.path.dirname(path)
+                if d:
+                    os.makedirs(d, exist_ok=True)
+                np.savez(path, **self.renderer.render_gbuffer(f))
             imgs.append(img)
         return imgs
 
@@ -107,6 +116,8 @@ def main(argv=None) -> int:
     ap.add_argument("--spp", type=int, default=RAYS_PER_PIXEL)
     ap.add_argument("--frames", type=int, default=1)
     ap.add_argument("--out", default=None, help="PPM path; '%%d' formats the frame number")
+    ap.add_argument("--gbuffer", default=None, metavar="PATTERN",
+                    help=".npz path of the G-buffer planes of each written frame; '%%d' formats the frame number")
     ap.add_argument("--every", type=int, default=1, help="write every k-th frame")
     ap.add_argument("--no-rebuild", action="store_true",
                     help="build once (the reference rebuilds every frame)")
@@ -124,5 +135,5 @@ def main(argv=None) -> int:
         scene = builtin_scene(a.scene)
     app = App(a.width, a.height, a.spp, device=a.device)
     app.load_models(scene)
-    app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every)
+    app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every, gbuffer_pattern=a.gbuffer)
     return 0

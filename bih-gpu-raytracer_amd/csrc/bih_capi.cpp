@@ -120,6 +120,7 @@ struct TreeParams {
     uint32_t static_soup = 0;         // BIH_PARAM_STATIC_SOUP
     uint32_t test_alloc_fail = 0;     // BIH_PARAM_TEST_ALLOC_FAIL (one-shot)
     uint32_t trace_lds = 0;           // BIH_PARAM_TRACE_LDS_SLOTS (0: bih::kTraceLds)
+    uint32_t gb_mask = 1;             // BIH_PARAM_GBUFFER_MASK
 };
 static const TreeParams &env_params() {
     static const TreeParams p = [] {
@@ -257,6 +258,18 @@ struct bih_tree {
     bool trace_used = false;
     char *tq_stage = nullptr;        // bih_trace's device copies of the rays and results
     size_t tq_stage_cap = 0;         // bytes
+    // G-buffer renders (bih_gbuffer.hip) take a render slot, as Whitted
+    // renders do (the XORWOW ring), and borrow the trace's cursor and spill
+    // area (so they join the ev_trace chain).  Their own: the primary
+    // samples' hit masks per tile with the scratch image the mask render
+    // writes its pixels to, and the host entry's device planes.
+    unsigned long long *gb_mask = nullptr;
+    size_t gb_mask_cap = 0;          // tiles
+    uint32_t *gb_scratch = nullptr;
+    size_t gb_scratch_cap = 0;       // pixels
+    int gb_prev_slot = -1;           // the last G-buffer launch's slot (its evd orders the next mask render)
+    char *gb_stage = nullptr;        // bih_render_gbuffer's device planes
+    size_t gb_stage_cap = 0;         // bytes
 };
 
 namespace {
@@ -694,6 +707,9 @@ void bih_free(bih_tree *tr) {
     if (tr->tq_cursor) (void)hipFree(tr->tq_cursor);
     if (tr->tq_spill) (void)hipFree(tr->tq_spill);
     if (tr->tq_stage) (void)hipFree(tr->tq_stage);
+    if (tr->gb_mask) (void)hipFree(tr->gb_mask);
+    if (tr->gb_scratch) (void)hipFree(tr->gb_scratch);
+    if (tr->gb_stage) (void)hipFree(tr->gb_stage);
     if (tr->ev_trace) (void)hipEventDestroy(tr->ev_trace);
     for (int k = 0; k < kSlots; ++k) {
         if (tr->ev0[k]) (void)hipEventDestroy(tr->ev0[k]);
@@ -753,7 +769,8 @@ int bih_tree_get_info(const bih_tree *tr, bih_tree_info *info) {
                           (tr->q_count ? (size_t)kSlots * 2 * bih::kBinSetWords : 0) +
                           (size_t)kSlots * tr->fbq_cap * 8) * 4 +
                          (tr->wh_mem ? bih::whitted_bytes(tr->wh_rays) : 0) + tr->wh_mask_cap * 8 + tr->stamp_cap * 8 +
-                         (tr->tq_cursor ? kTraceCursorBytes : 0) + tr->tq_spill_words * 4 + tr->tq_stage_cap;
+                         (tr->tq_cursor ? kTraceCursorBytes : 0) + tr->tq_spill_words * 4 + tr->tq_stage_cap +
+                         tr->gb_mask_cap * 8 + tr->gb_scratch_cap * 4 + tr->gb_stage_cap;
     info->build_ms = tr->build_ms;
     info->device_allocs = tr->allocs + tr->t.allocs + tr->back[0].allocs + tr->back[1].allocs;
     return BIH_OK;
@@ -1892,6 +1909,10 @@ int bih_tree_set_param(bih_tree *tr, int param, uint64_t value) {
         if (value != 0 && value != (uint64_t)bih::kTraceLdsTest) return BIH_ERR_INVALID;
         tr->prm.trace_lds = (uint32_t)value;
         return BIH_OK;
+    case BIH_PARAM_GBUFFER_MASK:
+        if (value > 1) return BIH_ERR_INVALID;
+        tr->prm.gb_mask = (uint32_t)value;
+        return BIH_OK;
     default:
         return BIH_ERR_INVALID;
     }
@@ -2179,6 +2200,212 @@ int bih_trace(const bih_tree *ctr, const bih_ray *rays, uint64_t n_rays, uint32_
         e = hipMemcpyAsync(out, d_res, out_bytes, hipMemcpyDeviceToHost, tr->stream);
         if (e != hipSuccess) rc = map_hip((int)e);
     }
+    e = hipStreamSynchronize(tr->stream);
+    return rc ? rc : map_hip((int)e);
+}
+
+// Argument checks of both G-buffer entries, in the header's order; none
+// touches the tree or a device.  *rows: the rows of the call.
+static int gbuffer_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                         const bih_rows *rows_in, const bih_gbuffer *pl, bih_rows *rows) {
+    if (!tr || !cam || !pl) return BIH_ERR_INVALID;
+    if (w == 0 || h == 0 || spp == 0) return BIH_ERR_INVALID;
+    if (spp > 64) return BIH_ERR_INVALID;   // one wave holds a pixel's samples
+    if (!pl->hits && !pl->depth && !pl->prim && !pl->bary && !pl->normal && !pl->coverage) return BIH_ERR_INVALID;
+    *rows = rows_in ? *rows_in : bih_rows{0, h, h, 1};
+    if (rows->nrows > 0) {
+        if (rows->band_h == 0 || rows->band_step == 0) return BIH_ERR_INVALID;
+        const uint64_t lr = rows->nrows - 1;
+        const uint64_t ylast = rows->row0 + (lr / rows->band_h) * (uint64_t)rows->band_h * rows->band_step +
+                               (lr % rows->band_h);
+        if (ylast >= h) return BIH_ERR_INVALID;
+    }
+    // u32 sample ids and tile cursor (as bih_render_whitted_device)
+    if ((uint64_t)h * w * spp > 0xFFFFFFFFull - (1ull << 20)) return BIH_ERR_TOO_LARGE;
+    if ((uintptr_t)pl->hits & 15u) return BIH_ERR_INVALID;   // records move as 16-byte words
+    return BIH_OK;
+}
+
+// bih_render_gbuffer_device under the tree's lock, arguments checked, nrows > 0.
+static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                          uint32_t frame, uint64_t seed, const bih_rows &rows, const bih_gbuffer &pl,
+                          void *stream) {
+    if (!tr->t.hdr) return BIH_ERR_INVALID;   // no tree was ever built into this buffer
+    hipStream_t st = stream ? (hipStream_t)stream : tr->stream;
+    int rc = ensure_trace(tr);
+    if (rc) return rc;
+    const size_t P = (size_t)rows.nrows * w;
+    // The primary samples' any-hit result from the frustum bins, as bounce 0
+    // of a Whitted render: the any-hit render of the same frame leaves per
+    // tile the mask of its samples that hit, and only those are walked (a
+    // proven miss has no closest hit: same visit set, same test).  Its pixels
+    // go to a scratch image.  BIH_PARAM_GBUFFER_MASK = 0: every sample is walked.
+    unsigned long long *mask = nullptr;
+    if (tr->prm.gb_mask && bins_enabled() && (spp & (spp - 1)) == 0 && tr->t.u > 1) {
+        uint32_t tiles_x = 0;
+        const size_t ntiles = (size_t)bih::gbuffer_tiles(w, rows.nrows, spp, &tiles_x);
+        if (tr->gb_mask_cap < ntiles || tr->gb_scratch_cap < P) {
+            rc = drain_renders(tr);
+            if (rc) return rc;
+            if (tr->gb_mask_cap < ntiles) {
+                if (tr->gb_mask) (void)hipFree(tr->gb_mask);
+                tr->gb_mask = nullptr;
+                tr->gb_mask_cap = 0;
+                const hipError_t e = tree_malloc(tr, &tr->gb_mask, ntiles * 8);
+                if (e != hipSuccess) return map_hip((int)e);
+                tr->gb_mask_cap = ntiles;
+            }
+            if (tr->gb_scratch_cap < P) {
+                if (tr->gb_scratch) (void)hipFree(tr->gb_scratch);
+                tr->gb_scratch = nullptr;
+                tr->gb_scratch_cap = 0;
+                const hipError_t e = tree_malloc(tr, &tr->gb_scratch, P * 4);
+                if (e != hipSuccess) return map_hip((int)e);
+                tr->gb_scratch_cap = P;
+            }
+        } else if (tr->gb_prev_slot >= 0 && tr->used[tr->gb_prev_slot]) {
+            // the mask and the scratch image are rewritten in place: after the
+            // last G-buffer launch (it reads the mask), whatever stream it ran on
+            const hipError_t e = hipStreamWaitEvent(st, tr->evd[tr->gb_prev_slot], 0);
+            if (e != hipSuccess) return map_hip((int)e);
+        }
+        const int mrc = render_device_impl(tr, cam, w, h, spp, frame, seed, &rows, BIH_TRAVERSE_ANYHIT,
+                                           tr->gb_scratch, nullptr, stream, 1, 0, tr->gb_mask, true);
+        if (mrc == BIH_OK) mask = tr->gb_mask;
+        else if (mrc != kRenderPerFrame) return mrc;
+    }
+    // the launch takes a render slot (the XORWOW ring's rotation): after every
+    // render in flight and the last writer of the ring; after the last
+    // (re)build; and after the trace or G-buffer launch before it (the shared
+    // cursor and spill area)
+    rc = wait_renders(tr, st);
+    if (rc) return rc;
+    {
+        const hipError_t e = wait_rng(tr, st);
+        if (e != hipSuccess) return map_hip((int)e);
+    }
+    if (tr->tree_pending && hipEventQuery(tr->ev_tree) == hipSuccess) tr->tree_pending = false;
+    if (tr->tree_pending) {
+        const hipError_t e = hipStreamWaitEvent(st, tr->ev_tree, 0);
+        if (e != hipSuccess) return map_hip((int)e);
+    }
+    rc = wait_traces(tr, st);
+    if (rc) return rc;
+    rc = prepare_rng(tr, w, spp, frame, seed, rows, st);
+    if (rc) return rc;
+    RngGuard rng_guard{tr};
+    const int cur = tr->rng_cur, nxt = (cur + 1) % kRngBufs;
+    rc = map_hip(bih::launch_rng_advance(rng_buf(tr, cur), rng_buf(tr, nxt), P, 2 * spp, tr->t.device, st));
+    if (rc) return rc;
+    hipError_t e = hipEventRecord(tr->ev_rng, st);
+    if (e != hipSuccess) return map_hip((int)e);
+    tr->rng_pending = true;
+    bih::RenderArgs a;
+    memcpy(a.cam, cam, sizeof a.cam);
+    a.w = w;
+    a.h = h;
+    a.spp = spp;
+    a.row0 = rows.row0;
+    a.nrows = rows.nrows;
+    a.band_h = rows.band_h;
+    a.band_step = rows.band_step;
+    uint32_t v[5], d0;
+    bih::xorwow_seed(seed, v, &d0);
+    a.d_base = d0 + (uint32_t)((uint64_t)2 * spp * frame) * 362437u;
+    a.rng_in = rng_buf(tr, cur);
+    bih::GBufferPlanes p;
+    p.hits = pl.hits;
+    p.depth = pl.depth;
+    p.prim = pl.prim;
+    p.bary = pl.bary;
+    p.normal = pl.normal;
+    p.coverage = pl.coverage;
+    const int slot = tr->slot;
+    if (tr->timing) {
+        e = hipEventRecord(tr->ev0[slot], st);
+        if (e != hipSuccess) return map_hip((int)e);
+    }
+    rc = bih::launch_gbuffer(tr->t, a, p, mask, tr->prm.trace_lds, tr->tq_cursor, tr->tq_spill, tr->tq_blocks, st);
+    // (a failed launch may have left work on st that uses the cursor: the event covers it)
+    e = hipEventRecord(tr->ev_trace, st);
+    if (e == hipSuccess) tr->trace_used = true;
+    if (rc) return map_hip(rc);
+    if (e != hipSuccess) return map_hip((int)e);
+    if (tr->timing) {
+        e = hipEventRecord(tr->ev1[slot], st);
+        if (e == hipSuccess) e = hipEventRecord(tr->ev2[slot], st);
+        if (e != hipSuccess) return map_hip((int)e);
+    }
+    tr->last_timed = tr->timing;
+    tr->slot_timed[slot] = tr->timing;
+    e = hipEventRecord(tr->evd[slot], st);
+    if (e != hipSuccess) return map_hip((int)e);
+    tr->used[slot] = true;
+    tr->slot_gen[slot] = tr->gen;
+    note_stream(tr, slot, st);
+    tr->slot_cs[slot] = -1;            // reads no camera set
+    tr->last_slot = slot;
+    tr->slot = (slot + 1) % kSlots;
+    tr->gb_prev_slot = slot;
+    tr->rng_cur = nxt;
+    rng_guard.armed = false;
+    return BIH_OK;
+}
+
+int bih_render_gbuffer_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                              uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_gbuffer *d_planes,
+                              void *stream) {
+    bih_rows rows;
+    const int rc = gbuffer_check(ctr, cam, w, h, spp, rows_in, d_planes, &rows);
+    if (rc || rows.nrows == 0) return rc;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    return gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, *d_planes, stream);
+}
+
+int bih_render_gbuffer(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                       uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_gbuffer *host_planes) {
+    bih_rows rows;
+    int rc = gbuffer_check(ctr, cam, w, h, spp, rows_in, host_planes, &rows);
+    if (rc || rows.nrows == 0) return rc;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    // device planes of the ones asked for, each at a multiple of 16 bytes
+    const size_t P = (size_t)rows.nrows * w;
+    void *const host[6] = {host_planes->hits, host_planes->depth, host_planes->prim,
+                           host_planes->bary, host_planes->normal, host_planes->coverage};
+    const size_t size[6] = {P * spp * sizeof(bih_hit), P * 4, P * 4, P * 8, P * 12, P * 4};
+    size_t off[6], total = 0;
+    for (int k = 0; k < 6; ++k) {
+        off[k] = total;
+        if (host[k]) total += (size[k] + 15) & ~(size_t)15;
+    }
+    if (tr->gb_stage_cap < total) {
+        // (its only users are calls of this function, which wait for their work)
+        if (tr->gb_stage) (void)hipFree(tr->gb_stage);
+        tr->gb_stage = nullptr;
+        tr->gb_stage_cap = 0;
+        const hipError_t e = tree_malloc(tr, &tr->gb_stage, total);
+        if (e != hipSuccess) return map_hip((int)e);
+        tr->gb_stage_cap = total;
+    }
+    auto dev_plane = [&](int k) -> void * { return host[k] ? tr->gb_stage + off[k] : nullptr; };
+    bih_gbuffer d;
+    d.hits = static_cast<bih_hit *>(dev_plane(0));
+    d.depth = static_cast<float *>(dev_plane(1));
+    d.prim = static_cast<uint32_t *>(dev_plane(2));
+    d.bary = static_cast<float *>(dev_plane(3));
+    d.normal = static_cast<float *>(dev_plane(4));
+    d.coverage = static_cast<uint32_t *>(dev_plane(5));
+    rc = gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, d, nullptr);
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 6 && rc == BIH_OK; ++k)
+        if (host[k]) {
+            e = hipMemcpyAsync(host[k], tr->gb_stage + off[k], size[k], hipMemcpyDeviceToHost, tr->stream);
+            if (e != hipSuccess) rc = map_hip((int)e);
+        }
     e = hipStreamSynchronize(tr->stream);
     return rc ? rc : map_hip((int)e);
 }

@@ -1,0 +1,471 @@
+// bih_gbuffer.hip -- G-buffer render (bih_render_gbuffer_device / bih_render_gbuffer,
+// include/bih.h): the closest hit of every primary sample of a frame and the
+// per-pixel planes resolved from them, in one pass on gfx950.
+//
+// Semantics: bih_trace's CLOSEST query (section
+// 4.5.1, the oracle's traverse_closest) applied to the rays bih_render casts:
+// sample (x, y, s) of frame f draws r0, r1 from the pixel's XORWOW state
+// (cudaRender's draws 2s, 2s+1 of the frame), u = (x + r0) / w, v = (y + r1) / h,
+// d = ((lower_left + u*horizontal) + v*vertical) - origin (camera_dir), o =
+// origin, t_lo = 0.  Every f32 expression is the oracle's, in its order
+// (-ffp-contract=off).
+//
+// One wave handles one tile of 64 samples, taken from a global cursor by
+// persistent one-wave blocks.  For a power-of-two spp the tile is TileShape's
+// TW x TH pixels x spp, lane = pixel_in_tile * spp + s: the layout of the
+// frustum bins' per-tile hit mask, whose zero bits are samples proven to miss
+// (they get the miss record without a walk).  Any other spp <= 64 packs
+// floor(64 / spp) consecutive local pixels into a wave.  The ray is made in
+// registers (no ray is written to or read from memory; the origin is
+// wave-uniform), walked with traverse_closest's step (restated here;
+// bih_trace.hip's tray_step shows the decision order), and the pixel planes
+// come from an in-wave min-reduction of (t bits, s) over the pixel's spp
+// adjacent lanes: t > 0, so the f32 bits order as integers.
+#include <hip/hip_runtime.h>
+#include <float.h>
+
+#include "bih_device.h"
+#include "bih_internal.h"
+
+namespace bih {
+namespace {
+
+using dev::kDetEps;
+
+constexpr uint32_t kGT = 64;             // threads per block: one wave
+constexpr uint32_t kNoHit = 0xFFFFFFFFu;
+// stack slots per lane in LDS: 6 KB per wave, so that the VGPRs (24 waves per
+// CU), not LDS, bound the occupancy (10 slots: 25.2 against 24.6 ms)
+constexpr int kGLds = 8;
+
+struct GArgs {
+    float cam[12];              // origin, lower_left, horizontal, vertical
+    uint32_t w, h, spp;
+    uint32_t row0, nrows, band_h, band_step;
+    uint32_t d_base;            // XORWOW Weyl counter at the start of the frame
+    uint32_t tiles_x, ntiles;   // POW2: TW x TH pixel tiles; else waves of ppw pixels
+    uint32_t log2spp;           // POW2 only
+    uint32_t ppw;               // pixels per wave (not POW2): 64 / spp
+    const TreeHeader *hdr;
+    const uint4 *nodes;
+    const float *tris;          // sorted {v0, e1, e2}
+    const uint32_t *dup;
+    const uint32_t *tri_idx;    // sorted position -> file order
+    const uint32_t *rng_in;     // 5 planes of nrows*w: XORWOW v at the start of the frame
+    const unsigned long long *hit_mask;   // per tile (POW2), or null: every sample is walked
+    uint4 *hits;                // bih_hit[P*spp] or null
+    float *depth;               // each plane may be null
+    uint32_t *prim;
+    float *bary;
+    float *normal;
+    uint32_t *coverage;
+    uint32_t *cursor;           // tiles taken so far (zero at launch)
+    uint32_t *spill;
+};
+
+__device__ __forceinline__ float pick3(uint32_t ax, float a, float b, float c) {
+    return ax == 0 ? a : (ax == 1 ? b : c);
+}
+
+struct GScene {
+    const uint4 *nodes;
+    const float *tris;
+    const uint32_t *dup;
+    float slo[3], shi[3];
+    float o[3];                 // the camera origin: every ray's (wave-uniform)
+    uint32_t U, N;
+};
+
+// One sample's walk state.  nd: the record of node cur, requested by the
+// previous step (one memory round trip per step).
+struct GRay {
+    float d[3], ix, iy, iz, tMin, tMax, bt;
+    uint32_t sg, cur, sp, bi;
+    uint4 nd;
+};
+
+// RayTriangleIntersection (CUDAKernels.cu:17-50) on a {v0, e1, e2} record for
+// a ray from the camera origin: true when the ray passes the determinant and
+// barycentric tests; t, u, v as the reference computes them.
+__device__ __forceinline__ bool mt_tuv(const float *__restrict__ tp, const GScene &s, const GRay &r, float &t,
+                                       float &u, float &v) {
+    const float v0x = tp[0], v0y = tp[1], v0z = tp[2];
+    const float e1x = tp[3], e1y = tp[4], e1z = tp[5];
+    const float e2x = tp[6], e2y = tp[7], e2z = tp[8];
+    const float dx = r.d[0], dy = r.d[1], dz = r.d[2];
+    const float px = dy * e2z - e2y * dz;                  // pvec = cross(D, e2)
+    const float py = dz * e2x - e2z * dx;
+    const float pz = dx * e2y - e2x * dy;
+    const float det = (e1x * px + e1y * py) + e1z * pz;
+    if (det <= kDetEps) return false;                      // det < 0.000001 (double); NaN passes
+    const float inv = 1.0f / det;
+    const float sx = s.o[0] - v0x, sy = s.o[1] - v0y, sz = s.o[2] - v0z;
+    u = ((sx * px + sy * py) + sz * pz) * inv;
+    if (u < 0.0f || u > 1.0f) return false;
+    const float qx = sy * e1z - e1y * sz;                  // qvec = cross(tvec, e1)
+    const float qy = sz * e1x - e1z * sx;
+    const float qz = sx * e1y - e1x * sy;
+    v = ((dx * qx + dy * qy) + dz * qz) * inv;
+    if (v < 0.0f || u + v > 1.0f) return false;
+    t = ((e2x * qx + e2y * qy) + e2z * qz) * inv;
+    return true;
+}
+
+// Leaf triangles [b, e): the (t, i) rule with 0 < t < FLT_MAX.
+__device__ __forceinline__ void gleaf(const GScene &s, GRay &r, uint32_t b, uint32_t e) {
+    for (uint32_t i = b; i < e; ++i) {
+        float t, u, v;
+        if (mt_tuv(s.tris + 9ull * i, s, r, t, u, v) && t > 0.0f && t < FLT_MAX &&
+            (t < r.bt || (t == r.bt && i < r.bi))) {
+            r.bt = t;
+            r.bi = i;
+        }
+    }
+}
+
+// Per-lane stack: slots [0, LDS) in LDS at [slot * kGT] from this lane's base,
+// deeper slots in this thread's memory area (slot-major, grid-interleaved; the
+// layout of bih_trace.hip's TStack, whose spill area this kernel borrows).
+template <int LDS>
+struct GStack {
+    uint32_t *sn;
+    float *smin, *smax;
+    uint32_t *spill;           // + gtid; slot k >= LDS at ((k - LDS) * 3) * gthreads
+    uint64_t gthreads;
+    __device__ __forceinline__ void push(uint32_t sp, uint32_t n, float lo, float hi) const {
+        if (sp < (uint32_t)LDS) {
+            sn[sp * kGT] = n; smin[sp * kGT] = lo; smax[sp * kGT] = hi;
+        } else {
+            uint32_t *q = spill + (uint64_t)(sp - LDS) * 3 * gthreads;
+            q[0] = n; q[gthreads] = __float_as_uint(lo); q[2 * gthreads] = __float_as_uint(hi);
+        }
+    }
+    __device__ __forceinline__ void pop(uint32_t sp, uint32_t &n, float &lo, float &hi) const {
+        if (sp < (uint32_t)LDS) {
+            n = sn[sp * kGT]; lo = smin[sp * kGT]; hi = smax[sp * kGT];
+        } else {
+            const uint32_t *q = spill + (uint64_t)(sp - LDS) * 3 * gthreads;
+            n = q[0]; lo = __uint_as_float(q[gthreads]); hi = __uint_as_float(q[2 * gthreads]);
+        }
+    }
+};
+
+// The walk's prologue (traverse_closest up to its loop, t_lo = 0); true when
+// the ray has nodes to walk, false when its result is final (it misses the
+// scene box, or the tree has no internal node: U <= 1 is one leaf of all N
+// triangles).
+__device__ __forceinline__ bool gray_start(const GScene &s, GRay &r) {
+    r.bt = FLT_MAX;
+    r.bi = kNoHit;
+    r.cur = 0;
+    r.sp = 0;
+    r.ix = 1.0f / r.d[0];
+    r.iy = 1.0f / r.d[1];
+    r.iz = 1.0f / r.d[2];
+    r.sg = (r.ix < 0.0f ? 1u : 0u) | (r.iy < 0.0f ? 2u : 0u) | (r.iz < 0.0f ? 4u : 0u);
+    // scene-AABB slab test, CUDAKernels.cu:237-262 (tMin may be negative)
+    float tMin = (((r.sg & 1) ? s.shi[0] : s.slo[0]) - s.o[0]) * r.ix;
+    float tMax = (((r.sg & 1) ? s.slo[0] : s.shi[0]) - s.o[0]) * r.ix;
+    const float tymin = (((r.sg & 2) ? s.shi[1] : s.slo[1]) - s.o[1]) * r.iy;
+    const float tymax = (((r.sg & 2) ? s.slo[1] : s.shi[1]) - s.o[1]) * r.iy;
+    if ((tMin > tymax) || (tymin > tMax)) return false;
+    if (tymin > tMin) tMin = tymin;
+    if (tymax < tMax) tMax = tymax;
+    const float tzmin = (((r.sg & 4) ? s.shi[2] : s.slo[2]) - s.o[2]) * r.iz;
+    const float tzmax = (((r.sg & 4) ? s.slo[2] : s.shi[2]) - s.o[2]) * r.iz;
+    if ((tMin > tzmax) || (tzmin > tMax)) return false;
+    if (tzmin > tMin) tMin = tzmin;
+    if (tzmax < tMax) tMax = tzmax;
+    if (s.U < 2) {   // single leaf (reference: UB; defined as the oracle's)
+        gleaf(s, r, 0, s.U ? s.N : 0u);
+        return false;
+    }
+    r.tMin = tMin;
+    r.tMax = tMax;
+    r.nd = s.nodes[0];
+    return true;
+}
+
+// One iteration of traverse_closest's loop; true when the walk has ended.
+// The next node's record is requested before the leaves this step visits are
+// tested (they are still tested before the next node's decisions read the
+// best hit: the same decisions, the same hit).
+template <class Stack>
+__device__ __forceinline__ bool gray_step(const GScene &s, GRay &r, const Stack &stk) {
+    const float best = r.bi != kNoHit ? r.bt : __builtin_inff();
+    if (r.tMin > best) {                          // entered beyond the best hit: skip
+        if (r.sp == 0) return true;
+        --r.sp;
+        stk.pop(r.sp, r.cur, r.tMin, r.tMax);
+        r.nd = s.nodes[r.cur];
+        return false;
+    }
+    if (best < r.tMax) r.tMax = best;
+    const uint4 nd = r.nd;
+    const uint32_t ax = (nd.z >> 27) & 3u;
+    const float org = pick3(ax, s.o[0], s.o[1], s.o[2]), inv = pick3(ax, r.ix, r.iy, r.iz);
+    const uint32_t nr = (r.sg >> ax) & 1u;
+    const float t0 = (__uint_as_float(nd.x) - org) * inv;
+    const float t1 = (__uint_as_float(nd.y) - org) * inv;
+    const float tn = nr ? t1 : t0, tf = nr ? t0 : t1;
+    const bool A = r.tMin < tn, B = r.tMax < tf;
+    const uint32_t split = nd.z & kIdxMask, mid = nd.w & kIdxMask;
+    const bool leafL = (nd.z >> 29) & 1u, leafR = (nd.z >> 30) & 1u;
+    const bool leafN = nr ? leafR : leafL, leafF = nr ? leafL : leafR;
+    uint32_t cL = (nd.w >> 27) & 3u, cR = (nd.w >> 29) & 3u;
+    if (leafL && cL == 0) cL = s.dup[split];
+    if (leafR && cR == 0) cR = s.dup[split + 1];
+    const uint32_t nb = nr ? mid : mid - cL, ne = nr ? mid + cR : mid;
+    const uint32_t fb = nr ? mid - cL : mid, fe = nr ? mid : mid + cR;
+    const uint32_t nearc = split + nr, farc = split + 1u - nr;
+    // the leaves this step visits, in the walk's order: [l0b, l0e) then [l1b, l1e)
+    uint32_t l0b = 0, l0e = 0, l1b = 0, l1e = 0;
+    bool pop = false;
+    if (!A && B) {
+        pop = true;
+    } else if (A && B) {
+        if (leafN) { l0b = nb; l0e = ne; pop = true; }
+        else { r.cur = nearc; r.tMax = tn; }
+    } else if (!A && !B) {
+        if (leafF) { l0b = fb; l0e = fe; pop = true; }
+        else { r.cur = farc; r.tMin = tf; }
+    } else {
+        if (leafN && leafF) {
+            l0b = nb; l0e = ne;
+            l1b = fb; l1e = fe;
+            pop = true;
+        } else if (!leafN && leafF) {
+            l0b = fb; l0e = fe;
+            r.cur = nearc; r.tMax = tn;
+        } else if (leafN && !leafF) {
+            l0b = nb; l0e = ne;
+            r.cur = farc; r.tMin = tf;
+        } else {
+            stk.push(r.sp, farc, tf, r.tMax);
+            ++r.sp;
+            r.cur = nearc; r.tMax = tn;
+        }
+    }
+    bool fin = false;
+    if (pop) {
+        if (r.sp == 0) {
+            fin = true;
+        } else {
+            --r.sp;
+            stk.pop(r.sp, r.cur, r.tMin, r.tMax);
+        }
+    }
+    if (!fin) r.nd = s.nodes[r.cur];
+    gleaf(s, r, l0b, l0e);
+    gleaf(s, r, l1b, l1e);
+    return fin;
+}
+
+// LDS: stack slots per lane kept in LDS.  POW2: spp is a power of two (tiles
+// of TW x TH pixels, the hit mask's layout).
+template <int LDS, bool POW2>
+__global__ void __launch_bounds__(kGT) k_gbuffer(const GArgs a) {
+    __shared__ uint32_t s_node[LDS * kGT];
+    __shared__ float s_min[LDS * kGT];
+    __shared__ float s_max[LDS * kGT];
+    const uint32_t lane = threadIdx.x;
+    GStack<LDS> stk;
+    stk.sn = s_node + lane;
+    stk.smin = s_min + lane;
+    stk.smax = s_max + lane;
+    stk.gthreads = (uint64_t)gridDim.x * kGT;
+    stk.spill = a.spill + (uint64_t)blockIdx.x * kGT + lane;
+    GScene sc;
+    sc.nodes = a.nodes;
+    sc.tris = a.tris;
+    sc.dup = a.dup;
+    for (int k = 0; k < 3; ++k) {
+        sc.slo[k] = a.hdr->scene_lo[k];
+        sc.shi[k] = a.hdr->scene_hi[k];
+        sc.o[k] = a.cam[k];
+    }
+    sc.U = a.hdr->n_unique;
+    sc.N = a.hdr->n_tris;
+    const uint64_t P = (uint64_t)a.nrows * a.w;
+    const uint32_t spp = a.spp;
+    const bool planes = a.depth || a.prim || a.bary || a.normal || a.coverage;
+    // this lane's place in every tile
+    uint32_t pix, s;
+    if (POW2) {
+        pix = lane >> a.log2spp;
+        s = lane & (spp - 1u);
+    } else {
+        pix = lane / spp;
+        s = lane - pix * spp;
+    }
+    const uint32_t base = lane - s;                    // the pixel's first lane
+    const unsigned long long gmask = spp >= 64u ? ~0ull : (1ull << spp) - 1ull;
+    for (;;) {
+        uint32_t tile = 0;
+        if (lane == 0) tile = atomicAdd(a.cursor, 1u);
+        tile = __builtin_amdgcn_readfirstlane(tile);
+        // (ntiles <= 2^32 - 2^20 and each wave overshoots it once: no wrap)
+        if (tile >= a.ntiles) break;
+        uint32_t x, lr;
+        bool valid;
+        if (POW2) {
+            // TileShape: TW x TH pixels, TW * TH = 64 >> log2(spp)
+            const uint32_t lpx = 6u - a.log2spp, ltw = (lpx + 1u) / 2u;
+            const uint32_t ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+            x = (tx << ltw) + (pix & ((1u << ltw) - 1u));
+            lr = (ty << (lpx / 2u)) + (pix >> ltw);
+            valid = x < a.w && lr < a.nrows;
+        } else {
+            const uint64_t lp0 = (uint64_t)tile * a.ppw + pix;
+            valid = pix < a.ppw && lp0 < P;
+            lr = (uint32_t)(lp0 / a.w);
+            x = (uint32_t)(lp0 - (uint64_t)lr * a.w);
+        }
+        const uint64_t lp = (uint64_t)lr * a.w + x;
+        bool walk = valid;
+        if (POW2 && a.hit_mask) walk = valid && ((a.hit_mask[tile] >> lane) & 1ull);
+        GRay r;
+        r.bt = FLT_MAX;
+        r.bi = kNoHit;
+        if (walk) {
+            // draws 2s, 2s+1 of this pixel's frame (cudaRender :413-415)
+            uint32_t v[5];
+            for (int i = 0; i < 5; ++i) v[i] = a.rng_in[(uint64_t)i * P + lp];
+            uint32_t d = a.d_base;
+            float ru = 0.f, rv = 0.f;
+            for (uint32_t k = 0; k <= s; ++k) {
+                ru = dev::xorwow_uniform(v, d);
+                rv = dev::xorwow_uniform(v, d);
+            }
+            const uint32_t y = dev::global_row(lr, a.row0, a.band_h, a.band_step);
+            const float fu = ((float)x + ru) / (float)a.w, fv = ((float)y + rv) / (float)a.h;
+            // Camera::GetRay direction, Camera.cu:18-20
+            for (int k = 0; k < 3; ++k) r.d[k] = ((a.cam[3 + k] + fu * a.cam[6 + k]) + fv * a.cam[9 + k]) - a.cam[k];
+            if (gray_start(sc, r)) {
+                while (!gray_step(sc, r, stk)) {}
+            }
+        }
+        // the sample's record: the accepted triangle's test once more (the
+        // same inputs and expressions, the same bits), then tri_idx
+        const bool hit = walk && r.bi != kNoHit;
+        float t = FLT_MAX, u = 0.0f, vv = 0.0f;
+        uint32_t prim = kNoHit;
+        if (hit) {
+            (void)mt_tuv(sc.tris + 9ull * r.bi, sc, r, t, u, vv);
+            prim = a.tri_idx[r.bi];
+        }
+        if (a.hits && valid)
+            a.hits[lp * spp + s] = make_uint4(__float_as_uint(t), __float_as_uint(u), __float_as_uint(vv), prim);
+        if (!planes) continue;
+        // the pixel's representative sample: min (t bits, s) over its hit samples
+        unsigned long long key = hit ? ((unsigned long long)__float_as_uint(t) << 32) | s : ~0ull;
+        if (POW2) {
+            for (uint32_t off = 1; off < spp; off <<= 1) {
+                const unsigned long long o = __shfl_xor(key, (int)off, 64);
+                key = o < key ? o : key;
+            }
+        } else {
+            // the pixel's first lane gathers its samples' keys, then hands the minimum back
+            unsigned long long m = key;
+            for (uint32_t k = 1; k < spp; ++k) {
+                const unsigned long long o = __shfl(key, (int)((lane + k) & 63u), 64);
+                if (s == 0 && o < m) m = o;
+            }
+            key = __shfl(m, (int)base, 64);
+        }
+        const unsigned long long hb = __ballot(hit);
+        const uint32_t cov = (uint32_t)__popcll((hb >> base) & gmask);
+        if (!valid) continue;
+        if (key == ~0ull) {
+            if (s != 0) continue;
+            if (a.depth) a.depth[lp] = FLT_MAX;
+            if (a.prim) a.prim[lp] = kNoHit;
+            if (a.bary) { a.bary[2 * lp] = 0.0f; a.bary[2 * lp + 1] = 0.0f; }
+            if (a.normal) { a.normal[3 * lp] = 0.0f; a.normal[3 * lp + 1] = 0.0f; a.normal[3 * lp + 2] = 0.0f; }
+            if (a.coverage) a.coverage[lp] = 0u;
+        } else if (hit && s == (uint32_t)key) {
+            if (a.depth) a.depth[lp] = t;
+            if (a.prim) a.prim[lp] = prim;
+            if (a.bary) { a.bary[2 * lp] = u; a.bary[2 * lp + 1] = vv; }
+            if (a.normal) {
+                // n = cross(e1, e2) (glm order), normalised: each op one rounded f32 op
+                const float *tp = sc.tris + 9ull * r.bi;
+                const float e1x = tp[3], e1y = tp[4], e1z = tp[5];
+                const float e2x = tp[6], e2y = tp[7], e2z = tp[8];
+                const float nx = e1y * e2z - e2y * e1z;
+                const float ny = e1z * e2x - e2z * e1x;
+                const float nz = e1x * e2y - e2x * e1y;
+                const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
+                a.normal[3 * lp] = nx / len;
+                a.normal[3 * lp + 1] = ny / len;
+                a.normal[3 * lp + 2] = nz / len;
+            }
+            if (a.coverage) a.coverage[lp] = cov;
+        }
+    }
+}
+
+}  // namespace
+
+// Tiles of a launch: for a power-of-two spp TileShape's TW x TH pixel tiles
+// over the local rows (*tiles_x across), else waves of 64 / spp local pixels.
+uint64_t gbuffer_tiles(uint32_t w, uint32_t nrows, uint32_t spp, uint32_t *tiles_x) {
+    if ((spp & (spp - 1)) == 0) {
+        const uint32_t lpx = 6u - (uint32_t)__builtin_ctz(spp);
+        const uint32_t tw = 1u << ((lpx + 1) / 2), th = 1u << (lpx / 2);
+        *tiles_x = (w + tw - 1) / tw;
+        return (uint64_t)*tiles_x * ((nrows + th - 1) / th);
+    }
+    const uint64_t ppw = 64 / spp;
+    *tiles_x = 0;
+    return ((uint64_t)nrows * w + ppw - 1) / ppw;
+}
+
+int launch_gbuffer(const DeviceTree &t, const RenderArgs &ra, const GBufferPlanes &p,
+                   const unsigned long long *hit_mask, uint32_t lds_slots, uint32_t *cursor, uint32_t *spill,
+                   uint32_t max_blocks, void *stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0 || ra.spp > 64) return 0;
+    const bool pow2 = (ra.spp & (ra.spp - 1)) == 0;
+    GArgs a;
+    for (int k = 0; k < 12; ++k) a.cam[k] = ra.cam[k];
+    a.w = ra.w;
+    a.h = ra.h;
+    a.spp = ra.spp;
+    a.row0 = ra.row0;
+    a.nrows = ra.nrows;
+    a.band_h = ra.band_h;
+    a.band_step = ra.band_step;
+    a.d_base = ra.d_base;
+    const uint64_t ntiles = gbuffer_tiles(ra.w, ra.nrows, ra.spp, &a.tiles_x);
+    if (ntiles > 0xFFFFFFFFull - (1ull << 20)) return (int)hipErrorInvalidValue;
+    a.ntiles = (uint32_t)ntiles;
+    a.log2spp = pow2 ? (uint32_t)__builtin_ctz(ra.spp) : 0u;
+    a.ppw = 64u / ra.spp;
+    a.hdr = t.hdr;
+    a.nodes = t.nodes;
+    a.tris = t.tris_s;
+    a.dup = t.dup_cnt;
+    a.tri_idx = t.vals;
+    a.rng_in = ra.rng_in;
+    a.hit_mask = pow2 ? hit_mask : nullptr;
+    a.hits = reinterpret_cast<uint4 *>(p.hits);
+    a.depth = p.depth;
+    a.prim = p.prim;
+    a.bary = p.bary;
+    a.normal = p.normal;
+    a.coverage = p.coverage;
+    a.cursor = cursor;
+    a.spill = spill;
+    hipError_t e = hipMemsetAsync(cursor, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return (int)e;
+    const dim3 grid(a.ntiles < max_blocks ? a.ntiles : max_blocks), block(kGT);
+    const bool small = lds_slots == (uint32_t)kTraceLdsTest;
+    if (small && pow2) hipLaunchKernelGGL((k_gbuffer<kTraceLdsTest, true>), grid, block, 0, st, a);
+    else if (small) hipLaunchKernelGGL((k_gbuffer<kTraceLdsTest, false>), grid, block, 0, st, a);
+    else if (pow2) hipLaunchKernelGGL((k_gbuffer<kGLds, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_gbuffer<kGLds, false>), grid, block, 0, st, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace bih

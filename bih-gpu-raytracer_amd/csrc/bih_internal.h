@@ -330,6 +330,25 @@ uint32_t trace_grid_blocks(int device);
 size_t trace_spill_words(uint32_t blocks);
 int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, bool occluded, void *d_out,
                  uint32_t lds_slots, uint32_t *cursor, uint32_t *spill, uint32_t max_blocks, void *stream);
+// G-buffer render (bih_gbuffer.hip): the closest hit of every primary sample
+// of the frame `a` describes (cam, w, h, spp, rows, d_base, rng_in), to
+// p.hits (bih_hit[P*spp], sample = local pixel * spp + s) and the pixel planes
+// resolved from them; a null plane is not written.  hit_mask (optional, spp a
+// power of two): per tile the samples that can hit (RenderArgs::hit_mask); the
+// others get the miss record unwalked.  cursor, spill, max_blocks, lds_slots:
+// as launch_trace (the kernel borrows the trace's cursor and spill area).
+struct GBufferPlanes {
+    void *hits = nullptr;
+    float *depth = nullptr;
+    uint32_t *prim = nullptr;
+    float *bary = nullptr;
+    float *normal = nullptr;
+    uint32_t *coverage = nullptr;
+};
+uint64_t gbuffer_tiles(uint32_t w, uint32_t nrows, uint32_t spp, uint32_t *tiles_x);
+int launch_gbuffer(const DeviceTree &t, const RenderArgs &a, const GBufferPlanes &p,
+                   const unsigned long long *hit_mask, uint32_t lds_slots, uint32_t *cursor, uint32_t *spill,
+                   uint32_t max_blocks, void *stream);
 int launch_rng_init(uint32_t *rng, uint32_t w, uint32_t row0, uint32_t nrows, uint32_t band_h,
                     uint32_t band_step, uint64_t seed, uint64_t skip, int device, void *stream);
 // dst = src's per-pixel state advanced by `steps` draws (planes of `pixels`; dst may be src)

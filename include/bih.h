@@ -36,7 +36,8 @@ extern "C" {
 
 #define BIH_ABI_VERSION 4   /* 2: bih_tree_info.device_allocs, bih_reserve, bih_tree_set_param;
                                3: bih_whitted_work, BIH_PARAM_WHITTED_COUNTERS;
-                               4: bih_host_register / bih_host_unregister, bih_render_history */
+                               4: bih_host_register / bih_host_unregister, bih_render_history;
+                               (4, added since: bih_trace*, bih_render_gbuffer*, BIH_PARAM_GBUFFER_MASK) */
 
 /* error codes */
 #define BIH_OK               0
@@ -239,6 +240,9 @@ int bih_reserve(bih_tree *tree, uint32_t w, uint32_t h, uint32_t spp, const bih_
                                         2 stack slots per lane on chip, so that
                                         the memory part of the stack is used;
                                         0 = the default; no result changes     */
+#define BIH_PARAM_GBUFFER_MASK     9  /* tests / A-B: 0 = bih_render_gbuffer*
+                                        walks every sample (no frustum-bin hit
+                                        mask); default 1; no result changes    */
 int bih_tree_set_param(bih_tree *tree, int param, uint64_t value);
 
 /* Ray queries: closest hit and occlusion for the caller's own rays (what
@@ -332,6 +336,65 @@ int bih_render_whitted(const bih_scene *scene, const bih_tree *tree, const bih_c
  * tree, whose walks have no nodes).  Waits for that render. */
 int bih_whitted_work(const bih_tree *tree, uint32_t rays[BIH_WHITTED_BOUNCES + 1],
                      uint64_t nodes[BIH_WHITTED_BOUNCES + 1], uint64_t tris[BIH_WHITTED_BOUNCES + 1]);
+
+/* G-buffer render: depth, primitive id, barycentrics, normal and coverage of
+ * the frame bih_render renders, plus (optionally) every primary sample's hit
+ * record -- one fused pass.
+ *
+ * Any plane may be NULL (not written); all NULL -> BIH_ERR_INVALID.
+ * P = rows->nrows * w local pixels, local pixel p = local_row * w + x. */
+typedef struct bih_gbuffer {
+    bih_hit  *hits;      /* bih_hit[P*spp], sample p*spp + s; 16-byte aligned */
+    float    *depth;     /* f32[P]    */
+    uint32_t *prim;      /* u32[P]    */
+    float    *bary;      /* f32[2*P]  u, v   */
+    float    *normal;    /* f32[3*P]  x, y, z */
+    uint32_t *coverage;  /* u32[P]    samples of the pixel that hit, 0..spp */
+} bih_gbuffer;
+
+/* Semantics: bih_trace's BIH_QUERY_CLOSEST applied to the rays bih_render
+ * casts, no new rule.
+ *  - Ray of sample (x, y, s) of frame f: r0, r1 = draws 2*spp*f + 2s and
+ *    2*spp*f + 2s + 1 of XORWOW subsequence y*w + x seeded with `seed`;
+ *    u = ((float)x + r0) / (float)w, v = ((float)y + r1) / (float)h;
+ *    d[a] = ((lower_left[a] + u*horizontal[a]) + v*vertical[a]) - origin[a];
+ *    o = origin, t_lo = 0: bit for bit the ray bih_render traces for that
+ *    sample.  y is the global row under bih_rows.
+ *  - hits[p*spp + s] is exactly the bih_hit bih_trace(.., BIH_QUERY_CLOSEST)
+ *    returns for that ray (the order of d_ray_stats; the same miss record).
+ *  - The pixel planes come from the pixel's representative sample, the hit
+ *    sample with the smallest (t, s): depth = its t, prim, bary = (u, v);
+ *    coverage = the number of hit samples; normal = cross(e1, e2) / |..| of
+ *    the hit triangle (e1 = v1-v0, e2 = v2-v0; n = (e1y*e2z - e2y*e1z,
+ *    e1z*e2x - e2z*e1x, e1x*e2y - e2x*e1y), len = sqrtf((nx*nx + ny*ny) +
+ *    nz*nz), normal = n / len, each operation one correctly rounded f32 op).
+ *    Triangles are one-sided, so an accepted triangle's normal faces the ray.
+ *    A pixel with no hit gets FLT_MAX, BIH_NO_HIT, (0,0), (0,0,0) and 0.
+ *  - depth is in units of |d| (P = o + t*d, d not normalised): for a camera
+ *    whose image plane is perpendicular to the view axis at distance L from
+ *    the origin it is the planar z-depth divided by L.
+ * Limits and errors, checked in this order before a device is touched: NULL
+ * tree, camera or planes -> BIH_ERR_INVALID; w, h or spp == 0 ->
+ * BIH_ERR_INVALID; spp > 64 -> BIH_ERR_INVALID (a limit of this call); all
+ * planes NULL -> BIH_ERR_INVALID; rows as bih_render_whitted_device
+ * (band_h or band_step == 0, or a row outside the frame -> BIH_ERR_INVALID);
+ * h*w*spp above 2^32 - 2^20 - 1 -> BIH_ERR_TOO_LARGE; hits not 16-byte aligned
+ * -> BIH_ERR_INVALID; nrows == 0 -> BIH_OK, nothing launched.
+ * RNG: the call counts as the render of frame f for the tree's persistent
+ * XORWOW state, as bih_render_whitted_device does; a bih_render of any frame
+ * before or after it is unchanged.
+ * Ordering: runs after the last bih_build / bih_rebuild, and a rebuild waits
+ * for it.  It borrows the ray queries' cursor and stack spill area (counted in
+ * bih_tree_info, allocated once), so G-buffer calls and traces of one tree
+ * order after each other; the hit mask and its scratch image are the tree's
+ * own, sized by the call's shape: after the first call of a shape further
+ * calls allocate nothing. */
+int bih_render_gbuffer_device(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                              uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                              const bih_gbuffer *d_planes, void *stream);   /* async; bih_sync waits */
+int bih_render_gbuffer(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                       uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                       const bih_gbuffer *host_planes);                     /* synchronous, host memory */
 
 /* The drop-in host loop (bih_render into a caller's framebuffer) ends in a
  * device-to-host copy of w*h*4 bytes.  Into pageable memory the runtime
