@@ -16,9 +16,11 @@
 //     plane (depth C_j . n > 0, n the camera's forward normal), that point has
 //     t > 0 and its projection (u*, v*) lies in the projection of the inflated
 //     triangle, the triangle of the projected corners.  The sample's own
-//     (u, v) -- the kernel's f32 (x + r) / W -- and the f32 D differ from
-//     (u*, v*) by ~1e-6 of the image: the footprint's pixel range is padded
-//     by half a pixel on each side;
+//     (u, v) -- the kernel's f32 (x + r) / W -- differs from (u*, v*) by the
+//     rounding of the f32 D (BinCamera::pad_e, pad_u, pad_v: ~1e-6 of the
+//     image near the scene, many pixels for a narrow view from far away):
+//     the footprint's range is padded by that bound and its pixel range by
+//     half a pixel on each side;
 //   behind the camera: all corners at negative depth and tnum_c larger than
 //     its rounding bound (exact t* has the sign of tnum* and det* > 0) --
 //     no primary ray can hit the triangle: no footprint;
@@ -502,11 +504,15 @@ __global__ void __launch_bounds__(kThreads) k_bin_fp(const float *__restrict__ p
         if (side == 1) {
             // pixel x holds the samples u in (x / W, (x + 1) / W]: pixels
             // [floor(W umin - 1/2) - 1, floor(W umax + 1/2)], clipped to the image
+            // (u, v) of a sample whose f32 ray meets the inflated triangle lie
+            // within (pu, pv) of the projected corners' range (BinCamera::pad_e)
             const double W = (double)c.w, H = (double)c.h;
-            const double fx0 = floor(fmax(fmin(umin * W - 0.5, 1e9), -1e9)) - 1.0;
-            const double fx1 = floor(fmax(fmin(umax * W + 0.5, 1e9), -1e9));
-            const double fy0 = floor(fmax(fmin(vmin * H - 0.5, 1e9), -1e9)) - 1.0;
-            const double fy1 = floor(fmax(fmin(vmax * H + 0.5, 1e9), -1e9));
+            const double pu = fmax(fabs(umin + c.ahu), fabs(umax + c.ahu)) * c.pad_e + c.pad_u;
+            const double pv = fmax(fabs(vmin + c.avv), fabs(vmax + c.avv)) * c.pad_e + c.pad_v;
+            const double fx0 = floor(fmax(fmin((umin - pu) * W - 0.5, 1e9), -1e9)) - 1.0;
+            const double fx1 = floor(fmax(fmin((umax + pu) * W + 0.5, 1e9), -1e9));
+            const double fy0 = floor(fmax(fmin((vmin - pv) * H - 0.5, 1e9), -1e9)) - 1.0;
+            const double fy1 = floor(fmax(fmin((vmax + pv) * H + 0.5, 1e9), -1e9));
             if (!(fx1 >= 0.0 && fy1 >= 0.0 && fx0 <= W - 1.0 && fy0 <= H - 1.0)) {
                 brect[i] = none;       // off the image: never listed (no entry, no plan)
                 return;
@@ -539,51 +545,6 @@ __global__ void __launch_bounds__(kThreads) k_bin_fp(const float *__restrict__ p
     float4 *o = reinterpret_cast<float4 *>(binrec + 16ull * i);
     for (int k = 0; k < 4; ++k) o[k] = make_float4(rec[4 * k], rec[4 * k + 1], rec[4 * k + 2], rec[4 * k + 3]);
     if (side == 0) glist[atomicAdd(gcount, 1u)] = i;   // every packet tests it
-}
-
-// Not launched.  The verification plan of alive triangle i = live[j] as a
-// kernel of its own, for a k_bin_fp that leaves (a, b, cc, 1) in the record's
-// plan slots (rec[12..15]) instead of the plan: the inflated triangle's
-// corners again from the record and (a, b, cc) -- the same f64 expressions,
-// the same corners -- then triangle_plan, the entry's leaf word and plan, and
-// the root path of a full-check leaf.  The split was slower (DESIGN, "Retired
-// experiments"); the kernel stays until this file's device code next changes,
-// so that retiring the switch left the code object byte for byte the same.
-__global__ void __launch_bounds__(kThreads) k_bin_plan(const float *__restrict__ prim, BinCamera c,
-                                                       const TreeHeader *__restrict__ hdr,
-                                                       const uint4 *__restrict__ node_prim,
-                                                       const uint32_t *__restrict__ tri_leaf,
-                                                       const int32_t *__restrict__ leaf_parent,
-                                                       const int32_t *__restrict__ parent,
-                                                       uint2 *__restrict__ path, float *__restrict__ binrec,
-                                                       const uint32_t *__restrict__ live,
-                                                       const uint32_t *__restrict__ live_count) {
-    __shared__ double s_tab[12 * kThreads];
-    const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
-    if (j >= *live_count) return;
-    const uint32_t i = live[j];
-    float *rec = binrec + 16ull * i;
-    const float4 abc = *reinterpret_cast<const float4 *>(rec + 12);
-    const uint32_t leaf = tri_leaf[i];
-    uint32_t plan = 3u;
-    float vals[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (abc.w != 0.0f) {
-        const float *r = prim + 16ull * i;
-        float rr[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) rr[k] = r[k];
-        const double cu[3] = {-(double)abc.x, 1.0 + (double)abc.y + (double)abc.z, -(double)abc.x};
-        const double cv[3] = {-(double)abc.y, -(double)abc.y, 1.0 + (double)abc.x + (double)abc.z};
-        double cx[3][3];
-        for (int q = 0; q < 3; ++q)
-            for (int ax = 0; ax < 3; ++ax)
-                cx[q][ax] = (cu[q] * (double)rr[ax] + cv[q] * (double)rr[3 + ax]) - (double)rr[6 + ax];
-        plan = triangle_plan(cx, leaf, hdr, c.o, node_prim, leaf_parent, parent, vals, s_tab + threadIdx.x);
-    }
-    rec[10] = __uint_as_float(leaf | (plan == 0u ? 0x80000000u : 0u));
-    rec[11] = __uint_as_float(plan);
-    *reinterpret_cast<float4 *>(rec + 12) = make_float4(vals[0], vals[1], vals[2], vals[3]);
-    if (plan == 3u || BIH_FAST_COUNTERS) write_path(node_prim, leaf, path);
 }
 
 // Tile (bx, by) against a triangle's edge pre-test (k0..k8 = 3 x {K0', Ku,
@@ -1201,8 +1162,19 @@ bool bin_camera(const float cam[12], const float dmax[3], uint32_t w, uint32_t h
     for (int k = 0; k < 3; ++k) c.o[k] = cam[k];
     // D.n = A.n exactly for D(u, v); the f32 D errs by delta per component
     c.dn_lb = an - 2.0 * (c.delta[0] * fabs(n[0]) + c.delta[1] * fabs(n[1]) + c.delta[2] * fabs(n[2]));
+    // (an origin so far out that an f32 D may point backwards: no bins)
+    if (!(c.dn_lb > 0.0)) return false;
     c.ahu = dot(A, c.hu);
     c.avv = dot(A, c.vv);
+    // The f32 ray of sample (u, v) is D' = A + u h + v vert + d, |d_i| <= delta_i.
+    // It meets a triangle's plane at X = lambda D', whose projection is u* =
+    // (X.hu)(A.n) / (X.n) - A.hu: with h.hu = 1, vert.hu = 0 and h.n = vert.n = 0,
+    // u - u* = (u* + A.hu)(d.n) / (A.n) - d.hu.  For a camera near the scene that
+    // is ~1e-6 of the image; far from the origin of coordinates with a narrow
+    // field of view (|O| ulp against |h|) it is many pixels.
+    c.pad_e = (c.delta[0] * fabs(n[0]) + c.delta[1] * fabs(n[1]) + c.delta[2] * fabs(n[2])) / an;
+    c.pad_u = c.delta[0] * fabs(c.hu[0]) + c.delta[1] * fabs(c.hu[1]) + c.delta[2] * fabs(c.hu[2]);
+    c.pad_v = c.delta[0] * fabs(c.vv[0]) + c.delta[1] * fabs(c.vv[1]) + c.delta[2] * fabs(c.vv[2]);
     c.w = w;
     c.h = h;
     c.tw = tw;

@@ -1111,6 +1111,8 @@ static int build_bins(bih_tree *tr, CamSet &c, const bih_camera *cam, const floa
                       uint32_t h, uint32_t spp, bool need_prim, hipStream_t st) {
     c.bins_valid = true;
     c.bins_usable = false;
+    c.bin_gn = 0;        // (an earlier camera's counts are not this one's: a camera
+    c.bin_entries = 0;   // that builds no bins reports none)
     c.uses = 0;
     c.gen = ++tr->bins_gen;
     c.bins_key[0] = w;
@@ -1226,6 +1228,9 @@ static int build_bins(bih_tree *tr, CamSet &c, const bih_camera *cam, const floa
         if (e != hipSuccess) return map_hip((int)e);
         c.bins_regrow = false;
         const uint64_t total = (uint64_t)g[4] | ((uint64_t)g[5] << 32);
+        // (the counts a camera without bins reports too: bih_bins_get_stats)
+        c.bin_gn = g[0];
+        c.bin_entries = total;
         // every packet tests the whole global list: beyond a few thousand
         // triangles the shortcut passes are the better proof
         if (g[0] > bih::kBinGlobalMax) return BIH_OK;
@@ -1250,8 +1255,6 @@ static int build_bins(bih_tree *tr, CamSet &c, const bih_camera *cam, const floa
         }
         le = bih::launch_bin_status(b, c.bin_list_cap, st);
         if (le) return map_hip(le);
-        c.bin_gn = g[0];
-        c.bin_entries = total;
     }
     le = bih::launch_bin_fill(n, bc, b, c.bin_list, gent, st);
     if (le) return map_hip(le);

@@ -224,6 +224,10 @@ struct BinCamera {
     double A[3], hh[3], vert[3], delta[3];   // A = lower_left - O, h, vert, |f32 D - D| bound
     double nlen, an, ahu, avv;
     double dn_lb;                             // <= D.n of every f32 primary ray (det_lower_bound)
+    // footprint padding (k_bin_fp): a sample's (u, v) against the projection (u*, v*) of
+    // the point its f32 ray meets, |u - u*| <= |u* + ahu| pad_e + pad_u (v alike):
+    // pad_e = |delta|.|n| / an, pad_u = |delta|.|hu|, pad_v = |delta|.|vv|
+    double pad_e, pad_u, pad_v;
     float dmax[3];
     float o[3];                               // origin (f32, as the kernels hold it)
     uint32_t w, h, tw, th;

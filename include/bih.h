@@ -426,7 +426,11 @@ int bih_render_history(const bih_tree *tree, uint32_t n, double *t);
 
 /* The frustum bins of the tree's current camera and image (any-hit renders):
  * usable = 1 when renders walk them; list entries over all tiles, entries of
- * the global list, tiles (TW x TH pixels, one 64-ray packet each). */
+ * the global list (triangles across the eye plane, which every packet tests),
+ * tiles (TW x TH pixels, one 64-ray packet each).  The two counts are those of
+ * the latest bins build, also when it ended without usable bins (a global list
+ * past 4096 entries, lists too long); a camera no bins can be built for
+ * reports zeros. */
 typedef struct bih_bins_stats {
     uint32_t usable;
     uint32_t tiles_x, tiles_y;

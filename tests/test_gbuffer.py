@@ -31,6 +31,9 @@ PLANES = ("depth", "prim", "bary", "normal", "coverage")
 EDGE = ["one_tri", "two_tris", "dup_all", "clustered", "flat_z", "signed_zero", "cornell", "dodeca",
         "bih1_dodeca"]
 SPARSE = ("clustered", "flat_z", "signed_zero")   # hit share below 10 % under both cameras: bits only
+# Other test modules' scenes (name -> () -> soup) and cameras (name -> (w, h) ->
+# float32[12]) for scene(), camera() and expected(): tests/test_cameras.py
+EXTRA_SCENES, EXTRA_CAMERAS = {}, {}
 
 
 def framing(lo, hi, w, h, k, fill=0.75):
@@ -95,7 +98,9 @@ def scene(name):
     """(tris, OracleTree) of an edge scene, or of the soups the tests use."""
     import bihrt
     import oracle
-    if name == "soup20k":
+    if name in EXTRA_SCENES:
+        tris = EXTRA_SCENES[name]()
+    elif name == "soup20k":
         tris = bihrt.scenes.soup(20000, seed=2, half=0.05)
     elif name.startswith("soup3k"):
         tris = bihrt.scenes.soup(3000, seed=int(name[6:] or 1), half=0.08)
@@ -106,19 +111,29 @@ def scene(name):
 
 
 def camera(name, kname, w, h):
+    if kname in EXTRA_CAMERAS:
+        return np.ascontiguousarray(EXTRA_CAMERAS[kname](w, h), F32)
     ot = scene(name)[1]
     return framing(ot.scene_lo, ot.scene_hi, w, h, KS[kname])
+
+
+@functools.lru_cache(maxsize=None)
+def frame_uniforms(w, h, spp, frame, seed=SEED):
+    """(h, w, 2*spp) f32: draws 2*spp*frame .. of XORWOW subsequence y*w + x; read-only."""
+    import oracle
+    r = np.empty((h, w, 2 * spp), F32)
+    for y in range(h):
+        for x in range(w):
+            r[y, x] = oracle.rng_uniforms(seed, y * w + x, 2 * spp, skip=2 * spp * frame)
+    r.setflags(write=False)
+    return r
 
 
 def frame_rays(cam, w, h, spp, frame, seed=SEED):
     """Directions (h, w, spp, 3) f32 of the frame's samples: r0, r1 = draws
     2*spp*frame + 2s (+ 1) of XORWOW subsequence y*w + x; u = (x + r0) / w,
     v = (y + r1) / h; d = ((lower_left + u*horizontal) + v*vertical) - origin."""
-    import oracle
-    r = np.empty((h, w, 2 * spp), F32)
-    for y in range(h):
-        for x in range(w):
-            r[y, x] = oracle.rng_uniforms(seed, y * w + x, 2 * spp, skip=2 * spp * frame)
+    r = frame_uniforms(w, h, spp, frame, seed)
     cam = np.asarray(cam, F32)
     xs = np.arange(w, dtype=F32)[None, :, None]
     ys = np.arange(h, dtype=F32)[:, None, None]
