@@ -1937,7 +1937,7 @@ int bih_render_whitted_device(const bih_tree *ctr, const bih_camera *cam, uint32
     uint64_t ylast = rows.row0 + (lr / rows.band_h) * (uint64_t)rows.band_h * rows.band_step +
                      (lr % rows.band_h);
     if (ylast >= h) return BIH_ERR_INVALID;
-    // u32 ray ids, and k_wh_trace_dyn's u32 fetch counter overshoots the ray
+    // u32 ray ids, and k_wh_trace's u32 fetch counter overshoots the ray
     // count by at most one 64-ray fetch per wave of its grid (<= 2^20 lanes)
     if ((uint64_t)h * w * spp > 0xFFFFFFFFull - (1ull << 20)) return BIH_ERR_TOO_LARGE;
     DeviceGuard g(tr->t.device);

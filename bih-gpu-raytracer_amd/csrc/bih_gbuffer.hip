@@ -16,24 +16,23 @@
 // frustum bins' per-tile hit mask, whose zero bits are samples proven to miss
 // (they get the miss record without a walk).  Any other spp <= 64 packs
 // floor(64 / spp) consecutive local pixels into a wave.  The ray is made in
-// registers (no ray is written to or read from memory; the origin is
-// wave-uniform), walked with traverse_closest's step (restated here;
-// bih_trace.hip's tray_step shows the decision order), and the pixel planes
-// come from an in-wave min-reduction of (t bits, s) over the pixel's spp
-// adjacent lanes: t > 0, so the f32 bits order as integers.
+// registers (no ray is written to or read from memory), walked with
+// bih_closest.h's walk -- its origin the camera's, straight from the kernel
+// arguments (wave-uniform: SGPRs), its t_lo the literal 0 -- and the pixel
+// planes come from an in-wave min-reduction of (t bits, s) over the pixel's
+// spp adjacent lanes: t > 0, so the f32 bits order as integers.
 #include <hip/hip_runtime.h>
 #include <float.h>
 
-#include "bih_device.h"
+#include "bih_closest.h"
 #include "bih_internal.h"
 
 namespace bih {
 namespace {
 
-using dev::kDetEps;
+using dev::kNoHit;
 
-constexpr uint32_t kGT = 64;             // threads per block: one wave
-constexpr uint32_t kNoHit = 0xFFFFFFFFu;
+constexpr uint32_t kGT = dev::kLanes;    // threads per block: one wave
 // stack slots per lane in LDS: 6 KB per wave, so that the VGPRs (24 waves per
 // CU), not LDS, bound the occupancy (10 slots: 25.2 against 24.6 ms)
 constexpr int kGLds = 8;
@@ -63,204 +62,6 @@ struct GArgs {
     uint32_t *spill;
 };
 
-__device__ __forceinline__ float pick3(uint32_t ax, float a, float b, float c) {
-    return ax == 0 ? a : (ax == 1 ? b : c);
-}
-
-struct GScene {
-    const uint4 *nodes;
-    const float *tris;
-    const uint32_t *dup;
-    float slo[3], shi[3];
-    float o[3];                 // the camera origin: every ray's (wave-uniform)
-    uint32_t U, N;
-};
-
-// One sample's walk state.  nd: the record of node cur, requested by the
-// previous step (one memory round trip per step).
-struct GRay {
-    float d[3], ix, iy, iz, tMin, tMax, bt;
-    uint32_t sg, cur, sp, bi;
-    uint4 nd;
-};
-
-// RayTriangleIntersection (CUDAKernels.cu:17-50) on a {v0, e1, e2} record for
-// a ray from the camera origin: true when the ray passes the determinant and
-// barycentric tests; t, u, v as the reference computes them.
-__device__ __forceinline__ bool mt_tuv(const float *__restrict__ tp, const GScene &s, const GRay &r, float &t,
-                                       float &u, float &v) {
-    const float v0x = tp[0], v0y = tp[1], v0z = tp[2];
-    const float e1x = tp[3], e1y = tp[4], e1z = tp[5];
-    const float e2x = tp[6], e2y = tp[7], e2z = tp[8];
-    const float dx = r.d[0], dy = r.d[1], dz = r.d[2];
-    const float px = dy * e2z - e2y * dz;                  // pvec = cross(D, e2)
-    const float py = dz * e2x - e2z * dx;
-    const float pz = dx * e2y - e2x * dy;
-    const float det = (e1x * px + e1y * py) + e1z * pz;
-    if (det <= kDetEps) return false;                      // det < 0.000001 (double); NaN passes
-    const float inv = 1.0f / det;
-    const float sx = s.o[0] - v0x, sy = s.o[1] - v0y, sz = s.o[2] - v0z;
-    u = ((sx * px + sy * py) + sz * pz) * inv;
-    if (u < 0.0f || u > 1.0f) return false;
-    const float qx = sy * e1z - e1y * sz;                  // qvec = cross(tvec, e1)
-    const float qy = sz * e1x - e1z * sx;
-    const float qz = sx * e1y - e1x * sy;
-    v = ((dx * qx + dy * qy) + dz * qz) * inv;
-    if (v < 0.0f || u + v > 1.0f) return false;
-    t = ((e2x * qx + e2y * qy) + e2z * qz) * inv;
-    return true;
-}
-
-// Leaf triangles [b, e): the (t, i) rule with 0 < t < FLT_MAX.
-__device__ __forceinline__ void gleaf(const GScene &s, GRay &r, uint32_t b, uint32_t e) {
-    for (uint32_t i = b; i < e; ++i) {
-        float t, u, v;
-        if (mt_tuv(s.tris + 9ull * i, s, r, t, u, v) && t > 0.0f && t < FLT_MAX &&
-            (t < r.bt || (t == r.bt && i < r.bi))) {
-            r.bt = t;
-            r.bi = i;
-        }
-    }
-}
-
-// Per-lane stack: slots [0, LDS) in LDS at [slot * kGT] from this lane's base,
-// deeper slots in this thread's memory area (slot-major, grid-interleaved; the
-// layout of bih_trace.hip's TStack, whose spill area this kernel borrows).
-template <int LDS>
-struct GStack {
-    uint32_t *sn;
-    float *smin, *smax;
-    uint32_t *spill;           // + gtid; slot k >= LDS at ((k - LDS) * 3) * gthreads
-    uint64_t gthreads;
-    __device__ __forceinline__ void push(uint32_t sp, uint32_t n, float lo, float hi) const {
-        if (sp < (uint32_t)LDS) {
-            sn[sp * kGT] = n; smin[sp * kGT] = lo; smax[sp * kGT] = hi;
-        } else {
-            uint32_t *q = spill + (uint64_t)(sp - LDS) * 3 * gthreads;
-            q[0] = n; q[gthreads] = __float_as_uint(lo); q[2 * gthreads] = __float_as_uint(hi);
-        }
-    }
-    __device__ __forceinline__ void pop(uint32_t sp, uint32_t &n, float &lo, float &hi) const {
-        if (sp < (uint32_t)LDS) {
-            n = sn[sp * kGT]; lo = smin[sp * kGT]; hi = smax[sp * kGT];
-        } else {
-            const uint32_t *q = spill + (uint64_t)(sp - LDS) * 3 * gthreads;
-            n = q[0]; lo = __uint_as_float(q[gthreads]); hi = __uint_as_float(q[2 * gthreads]);
-        }
-    }
-};
-
-// The walk's prologue (traverse_closest up to its loop, t_lo = 0); true when
-// the ray has nodes to walk, false when its result is final (it misses the
-// scene box, or the tree has no internal node: U <= 1 is one leaf of all N
-// triangles).
-__device__ __forceinline__ bool gray_start(const GScene &s, GRay &r) {
-    r.bt = FLT_MAX;
-    r.bi = kNoHit;
-    r.cur = 0;
-    r.sp = 0;
-    r.ix = 1.0f / r.d[0];
-    r.iy = 1.0f / r.d[1];
-    r.iz = 1.0f / r.d[2];
-    r.sg = (r.ix < 0.0f ? 1u : 0u) | (r.iy < 0.0f ? 2u : 0u) | (r.iz < 0.0f ? 4u : 0u);
-    // scene-AABB slab test, CUDAKernels.cu:237-262 (tMin may be negative)
-    float tMin = (((r.sg & 1) ? s.shi[0] : s.slo[0]) - s.o[0]) * r.ix;
-    float tMax = (((r.sg & 1) ? s.slo[0] : s.shi[0]) - s.o[0]) * r.ix;
-    const float tymin = (((r.sg & 2) ? s.shi[1] : s.slo[1]) - s.o[1]) * r.iy;
-    const float tymax = (((r.sg & 2) ? s.slo[1] : s.shi[1]) - s.o[1]) * r.iy;
-    if ((tMin > tymax) || (tymin > tMax)) return false;
-    if (tymin > tMin) tMin = tymin;
-    if (tymax < tMax) tMax = tymax;
-    const float tzmin = (((r.sg & 4) ? s.shi[2] : s.slo[2]) - s.o[2]) * r.iz;
-    const float tzmax = (((r.sg & 4) ? s.slo[2] : s.shi[2]) - s.o[2]) * r.iz;
-    if ((tMin > tzmax) || (tzmin > tMax)) return false;
-    if (tzmin > tMin) tMin = tzmin;
-    if (tzmax < tMax) tMax = tzmax;
-    if (s.U < 2) {   // single leaf (reference: UB; defined as the oracle's)
-        gleaf(s, r, 0, s.U ? s.N : 0u);
-        return false;
-    }
-    r.tMin = tMin;
-    r.tMax = tMax;
-    r.nd = s.nodes[0];
-    return true;
-}
-
-// One iteration of traverse_closest's loop; true when the walk has ended.
-// The next node's record is requested before the leaves this step visits are
-// tested (they are still tested before the next node's decisions read the
-// best hit: the same decisions, the same hit).
-template <class Stack>
-__device__ __forceinline__ bool gray_step(const GScene &s, GRay &r, const Stack &stk) {
-    const float best = r.bi != kNoHit ? r.bt : __builtin_inff();
-    if (r.tMin > best) {                          // entered beyond the best hit: skip
-        if (r.sp == 0) return true;
-        --r.sp;
-        stk.pop(r.sp, r.cur, r.tMin, r.tMax);
-        r.nd = s.nodes[r.cur];
-        return false;
-    }
-    if (best < r.tMax) r.tMax = best;
-    const uint4 nd = r.nd;
-    const uint32_t ax = (nd.z >> 27) & 3u;
-    const float org = pick3(ax, s.o[0], s.o[1], s.o[2]), inv = pick3(ax, r.ix, r.iy, r.iz);
-    const uint32_t nr = (r.sg >> ax) & 1u;
-    const float t0 = (__uint_as_float(nd.x) - org) * inv;
-    const float t1 = (__uint_as_float(nd.y) - org) * inv;
-    const float tn = nr ? t1 : t0, tf = nr ? t0 : t1;
-    const bool A = r.tMin < tn, B = r.tMax < tf;
-    const uint32_t split = nd.z & kIdxMask, mid = nd.w & kIdxMask;
-    const bool leafL = (nd.z >> 29) & 1u, leafR = (nd.z >> 30) & 1u;
-    const bool leafN = nr ? leafR : leafL, leafF = nr ? leafL : leafR;
-    uint32_t cL = (nd.w >> 27) & 3u, cR = (nd.w >> 29) & 3u;
-    if (leafL && cL == 0) cL = s.dup[split];
-    if (leafR && cR == 0) cR = s.dup[split + 1];
-    const uint32_t nb = nr ? mid : mid - cL, ne = nr ? mid + cR : mid;
-    const uint32_t fb = nr ? mid - cL : mid, fe = nr ? mid : mid + cR;
-    const uint32_t nearc = split + nr, farc = split + 1u - nr;
-    // the leaves this step visits, in the walk's order: [l0b, l0e) then [l1b, l1e)
-    uint32_t l0b = 0, l0e = 0, l1b = 0, l1e = 0;
-    bool pop = false;
-    if (!A && B) {
-        pop = true;
-    } else if (A && B) {
-        if (leafN) { l0b = nb; l0e = ne; pop = true; }
-        else { r.cur = nearc; r.tMax = tn; }
-    } else if (!A && !B) {
-        if (leafF) { l0b = fb; l0e = fe; pop = true; }
-        else { r.cur = farc; r.tMin = tf; }
-    } else {
-        if (leafN && leafF) {
-            l0b = nb; l0e = ne;
-            l1b = fb; l1e = fe;
-            pop = true;
-        } else if (!leafN && leafF) {
-            l0b = fb; l0e = fe;
-            r.cur = nearc; r.tMax = tn;
-        } else if (leafN && !leafF) {
-            l0b = nb; l0e = ne;
-            r.cur = farc; r.tMin = tf;
-        } else {
-            stk.push(r.sp, farc, tf, r.tMax);
-            ++r.sp;
-            r.cur = nearc; r.tMax = tn;
-        }
-    }
-    bool fin = false;
-    if (pop) {
-        if (r.sp == 0) {
-            fin = true;
-        } else {
-            --r.sp;
-            stk.pop(r.sp, r.cur, r.tMin, r.tMax);
-        }
-    }
-    if (!fin) r.nd = s.nodes[r.cur];
-    gleaf(s, r, l0b, l0e);
-    gleaf(s, r, l1b, l1e);
-    return fin;
-}
-
 // LDS: stack slots per lane kept in LDS.  POW2: spp is a power of two (tiles
 // of TW x TH pixels, the hit mask's layout).
 template <int LDS, bool POW2>
@@ -269,23 +70,9 @@ __global__ void __launch_bounds__(kGT) k_gbuffer(const GArgs a) {
     __shared__ float s_min[LDS * kGT];
     __shared__ float s_max[LDS * kGT];
     const uint32_t lane = threadIdx.x;
-    GStack<LDS> stk;
-    stk.sn = s_node + lane;
-    stk.smin = s_min + lane;
-    stk.smax = s_max + lane;
-    stk.gthreads = (uint64_t)gridDim.x * kGT;
-    stk.spill = a.spill + (uint64_t)blockIdx.x * kGT + lane;
-    GScene sc;
-    sc.nodes = a.nodes;
-    sc.tris = a.tris;
-    sc.dup = a.dup;
-    for (int k = 0; k < 3; ++k) {
-        sc.slo[k] = a.hdr->scene_lo[k];
-        sc.shi[k] = a.hdr->scene_hi[k];
-        sc.o[k] = a.cam[k];
-    }
-    sc.U = a.hdr->n_unique;
-    sc.N = a.hdr->n_tris;
+    // (the stack's layout is the ray queries', whose spill area this kernel borrows)
+    const dev::LaneStack<LDS> stk(s_node, s_min, s_max, a.spill);
+    const dev::ClosestScene sc = dev::load_closest_scene(a.hdr, a.nodes, a.tris, a.dup);
     const uint64_t P = (uint64_t)a.nrows * a.w;
     const uint32_t spp = a.spp;
     const bool planes = a.depth || a.prim || a.bary || a.normal || a.coverage;
@@ -324,7 +111,7 @@ __global__ void __launch_bounds__(kGT) k_gbuffer(const GArgs a) {
         const uint64_t lp = (uint64_t)lr * a.w + x;
         bool walk = valid;
         if (POW2 && a.hit_mask) walk = valid && ((a.hit_mask[tile] >> lane) & 1ull);
-        GRay r;
+        dev::ClosestRay r;
         r.bt = FLT_MAX;
         r.bi = kNoHit;
         if (walk) {
@@ -341,8 +128,8 @@ __global__ void __launch_bounds__(kGT) k_gbuffer(const GArgs a) {
             const float fu = ((float)x + ru) / (float)a.w, fv = ((float)y + rv) / (float)a.h;
             // Camera::GetRay direction, Camera.cu:18-20
             for (int k = 0; k < 3; ++k) r.d[k] = ((a.cam[3 + k] + fu * a.cam[6 + k]) + fv * a.cam[9 + k]) - a.cam[k];
-            if (gray_start(sc, r)) {
-                while (!gray_step(sc, r, stk)) {}
+            if (dev::closest_start<false>(sc, r, a.cam, 0.0f)) {
+                while (!dev::closest_step<false>(sc, r, a.cam, 0.0f, stk)) {}
             }
         }
         // the sample's record: the accepted triangle's test once more (the
@@ -351,7 +138,7 @@ __global__ void __launch_bounds__(kGT) k_gbuffer(const GArgs a) {
         float t = FLT_MAX, u = 0.0f, vv = 0.0f;
         uint32_t prim = kNoHit;
         if (hit) {
-            (void)mt_tuv(sc.tris + 9ull * r.bi, sc, r, t, u, vv);
+            (void)dev::mt_tuv(sc.tris + 9ull * r.bi, a.cam, r.d, t, u, vv);
             prim = a.tri_idx[r.bi];
         }
         if (a.hits && valid)

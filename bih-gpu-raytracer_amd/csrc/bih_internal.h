@@ -315,8 +315,9 @@ int launch_rng_sync(unsigned long long *stamps, uint32_t *buf0, uint32_t *buf1, 
                     uint32_t nrows, uint32_t spp, uint32_t target, uint32_t seq, int device, void *stream);
 const uint32_t *rng_tables_device(int device);      // xorwow_init_tables_host() on the device
 // config C4 (bih_whitted.hip): device bytes of the ray queues for `rays`
-// samples, and the frame's launches (k_wh_gen, 9 x k_wh_trace, k_wh_shade);
-// ev_k0/ev_k1 bracket the trace launches.  d_hits (optional): u32 hit count
+// samples, and the frame's launches (k_wh_gen, 9 x k_wh_trace -- the per-lane
+// kernel, for every tree -- and k_wh_shade); ev_k0/ev_k1 bracket the trace
+// launches.  d_hits (optional): u32 hit count
 // per sample.
 size_t whitted_bytes(uint64_t rays);
 int launch_whitted(const RenderArgs &a, void *mem, uint64_t rays, uint32_t *d_hits, void *stream, void *ev_k0,
@@ -328,6 +329,8 @@ int whitted_work(const void *mem, uint64_t rays, uint32_t ray_counts[9], unsigne
 // u32, max_blocks = trace_grid_blocks(device), the persistent grid's cap.
 // lds_slots: kTraceLdsTest selects the instantiation that keeps only that many
 // stack slots per lane on chip (BIH_PARAM_TRACE_LDS_SLOTS), anything else kTraceLds.
+// The stack is bih_closest.h's LaneStack, shared with the G-buffer and C4, so
+// the small instantiation exercises the spill code of all three.
 constexpr int kTraceLds = 10;       // as kWLds (bih_whitted.hip)
 constexpr int kTraceLdsTest = 2;
 uint32_t trace_grid_blocks(int device);

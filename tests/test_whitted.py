@@ -119,12 +119,12 @@ def test_oracle_whitted_primary_hits_match_primary_render(oracle_mod):
 
 # --- GPU parity (bih_render_whitted_device vs the oracle) ----------------------
 
-def _whitted_device(bihrt, g, w, h, frame, rows=None, spp=4):
+def _whitted_device(bihrt, g, w, h, frame, rows=None, spp=4, cam=None):
     import torch
     nrows = rows.nrows if rows is not None else h
     out = torch.zeros(nrows * w, dtype=torch.int32, device="cuda")
     hits = torch.zeros(nrows * w * spp, dtype=torch.int32, device="cuda")
-    r = bihrt.Renderer(g, w, h, spp=spp)
+    r = bihrt.Renderer(g, w, h, spp=spp, camera=bihrt.Camera.from_list(cam) if cam is not None else None)
     r.render_whitted_device(out.data_ptr(), frame, rows=rows, hits_ptr=hits.data_ptr())
     r.sync()
     return (out.cpu().numpy().view(np.uint32).reshape(nrows, w),
@@ -186,6 +186,71 @@ def test_whitted_work_counters_match_oracle(scene, gpu, bihrt_mod, oracle_mod):
     assert np.array_equal(img0, ref)
     with pytest.raises(bihrt_mod.BihError):
         r.whitted_work()                               # the last render had no counters
+
+
+@pytest.mark.gpu
+def test_whitted_empty_scene_matches_oracle(gpu, bihrt_mod, oracle_mod):
+    """A tree of no triangles (U = 0): every sample misses, in the image and
+    in the per-sample hit counts, as the oracle's."""
+    tris = np.zeros((0, 9), np.float32)
+    g = bihrt_mod.GPUArrayManager(tris)
+    ot = oracle_mod.OracleTree(tris)
+    w, h = 64, 48
+    for frame in (0, 2):
+        img, hits = _whitted_device(bihrt_mod, g, w, h, frame)
+        ref, _, dep = ot.render_whitted(w, h, frame=frame, depths=True)
+        assert not dep.any() and not hits.any(), frame
+        assert np.array_equal(hits, dep), frame
+        assert np.array_equal(img, ref), frame
+
+
+def _groove():
+    """A one-leaf tree that is hit more than once: two triangles with the same
+    bounding box (one Morton code, U = 1, N = 2) that cross at right angles and
+    face upwards, and a camera looking down into the groove: samples hit 0, 1
+    or 2 times, the second hit with a bounce's t_lo."""
+    s = 2.0
+    tris = np.array([[-s, -s, -s, s, -s, -s, 0, s, s], [-s, -s, s, s, -s, s, 0, s, -s]], F32)
+    cam = np.array([0.3, 0.2, 6, -3.7, -2.8, 0, 8, 0, 0, 0, 6, 0], F32)
+    return tris, cam
+
+
+def test_oracle_groove_is_one_leaf_with_second_hits(oracle_mod):
+    tris, cam = _groove()
+    ot = oracle_mod.OracleTree(tris)
+    _, _, dep = ot.render_whitted(64, 48, cam=cam, depths=True)
+    assert ot.U == 1 and (dep == 0).any() and (dep == 1).any() and (dep == 2).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene", ["one_tri", "dup_all", "groove"])
+def test_whitted_one_leaf_work_counters(scene, gpu, bihrt_mod, oracle_mod):
+    """A one-leaf tree (U = 1) with BIH_PARAM_WHITTED_COUNTERS on: its rays end
+    in the walk's prologue, hits included (the reference camera sees the back of
+    one_tri and dup_all: no hits; groove has first and second hits).  Image and
+    hit counts are the oracle's, rays[d] = samples with at least d hits, and no
+    nodes or triangles are counted (include/bih.h: no counts for a one-leaf
+    tree); groove is then rendered without counters too."""
+    tris, cam = _groove() if scene == "groove" else (edge_scenes()[scene], None)
+    g = bihrt_mod.GPUArrayManager(tris)
+    ot = oracle_mod.OracleTree(tris)
+    w, h = 64, 48
+    refs = {f: ot.render_whitted(w, h, frame=f, cam=cam, depths=True) for f in (0, 2)}
+    g.set_param(bihrt_mod.PARAM_WHITTED_COUNTERS, 1)
+    r = bihrt_mod.Renderer(g, w, h)
+    for frame, (ref, _, dep) in refs.items():
+        img, hits = _whitted_device(bihrt_mod, g, w, h, frame, cam=cam)
+        wk = r.whitted_work()
+        assert np.array_equal(hits, dep), (scene, frame, int((hits != dep).sum()))
+        assert np.array_equal(img, ref), (scene, frame)
+        for d in range(9):
+            assert wk["rays"][d] == int((dep >= d).sum()), (frame, d)
+        assert not any(wk["nodes"]) and not any(wk["tris"]), (frame, wk)
+    g.set_param(bihrt_mod.PARAM_WHITTED_COUNTERS, 0)
+    if scene == "groove":
+        for frame, (ref, _, dep) in refs.items():
+            img, hits = _whitted_device(bihrt_mod, g, w, h, frame, cam=cam)
+            assert np.array_equal(hits, dep) and np.array_equal(img, ref), frame
 
 
 @pytest.mark.gpu
