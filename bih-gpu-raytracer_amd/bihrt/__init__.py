@@ -21,7 +21,7 @@ import numpy as np
 from . import scenes  # noqa: F401
 from ._lib import (PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_STATIC_SOUP,
                    PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS, PARAM_GBUFFER_MASK,
-                   NO_HIT, QUERY_CLOSEST, QUERY_OCCLUDED, GBuffer, Hit, Ray, TRAVERSE_ANYHIT,
+                   NO_HIT, LIGHT_DTYPE, MAX_LIGHTS, SHADOW_T_LO, QUERY_CLOSEST, QUERY_OCCLUDED, Direct, GBuffer, Hit, Light, Ray, TRAVERSE_ANYHIT,
                    TRAVERSE_REFERENCE, BihError, Camera, Framebuffer, Rows, Scene, TreeInfo, check, load)
 from . import _lib
 
@@ -54,6 +54,20 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), (
 # G-buffer pixel planes (bih_gbuffer): name -> (dtype, components per pixel)
 GBUFFER_PLANES = {"depth": (np.float32, 1), "prim": (np.uint32, 1), "bary": (np.float32, 2),
                   "normal": (np.float32, 3), "coverage": (np.uint32, 1)}
+
+
+# the planes of a direct-lighting render (bih_direct): name -> (dtype, values
+# per pixel; 0: one per sample); lights are LIGHT_DTYPE arrays (bih_light)
+DIRECT_PLANES = {"lit": (np.uint64, 0), "irradiance": (np.float32, 1), "rgba": (np.uint32, 1)}
+
+
+def pack_lights(lights) -> np.ndarray:
+    """(k,) LIGHT_DTYPE array (bih_light records) of a LIGHT_DTYPE array or of
+    (k, 4) rows {dir.x, dir.y, dir.z, weight}."""
+    a = np.asarray(lights)
+    if a.dtype != LIGHT_DTYPE:
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 4).view(LIGHT_DTYPE).reshape(-1)
+    return np.ascontiguousarray(a).reshape(-1)
 
 
 def pack_rays(orig, dirs, t_lo=0.0) -> np.ndarray:
@@ -291,6 +305,45 @@ class Renderer:
                                                frame, self.seed, C.byref(rows) if rows is not None else None,
                                                C.byref(gb), C.c_void_p(stream or 0)), "bih_render_gbuffer_device")
 
+    def render_direct(self, lights, frame: int | None = None, rows: Rows | None = None,
+                      planes=("lit", "irradiance", "rgba")) -> dict:
+        """One frame's direct lighting into host arrays (bih_render_direct;
+        synchronous).  lights: a LIGHT_DTYPE array or (k, 4) rows {dir, weight},
+        k <= MAX_LIGHTS, dir towards the light (scenes.sky_dome makes a sky).
+        Returns a dict of the planes asked for (DIRECT_PLANES): "lit"
+        (nrows*w*spp,) uint64, bit k = light k reaches sample p*spp + s;
+        "irradiance" (nrows, w) float32; "rgba" (nrows, w) uint32 grey."""
+        f = self.frame if frame is None else frame
+        nrows = rows.nrows if rows is not None else self.h
+        lt = pack_lights(lights)
+        out, dp = {}, Direct()
+        for name in planes:
+            dt, k = DIRECT_PLANES[name]
+            out[name] = np.zeros((nrows, self.w) if k else nrows * self.w * self.spp, dt)
+            setattr(dp, name, out[name].ctypes.data)
+        check(load().bih_render_direct(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
+                                       self.seed, C.byref(rows) if rows is not None else None,
+                                       C.c_void_p(lt.ctypes.data), lt.shape[0], C.byref(dp)), "bih_render_direct")
+        self.frame = f + 1
+        return out
+
+    def render_direct_device(self, ptrs: dict, lights, frame: int, rows: Rows | None = None,
+                             stream: int | None = None):
+        """Asynchronous direct-lighting render into device memory
+        (bih_render_direct_device): ptrs maps plane names ("lit", "irradiance",
+        "rgba") to device pointers; planes left out are not written.  lights is
+        host memory (as render_direct's), copied by the call."""
+        dp = Direct()
+        for name, ptr in ptrs.items():
+            if name not in DIRECT_PLANES:
+                raise KeyError(name)
+            setattr(dp, name, ptr or None)
+        lt = pack_lights(lights)
+        check(load().bih_render_direct_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
+                                              frame, self.seed, C.byref(rows) if rows is not None else None,
+                                              C.c_void_p(lt.ctypes.data), lt.shape[0], C.byref(dp),
+                                              C.c_void_p(stream or 0)), "bih_render_direct_device")
+
     def whitted_work(self) -> dict:
         """Per bounce d = 0..8 of the last Whitted render (run with
         PARAM_WHITTED_COUNTERS on): rays traced, BIH nodes entered, triangles
@@ -386,4 +439,5 @@ __all__ = ["GPUArrayManager", "Renderer", "Model", "load_obj", "host_register", 
            "camera_ray_bound", "device_count", "unpack_rgba", "write_ppm", "scenes", "TRAVERSE_ANYHIT",
            "TRAVERSE_REFERENCE", "PARAM_ITEM_TILES", "PARAM_PAIR_CAP", "PARAM_BINS_CAP", "PARAM_FORCE_FALLBACK",
            "PARAM_WHITTED_COUNTERS", "PARAM_STATIC_SOUP", "PARAM_TEST_ALLOC_FAIL", "PARAM_TRACE_LDS_SLOTS",
-           "PARAM_GBUFFER_MASK", "GBuffer", "GBUFFER_PLANES", "QUERY_CLOSEST", "QUERY_OCCLUDED", "NO_HIT", "Ray", "Hit", "RAY_DTYPE", "HIT_DTYPE", "pack_rays"]
+           "PARAM_GBUFFER_MASK", "GBuffer", "GBUFFER_PLANES", "QUERY_CLOSEST", "QUERY_OCCLUDED", "NO_HIT", "Ray", "Hit", "RAY_DTYPE", "HIT_DTYPE", "pack_rays",
+           "Light", "Direct", "LIGHT_DTYPE", "DIRECT_PLANES", "MAX_LIGHTS", "SHADOW_T_LO", "pack_lights"]

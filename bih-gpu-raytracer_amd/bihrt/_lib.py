@@ -10,6 +10,8 @@ import ctypes as C
 import os
 import re
 
+import numpy as np
+
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REPO_DIR = os.path.dirname(PKG_DIR)
 LIB_PATH = os.environ.get("BIH_LIB") or os.path.join(PKG_DIR, "lib", "libbih_amd.so")
@@ -30,6 +32,9 @@ PARAM_GBUFFER_MASK = 9      # tests / A-B: 0 = G-buffer renders walk every sampl
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1   # bih_trace / bih_trace_device
 NO_HIT = 0xFFFFFFFF
 MAX_RAYS = 1 << 30
+MAX_LIGHTS = 64           # bih_render_direct*: one bit each of a sample's lit word
+LIGHT_DTYPE = np.dtype([("dir", np.float32, 3), ("weight", np.float32)])   # numpy view of a bih_light array
+SHADOW_T_LO = 1e-4        # BIH_SHADOW_T_LO
 (ARR_MORTON_SORTED, ARR_TRI_INDEX, ARR_UNIQUE_MC, ARR_DUP_COUNT, ARR_FIRST_IDX, ARR_LEAF_PARENT,
  ARR_CLIP, ARR_AXIS, ARR_CHILDREN, ARR_IS_LEAF, ARR_PARENT, ARR_TRI_LO, ARR_TRI_HI) = range(13)
 
@@ -87,6 +92,16 @@ class GBuffer(C.Structure):
     """bih_gbuffer: six plane pointers, any of them NULL (not written)."""
     _fields_ = [("hits", C.c_void_p), ("depth", C.c_void_p), ("prim", C.c_void_p), ("bary", C.c_void_p),
                 ("normal", C.c_void_p), ("coverage", C.c_void_p)]
+
+
+class Light(C.Structure):
+    """bih_light (16 bytes): a directional light, dir towards the light."""
+    _fields_ = [("dir", C.c_float * 3), ("weight", C.c_float)]
+
+
+class Direct(C.Structure):
+    """bih_direct: three plane pointers, any of them NULL (not written)."""
+    _fields_ = [("lit", C.c_void_p), ("irradiance", C.c_void_p), ("rgba", C.c_void_p)]
 
 
 class BinsStats(C.Structure):
@@ -170,13 +185,17 @@ def load():
                                             C.POINTER(GBuffer), vp]
     L.bih_render_gbuffer.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
                                      C.POINTER(GBuffer)]
+    L.bih_render_direct_device.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                           vp, u32, C.POINTER(Direct), vp]
+    L.bih_render_direct.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                    vp, u32, C.POINTER(Direct)]
     for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
                  "bih_render_whitted_device", "bih_render_whitted", "bih_render_device_frames",
                  "bih_bins_get_stats", "bih_reserve", "bih_tree_set_param", "bih_whitted_work",
                  "bih_host_register", "bih_host_unregister", "bih_render_history", "bih_trace_device", "bih_trace",
-                 "bih_render_gbuffer_device", "bih_render_gbuffer"):
+                 "bih_render_gbuffer_device", "bih_render_gbuffer", "bih_render_direct_device", "bih_render_direct"):
         getattr(L, name).restype = i32
     _lib = L
     return L

@@ -15,6 +15,7 @@ Mirrors the reference application shell without windowing or GL interop:
 usage:  python -m bihrt --mesh sponza --resources path/to/resources --frames 10 \
             --out frames/f%04d.ppm [--width 640 --height 480 --no-rebuild]
             [--gbuffer frames/g%04d.npz]   (depth, prim, bary, normal, coverage per written frame)
+            [--direct frames/d%04d.ppm [--sun X,Y,Z] [--sky K]]   (sky- and sun-lit grey preview per written frame)
         python -m bihrt --obj file.obj ...     (explicit path)
         python -m bihrt --scene cornell|torus|soup[:N] ...   (built-in scenes)
 """
@@ -71,12 +72,17 @@ class App:
         return tris.shape[0]
 
     def run(self, frames: int, out_pattern: str | None = None, rebuild: bool = True,
-            every: int = 1, gbuffer_pattern: str | None = None):
+            every: int = 1, gbuffer_pattern: str | None = None, direct_pattern: str | None = None,
+            lights=None):
         """App::Run for a fixed number of frames: Renderer::Render each frame
         (BIH rebuild + render), optional PPM output; returns the frames.
         gbuffer_pattern: one .npz of the frame's G-buffer planes
-        (Renderer.render_gbuffer) per written frame."""
+        (Renderer.render_gbuffer) per written frame.  direct_pattern: one PPM
+        of the frame's direct lighting under `lights` (Renderer.render_direct's
+        rgba plane) per written frame; lights = None: scenes.sky_dome(8)."""
         assert self.renderer is not None, "load_models first"
+        if direct_pattern and lights is None:
+            lights = scenes.sky_dome(8)
         imgs = []
         last = time.perf_counter()
         for f in range(frames):
@@ -99,6 +105,12 @@ class App:
                 if d:
                     os.makedirs(d, exist_ok=True)
                 np.savez(path, **self.renderer.render_gbuffer(f))
+            if direct_pattern and f % every == 0:
+                path = direct_pattern % f if "%" in direct_pattern else direct_pattern
+                d = os.path.dirname(path)
+                if d:
+                    os.makedirs(d, exist_ok=True)
+                write_ppm(path, self.renderer.render_direct(lights, f, planes=("rgba",))["rgba"])
             imgs.append(img)
         return imgs
 
@@ -118,6 +130,10 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default=None, help="PPM path; '%%d' formats the frame number")
     ap.add_argument("--gbuffer", default=None, metavar="PATTERN",
                     help=".npz path of the G-buffer planes of each written frame; '%%d' formats the frame number")
+    ap.add_argument("--direct", default=None, metavar="PATTERN",
+                    help="PPM path of the direct-lighting preview of each written frame; '%%d' formats the frame number")
+    ap.add_argument("--sun", default=None, metavar="X,Y,Z", help="--direct: direction towards the sun")
+    ap.add_argument("--sky", type=int, default=None, metavar="K", help="--direct: sky directions (default 8; 0: none)")
     ap.add_argument("--every", type=int, default=1, help="write every k-th frame")
     ap.add_argument("--no-rebuild", action="store_true",
                     help="build once (the reference rebuilds every frame)")
@@ -133,7 +149,22 @@ def main(argv=None) -> int:
         scene = a.obj
     else:
         scene = builtin_scene(a.scene)
+    lights = None
+    if not a.direct and (a.sun is not None or a.sky is not None):
+        ap.error("--sun and --sky belong to --direct")
+    if a.direct:
+        a.sky = 8 if a.sky is None else a.sky
+        sun = [float(x) for x in a.sun.split(",")] if a.sun else None
+        if sun is not None and len(sun) != 3:
+            ap.error("--sun takes X,Y,Z")
+        if a.sky < 0 or a.sky + (sun is not None) > 64 or a.sky + (sun is not None) == 0:
+            ap.error("--direct needs 1..64 lights (--sky K, --sun)")
+        if a.sky:
+            lights = scenes.sky_dome(a.sky, sun)
+        else:
+            lights = scenes.sky_dome(1, sun)[:1]
     app = App(a.width, a.height, a.spp, device=a.device)
     app.load_models(scene)
-    app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every, gbuffer_pattern=a.gbuffer)
+    app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every, gbuffer_pattern=a.gbuffer,
+            direct_pattern=a.direct, lights=lights)
     return 0

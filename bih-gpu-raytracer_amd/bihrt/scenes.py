@@ -15,6 +15,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._lib import LIGHT_DTYPE
+
 _GOLD = np.uint64(0x9E3779B97F4A7C15)
 
 
@@ -209,3 +211,28 @@ def write_obj(path: str, tris: np.ndarray, shared: bool = False):
             f.write("v %s %s %s\n" % tuple(str(x) for x in p))
         for t in idx.reshape(-1, 3):
             f.write("f %d %d %d\n" % tuple(int(k) + 1 for k in t))
+
+
+def sky_dome(k: int, sun=None) -> np.ndarray:
+    """Directional lights of a uniform sky for Renderer.render_direct: k
+    Fibonacci directions on the upper (+y) hemisphere, (k,) float32 records
+    {dir[3], weight} (bihrt.LIGHT_DTYPE), unit length.  The weights make a
+    horizontal unoccluded surface (normal +y) sum to 1: weight = 1 / sum(dir.y).
+    sun: an optional (x, y, z) direction towards the sun, normalised and
+    prepended with weight 1 (k + 1 lights)."""
+    if k < 1:
+        raise ValueError("sky_dome needs at least one direction")
+    i = np.arange(k, dtype=np.float64) + 0.5
+    y = i / k                                     # uniform in height: uniform on the hemisphere
+    r = np.sqrt(np.maximum(0.0, 1.0 - y * y))
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    out = np.zeros((k, 4), np.float64)
+    out[:, 0], out[:, 1], out[:, 2] = r * np.cos(phi), y, r * np.sin(phi)
+    out[:, 3] = 1.0 / y.sum()
+    if sun is not None:
+        s = np.asarray(sun, np.float64).reshape(3)
+        n = np.linalg.norm(s)
+        if not n > 0:
+            raise ValueError("sun direction must be non-zero")
+        out = np.concatenate([[[*(s / n), 1.0]], out])
+    return np.ascontiguousarray(out, np.float32).view(LIGHT_DTYPE).reshape(-1)

@@ -34,7 +34,9 @@ constexpr int kRngBufs = kSlots + 1;
 // one-frame renders also take the shared grid while another render is in flight
 constexpr bool kShareOneFrame = BIH_SHARE_ONE_FRAME != 0;
 constexpr size_t kEntryBytes = 16 * bih::kBinEntryF4;   // frustum-bin list entry
-constexpr size_t kTraceCursorBytes = 256;               // the trace cursor's allocation (one u32 used)
+constexpr size_t kTraceCursorBytes = 256;               // the trace cursor's allocation (u32 at 0: rays / tiles taken;
+                                                        // direct lighting: u64 at 8 items taken, u32 at 16 listed samples)
+constexpr size_t kDirectSampleBytes = 16 + 8 + 4;       // dr_mem per sample: record, facing mask, list entry
 
 // Per-camera structures (bih_render.hip / bih_bins.hip): primary-ray records,
 // frustum bins and the tile queue of one camera.  A tree keeps kCamSets of
@@ -270,6 +272,18 @@ struct bih_tree {
     int gb_prev_slot = -1;           // the last G-buffer launch's slot (its evd orders the next mask render)
     char *gb_stage = nullptr;        // bih_render_gbuffer's device planes
     size_t gb_stage_cap = 0;         // bytes
+    // Direct-lighting renders (bih_direct.hip) are a G-buffer launch (hits
+    // only, into dr_mem) with the shadow kernels behind it on the same stream,
+    // inside the same ev_trace link.  Their own: per sample the hit record
+    // and the list of hit samples with their facing masks, sized by the
+    // call's shape; the lit words of calls whose caller passes none; and the
+    // host entry's device planes.
+    char *dr_mem = nullptr;
+    size_t dr_cap = 0;               // samples (kDirectSampleBytes each)
+    unsigned long long *dr_lit = nullptr;   // lit words of a call without a `lit` plane
+    size_t dr_lit_cap = 0;           // samples
+    char *dr_stage = nullptr;        // bih_render_direct's device planes
+    size_t dr_stage_cap = 0;         // bytes
 };
 
 namespace {
@@ -710,6 +724,9 @@ void bih_free(bih_tree *tr) {
     if (tr->gb_mask) (void)hipFree(tr->gb_mask);
     if (tr->gb_scratch) (void)hipFree(tr->gb_scratch);
     if (tr->gb_stage) (void)hipFree(tr->gb_stage);
+    if (tr->dr_mem) (void)hipFree(tr->dr_mem);
+    if (tr->dr_lit) (void)hipFree(tr->dr_lit);
+    if (tr->dr_stage) (void)hipFree(tr->dr_stage);
     if (tr->ev_trace) (void)hipEventDestroy(tr->ev_trace);
     for (int k = 0; k < kSlots; ++k) {
         if (tr->ev0[k]) (void)hipEventDestroy(tr->ev0[k]);
@@ -770,7 +787,8 @@ int bih_tree_get_info(const bih_tree *tr, bih_tree_info *info) {
                           (size_t)kSlots * tr->fbq_cap * 8) * 4 +
                          (tr->wh_mem ? bih::whitted_bytes(tr->wh_rays) : 0) + tr->wh_mask_cap * 8 + tr->stamp_cap * 8 +
                          (tr->tq_cursor ? kTraceCursorBytes : 0) + tr->tq_spill_words * 4 + tr->tq_stage_cap +
-                         tr->gb_mask_cap * 8 + tr->gb_scratch_cap * 4 + tr->gb_stage_cap;
+                         tr->gb_mask_cap * 8 + tr->gb_scratch_cap * 4 + tr->gb_stage_cap +
+                         tr->dr_cap * kDirectSampleBytes + tr->dr_lit_cap * 8 + tr->dr_stage_cap;
     info->build_ms = tr->build_ms;
     info->device_allocs = tr->allocs + tr->t.allocs + tr->back[0].allocs + tr->back[1].allocs;
     return BIH_OK;
@@ -2229,10 +2247,20 @@ static int gbuffer_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, 
     return BIH_OK;
 }
 
+// What a direct-lighting call adds to its G-buffer launch: the lights (host
+// memory) and the caller's planes.  The launch's hits go to dr_mem.
+struct DirectJob {
+    const bih_light *lights;
+    uint32_t n_lights;
+    bih_direct planes;
+};
+
 // bih_render_gbuffer_device under the tree's lock, arguments checked, nrows > 0.
+// dj: the call is bih_render_direct_device's (pl.hits = dr_mem, sized for it):
+// the records carry sorted positions and the direct-lighting kernels follow.
 static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                           uint32_t frame, uint64_t seed, const bih_rows &rows, const bih_gbuffer &pl,
-                          void *stream) {
+                          void *stream, const DirectJob *dj = nullptr) {
     if (!tr->t.hdr) return BIH_ERR_INVALID;   // no tree was ever built into this buffer
     hipStream_t st = stream ? (hipStream_t)stream : tr->stream;
     int rc = ensure_trace(tr);
@@ -2328,7 +2356,22 @@ static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
         e = hipEventRecord(tr->ev0[slot], st);
         if (e != hipSuccess) return map_hip((int)e);
     }
-    rc = bih::launch_gbuffer(tr->t, a, p, mask, tr->prm.trace_lds, tr->tq_cursor, tr->tq_spill, tr->tq_blocks, st);
+    rc = bih::launch_gbuffer(tr->t, a, p, mask, tr->prm.trace_lds, tr->tq_cursor, tr->tq_spill, tr->tq_blocks, st,
+                             dj != nullptr);
+    if (rc == 0 && dj) {
+        // dr_mem: records, facing masks, list (each at a multiple of 8 bytes)
+        const size_t S = tr->dr_cap;
+        char *rec = tr->dr_mem, *face = rec + 16 * S, *list = face + 8 * S;
+        bih::DirectPlanes dp;
+        dp.lit = dj->planes.lit ? reinterpret_cast<unsigned long long *>(dj->planes.lit) : tr->dr_lit;
+        dp.irradiance = dj->planes.irradiance;
+        dp.rgba = dj->planes.rgba;
+        rc = bih::launch_direct(tr->t, a, dp, &dj->lights[0].dir[0], dj->n_lights, rec,
+                                reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
+                                tr->prm.trace_lds, tr->tq_cursor + 4,
+                                reinterpret_cast<unsigned long long *>(tr->tq_cursor + 2), tr->tq_spill,
+                                tr->tq_blocks, st);
+    }
     // (a failed launch may have left work on st that uses the cursor: the event covers it)
     e = hipEventRecord(tr->ev_trace, st);
     if (e == hipSuccess) tr->trace_used = true;
@@ -2407,6 +2450,111 @@ int bih_render_gbuffer(const bih_tree *ctr, const bih_camera *cam, uint32_t w, u
     for (int k = 0; k < 6 && rc == BIH_OK; ++k)
         if (host[k]) {
             e = hipMemcpyAsync(host[k], tr->gb_stage + off[k], size[k], hipMemcpyDeviceToHost, tr->stream);
+            if (e != hipSuccess) rc = map_hip((int)e);
+        }
+    e = hipStreamSynchronize(tr->stream);
+    return rc ? rc : map_hip((int)e);
+}
+
+// Argument checks of both direct-lighting entries, in the header's order; none
+// touches the tree or a device.  *rows: the rows of the call.
+static int direct_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                        const bih_rows *rows_in, const bih_light *lights, uint32_t n_lights, const bih_direct *pl,
+                        bih_rows *rows) {
+    // the G-buffer's checks; its "all planes NULL" is about the three planes here
+    static float some_plane;
+    bih_gbuffer g = {};
+    if (pl && (pl->lit || pl->irradiance || pl->rgba)) g.depth = &some_plane;
+    const int rc = gbuffer_check(tr, cam, w, h, spp, rows_in, pl ? &g : nullptr, rows);
+    if (rc) return rc;
+    if (!lights || n_lights == 0 || n_lights > BIH_MAX_LIGHTS) return BIH_ERR_INVALID;
+    if ((uintptr_t)pl->lit & 7u) return BIH_ERR_INVALID;   // the lit words take 64-bit atomics
+    return BIH_OK;
+}
+
+// bih_render_direct_device under the tree's lock, arguments checked, nrows > 0.
+static int direct_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t frame,
+                         uint64_t seed, const bih_rows &rows, const bih_light *lights, uint32_t n_lights,
+                         const bih_direct &pl, void *stream) {
+    const size_t S = (size_t)rows.nrows * w * spp;
+    const bool own_lit = !pl.lit && tr->dr_lit_cap < S;
+    if ((tr->dr_cap < S || own_lit) && tr->trace_used) {
+        // (the users of both buffers are direct-lighting launches: each ends before its ev_trace record)
+        const hipError_t e = hipEventSynchronize(tr->ev_trace);
+        if (e != hipSuccess) return map_hip((int)e);
+    }
+    if (own_lit) {
+        if (tr->dr_lit) (void)hipFree(tr->dr_lit);
+        tr->dr_lit = nullptr;
+        tr->dr_lit_cap = 0;
+        const hipError_t e = tree_malloc(tr, &tr->dr_lit, S * 8);
+        if (e != hipSuccess) return map_hip((int)e);
+        tr->dr_lit_cap = S;
+    }
+    if (tr->dr_cap < S) {
+        if (tr->dr_mem) (void)hipFree(tr->dr_mem);
+        tr->dr_mem = nullptr;
+        tr->dr_cap = 0;
+        const hipError_t e = tree_malloc(tr, &tr->dr_mem, S * kDirectSampleBytes);
+        if (e != hipSuccess) return map_hip((int)e);
+        tr->dr_cap = S;
+    }
+    static_assert(sizeof(bih_light) == 16 && BIH_MAX_LIGHTS == bih::kMaxLights, "bih_light / kMaxLights");
+    bih_gbuffer g = {};
+    g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
+    const DirectJob dj{lights, n_lights, pl};
+    return gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, g, stream, &dj);
+}
+
+int bih_render_direct_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                             uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light *lights,
+                             uint32_t n_lights, const bih_direct *d_planes, void *stream) {
+    bih_rows rows;
+    const int rc = direct_check(ctr, cam, w, h, spp, rows_in, lights, n_lights, d_planes, &rows);
+    if (rc || rows.nrows == 0) return rc;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    return direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_lights, *d_planes, stream);
+}
+
+int bih_render_direct(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                      uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light *lights,
+                      uint32_t n_lights, const bih_direct *host_planes) {
+    bih_rows rows;
+    int rc = direct_check(ctr, cam, w, h, spp, rows_in, lights, n_lights, host_planes, &rows);
+    if (rc || rows.nrows == 0) return rc;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    // device planes of the ones asked for, each at a multiple of 16 bytes
+    const size_t P = (size_t)rows.nrows * w;
+    void *const host[3] = {host_planes->lit, host_planes->irradiance, host_planes->rgba};
+    const size_t size[3] = {P * spp * 8, P * 4, P * 4};
+    size_t off[3], total = 0;
+    for (int k = 0; k < 3; ++k) {
+        off[k] = total;
+        if (host[k]) total += (size[k] + 15) & ~(size_t)15;
+    }
+    if (tr->dr_stage_cap < total) {
+        // (its only users are calls of this function, which wait for their work)
+        if (tr->dr_stage) (void)hipFree(tr->dr_stage);
+        tr->dr_stage = nullptr;
+        tr->dr_stage_cap = 0;
+        const hipError_t e = tree_malloc(tr, &tr->dr_stage, total);
+        if (e != hipSuccess) return map_hip((int)e);
+        tr->dr_stage_cap = total;
+    }
+    auto dev_plane = [&](int k) -> void * { return host[k] ? tr->dr_stage + off[k] : nullptr; };
+    bih_direct d;
+    d.lit = static_cast<uint64_t *>(dev_plane(0));
+    d.irradiance = static_cast<float *>(dev_plane(1));
+    d.rgba = static_cast<uint32_t *>(dev_plane(2));
+    rc = direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_lights, d, nullptr);
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 3 && rc == BIH_OK; ++k)
+        if (host[k]) {
+            e = hipMemcpyAsync(host[k], tr->dr_stage + off[k], size[k], hipMemcpyDeviceToHost, tr->stream);
             if (e != hipSuccess) rc = map_hip((int)e);
         }
     e = hipStreamSynchronize(tr->stream);

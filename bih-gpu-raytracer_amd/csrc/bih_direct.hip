@@ -1,0 +1,289 @@
+// bih_direct.hip -- direct-lighting render (bih_render_direct_device /
+// bih_render_direct, include/bih.h): per primary sample the set of directional
+// lights that reach its hit point, and the pixel's irradiance and grey shade
+// summed from them, on gfx950.
+//
+// Semantics, no new rule: the G-buffer's closest hit
+// of the sample (section 4.5.2), then for every light that faces the hit
+// triangle bih_trace's OCCLUDED query (section 4.5.1) of the ray {o = P, t_lo
+// = BIH_SHADOW_T_LO, d = light direction}, then sums in a stated order.  Every
+// f32 expression is separately rounded (-ffp-contract=off).
+//
+// Three kernels behind the G-buffer launch, which leaves every sample's hit
+// record -- prim = the triangle's sorted position -- in the call's scratch:
+//   k_direct_setup    per sample: the primary direction once more (bih_primary.h),
+//                     P = o + t*d, the triangle's normal, the 64-bit mask of
+//                     facing lights; hit samples with a facing light are
+//                     appended to a list (wave ballot, prefix count, one atomic
+//                     per wave), their record's {t, u, v} becomes P; lit = 0.
+//   k_shadow          the hot path, k_trace's shape (bih_trace.hip): persistent
+//                     one-wave blocks; work item = (listed sample, light k),
+//                     taken from a global cursor; a lane whose walk has ended
+//                     takes the next item while its wave-mates keep walking.
+//                     No ray is written to or read from memory: the origin
+//                     comes from the sample's record, the direction from the
+//                     kernel arguments.  The walk is
+//                     bih_closest.h's ANY walk; an unoccluded item sets its bit
+//                     of the sample's lit word with one 64-bit atomic OR (the
+//                     order of the ORs does not matter: deterministic).
+//   k_direct_resolve  per pixel: the sums, in the header's order.
+// The lights travel in the kernel arguments (the call's copy of the caller's
+// host array): no device buffer of them exists.
+#include <hip/hip_runtime.h>
+#include <float.h>
+
+#include "bih_closest.h"
+#include "bih_internal.h"
+#include "bih_primary.h"
+
+namespace bih {
+namespace {
+
+using dev::ClosestRay;
+using dev::ClosestScene;
+using dev::kNoHit;
+
+constexpr uint32_t kDT = dev::kLanes;    // k_shadow: threads per block, one wave
+constexpr uint32_t kDSetupT = 256;       // k_direct_setup, k_direct_resolve: threads per block
+constexpr int kDRefill = 16;             // idle lanes of a wave that trigger a refill (as k_trace)
+constexpr int kDSteps = 256;             // walk steps per lane between refill checks (as k_trace)
+constexpr float kShadowTLo = 1e-4f;      // BIH_SHADOW_T_LO
+constexpr uint32_t kMissShade = 0x00281414u;   // (20, 20, 40): Whitted's miss shade
+
+struct DLight { float x, y, z, w; };     // bih_light
+
+struct DArgs {
+    float cam[12];              // origin, lower_left, horizontal, vertical
+    uint32_t w, h, spp;
+    uint32_t row0, nrows, band_h, band_step;
+    uint32_t d_base;            // XORWOW Weyl counter at the start of the frame
+    uint32_t n_lights;
+    const TreeHeader *hdr;
+    const uint4 *nodes;
+    const float *tris;          // sorted {v0, e1, e2}
+    const uint32_t *dup;
+    const uint32_t *rng_in;     // 5 planes of nrows*w: XORWOW v at the start of the frame
+    uint4 *rec;                 // [P*spp]: the G-buffer's {t, u, v, sorted position}; listed samples: {P, sorted position}
+    uint32_t *list;             // [P*spp]: listed samples
+    unsigned long long *face;   // [P*spp]: a listed sample's facing lights
+    unsigned long long *lit;    // [P*spp]
+    float *irradiance;          // [P] or null
+    uint32_t *rgba;             // [P] or null
+    uint32_t *count;            // listed samples (zero at launch)
+    unsigned long long *cursor; // items taken so far (zero at launch)
+    uint32_t *spill;
+    DLight lights[kMaxLights];
+};
+
+__global__ void __launch_bounds__(kDSetupT) k_direct_setup(const DArgs a) {
+    const uint64_t P = (uint64_t)a.nrows * a.w;
+    const uint64_t n = P * a.spp;
+    const uint64_t i = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
+    unsigned long long face = 0ull;
+    float pt[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t bi = kNoHit;
+    if (i < n) {
+        const uint4 h = a.rec[i];
+        bi = h.w;
+        if (bi != kNoHit) {
+            const uint64_t lp = i / a.spp;
+            const uint32_t s = (uint32_t)(i - lp * a.spp);
+            const uint32_t lr = (uint32_t)(lp / a.w), x = (uint32_t)(lp - (uint64_t)lr * a.w);
+            const uint32_t y = dev::global_row(lr, a.row0, a.band_h, a.band_step);
+            float d[3], nrm[3];
+            dev::primary_dir(a.cam, a.rng_in, P, lp, a.d_base, s, x, y, a.w, a.h, d);
+            const float t = __uint_as_float(h.x);
+            for (int k = 0; k < 3; ++k) pt[k] = a.cam[k] + t * d[k];
+            dev::tri_normal(a.tris + 9ull * bi, nrm);
+            for (uint32_t k = 0; k < a.n_lights; ++k) {   // (k is uniform: the lights come as scalars)
+                const float c = (nrm[0] * a.lights[k].x + nrm[1] * a.lights[k].y) + nrm[2] * a.lights[k].z;
+                if (c > 0.0f) face |= 1ull << k;
+            }
+        }
+        a.lit[i] = 0ull;
+    }
+    // the wave's listed samples take consecutive list slots: one atomic per wave
+    const bool listed = face != 0ull;
+    const unsigned long long m = __ballot(listed);
+    if (!m) return;
+    const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    uint32_t first = 0;
+    if ((threadIdx.x & (dev::kLanes - 1u)) == 0) first = atomicAdd(a.count, (uint32_t)__popcll(m));
+    first = __builtin_amdgcn_readfirstlane(first);
+    if (listed) {
+        const uint32_t j = first + rk;
+        a.rec[i] = make_uint4(__float_as_uint(pt[0]), __float_as_uint(pt[1]), __float_as_uint(pt[2]), bi);
+        a.list[j] = (uint32_t)i;
+        a.face[j] = face;
+    }
+}
+
+// A work item: where its ray starts, whose bit it decides, and its walk.
+struct SRay {
+    float o[3];
+    uint32_t i, k;              // sample, light
+    ClosestRay w;
+};
+
+__device__ __forceinline__ void sray_write(const DArgs &a, const SRay &r) {
+    if (r.w.bi == kNoHit) atomicOr(a.lit + r.i, 1ull << r.k);
+}
+
+// LDS: stack slots per lane kept in LDS (the rest in this thread's HBM area).
+template <int LDS>
+__global__ void __launch_bounds__(kDT) k_shadow(const DArgs a) {
+    __shared__ uint32_t s_node[LDS * kDT];
+    __shared__ float s_min[LDS * kDT];
+    __shared__ float s_max[LDS * kDT];
+    const uint32_t lane = threadIdx.x;
+    const dev::LaneStack<LDS> stk(s_node, s_min, s_max, a.spill);
+    const ClosestScene sc = dev::load_closest_scene(a.hdr, a.nodes, a.tris, a.dup);
+    const uint32_t K = a.n_lights;
+    const uint64_t n = (uint64_t)*a.count * K;    // items: (listed sample, light)
+    SRay r;
+    bool has = false;          // this lane walks a ray
+    bool more = true;          // (wave-uniform) the cursor may still be short of n
+    for (;;) {
+        // (fetched again while enough lanes stay idle: a non-facing item leaves its lane idle)
+        unsigned long long idle = __ballot(!has);
+        while (more && (__popcll(idle) >= kDRefill || idle == ~0ull)) {
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            unsigned long long first = 0;
+            if (lane == 0) first = atomicAdd(a.cursor, (unsigned long long)cnt);
+            first = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(first >> 32)) << 32) |
+                    __builtin_amdgcn_readfirstlane((uint32_t)first);
+            // (a 64-bit cursor: n < 2^38, and the grid's overshoot is far below 2^63)
+            if (first + cnt >= n) more = false;
+            if (!has && first < n) {
+                const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                // item = first + rk = (j0 * K + k0) + rk: one wide division per fetch (uniform)
+                const uint64_t j0 = first / K;
+                const uint32_t kk = (uint32_t)(first - j0 * K) + rk;
+                const uint64_t j = j0 + kk / K;
+                const uint32_t k = kk % K;
+                if (first + rk < n && ((a.face[j] >> k) & 1ull)) {   // a non-facing item ends at once
+                    r.i = a.list[j];
+                    r.k = k;
+                    const uint4 q = a.rec[r.i];
+                    r.o[0] = __uint_as_float(q.x); r.o[1] = __uint_as_float(q.y); r.o[2] = __uint_as_float(q.z);
+                    // (from the kernel arguments, one 16-byte load per item: a copy in LDS
+                    // costs the walk three waves per CU, 175 against 164 ms)
+                    const DLight l = a.lights[k];
+                    r.w.d[0] = l.x; r.w.d[1] = l.y; r.w.d[2] = l.z;
+                    has = dev::closest_start<true>(sc, r.w, r.o, kShadowTLo);
+                    if (!has) sray_write(a, r);   // missed the box / one-leaf tree: final
+                }
+            }
+            idle = __ballot(!has);
+        }
+        if (!__ballot(has)) {
+            if (!more) break;
+            continue;
+        }
+        if (has) {
+            bool fin = false;
+            for (int k = 0; k < kDSteps && !fin; ++k) fin = dev::closest_step<true>(sc, r.w, r.o, kShadowTLo, stk);
+            if (fin) {
+                sray_write(a, r);
+                has = false;
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kDSetupT) k_direct_resolve(const DArgs a) {
+    __shared__ DLight s_light[kMaxLights];
+    if (threadIdx.x < a.n_lights) s_light[threadIdx.x] = a.lights[threadIdx.x];
+    __syncthreads();
+    const uint64_t P = (uint64_t)a.nrows * a.w;
+    const uint64_t lp = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
+    if (lp >= P) return;
+    float E = 0.0f;
+    bool any = false;
+    for (uint32_t s = 0; s < a.spp; ++s) {
+        const uint64_t i = lp * a.spp + s;
+        const uint32_t bi = a.rec[i].w;
+        any = any || bi != kNoHit;
+        unsigned long long l = a.lit[i];
+        float e = 0.0f;
+        if (l) {
+            float nrm[3];
+            dev::tri_normal(a.tris + 9ull * bi, nrm);
+            while (l) {   // k ascending over the lit bits
+                const DLight q = s_light[__builtin_ctzll(l)];
+                l &= l - 1ull;
+                const float c = (nrm[0] * q.x + nrm[1] * q.y) + nrm[2] * q.z;
+                e = e + q.w * c;
+            }
+        }
+        E = s == 0 ? e : E + e;
+    }
+    E = E / (float)a.spp;
+    if (a.irradiance) a.irradiance[lp] = E;
+    if (a.rgba) {
+        const uint32_t g = (uint32_t)(int)fmaxf(0.0f, fminf(255.0f, 255.0f * E));
+        a.rgba[lp] = any ? (g | (g << 8) | (g << 16)) : kMissShade;
+    }
+}
+
+}  // namespace
+
+int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes &p, const float *lights,
+                  uint32_t n_lights, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
+                  uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0 || n_lights == 0) return 0;
+    if (n_lights > kMaxLights) return (int)hipErrorInvalidValue;
+    DArgs a;
+    for (int k = 0; k < 12; ++k) a.cam[k] = ra.cam[k];
+    a.w = ra.w;
+    a.h = ra.h;
+    a.spp = ra.spp;
+    a.row0 = ra.row0;
+    a.nrows = ra.nrows;
+    a.band_h = ra.band_h;
+    a.band_step = ra.band_step;
+    a.d_base = ra.d_base;
+    a.n_lights = n_lights;
+    a.hdr = t.hdr;
+    a.nodes = t.nodes;
+    a.tris = t.tris_s;
+    a.dup = t.dup_cnt;
+    a.rng_in = ra.rng_in;
+    a.rec = reinterpret_cast<uint4 *>(rec);
+    a.list = list;
+    a.face = face;
+    a.lit = p.lit;
+    a.irradiance = p.irradiance;
+    a.rgba = p.rgba;
+    a.count = count;
+    a.cursor = cursor;
+    a.spill = spill;
+    for (uint32_t k = 0; k < kMaxLights; ++k) {
+        const bool on = k < n_lights;
+        a.lights[k] = DLight{on ? lights[4 * k] : 0.0f, on ? lights[4 * k + 1] : 0.0f, on ? lights[4 * k + 2] : 0.0f,
+                             on ? lights[4 * k + 3] : 0.0f};
+    }
+    hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), st);
+    if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), st);
+    if (e != hipSuccess) return (int)e;
+    const uint64_t P = (uint64_t)ra.nrows * ra.w, n = P * ra.spp;
+    hipLaunchKernelGGL(k_direct_setup, dim3((uint32_t)((n + kDSetupT - 1) / kDSetupT)), dim3(kDSetupT), 0, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    // (the listed samples are counted on the device: the grid covers all of them)
+    const uint64_t need = (n * n_lights + kDT - 1) / kDT;
+    const dim3 grid((uint32_t)(need < max_blocks ? need : max_blocks)), block(kDT);
+    if (lds_slots == (uint32_t)kTraceLdsTest) hipLaunchKernelGGL((k_shadow<kTraceLdsTest>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_shadow<kTraceLds>), grid, block, 0, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    if (p.irradiance || p.rgba) {
+        hipLaunchKernelGGL(k_direct_resolve, dim3((uint32_t)((P + kDSetupT - 1) / kDSetupT)), dim3(kDSetupT), 0, st, a);
+        e = hipGetLastError();
+    }
+    return (int)e;
+}
+
+}  // namespace bih

@@ -26,6 +26,7 @@
 
 #include "bih_closest.h"
 #include "bih_internal.h"
+#include "bih_primary.h"
 
 namespace bih {
 namespace {
@@ -49,7 +50,7 @@ struct GArgs {
     const uint4 *nodes;
     const float *tris;          // sorted {v0, e1, e2}
     const uint32_t *dup;
-    const uint32_t *tri_idx;    // sorted position -> file order
+    const uint32_t *tri_idx;    // sorted position -> file order; null: prim is the sorted position
     const uint32_t *rng_in;     // 5 planes of nrows*w: XORWOW v at the start of the frame
     const unsigned long long *hit_mask;   // per tile (POW2), or null: every sample is walked
     uint4 *hits;                // bih_hit[P*spp] or null
@@ -115,19 +116,9 @@ __global__ void __launch_bounds__(kGT) k_gbuffer(const GArgs a) {
         r.bt = FLT_MAX;
         r.bi = kNoHit;
         if (walk) {
-            // draws 2s, 2s+1 of this pixel's frame (cudaRender :413-415)
-            uint32_t v[5];
-            for (int i = 0; i < 5; ++i) v[i] = a.rng_in[(uint64_t)i * P + lp];
-            uint32_t d = a.d_base;
-            float ru = 0.f, rv = 0.f;
-            for (uint32_t k = 0; k <= s; ++k) {
-                ru = dev::xorwow_uniform(v, d);
-                rv = dev::xorwow_uniform(v, d);
-            }
+            // the sample's ray (bih_primary.h): draws 2s, 2s+1 of this pixel's frame
             const uint32_t y = dev::global_row(lr, a.row0, a.band_h, a.band_step);
-            const float fu = ((float)x + ru) / (float)a.w, fv = ((float)y + rv) / (float)a.h;
-            // Camera::GetRay direction, Camera.cu:18-20
-            for (int k = 0; k < 3; ++k) r.d[k] = ((a.cam[3 + k] + fu * a.cam[6 + k]) + fv * a.cam[9 + k]) - a.cam[k];
+            dev::primary_dir(a.cam, a.rng_in, P, lp, a.d_base, s, x, y, a.w, a.h, r.d);
             if (dev::closest_start<false>(sc, r, a.cam, 0.0f)) {
                 while (!dev::closest_step<false>(sc, r, a.cam, 0.0f, stk)) {}
             }
@@ -139,7 +130,7 @@ __global__ void __launch_bounds__(kGT) k_gbuffer(const GArgs a) {
         uint32_t prim = kNoHit;
         if (hit) {
             (void)dev::mt_tuv(sc.tris + 9ull * r.bi, a.cam, r.d, t, u, vv);
-            prim = a.tri_idx[r.bi];
+            prim = a.tri_idx ? a.tri_idx[r.bi] : r.bi;
         }
         if (a.hits && valid)
             a.hits[lp * spp + s] = make_uint4(__float_as_uint(t), __float_as_uint(u), __float_as_uint(vv), prim);
@@ -175,17 +166,11 @@ __global__ void __launch_bounds__(kGT) k_gbuffer(const GArgs a) {
             if (a.prim) a.prim[lp] = prim;
             if (a.bary) { a.bary[2 * lp] = u; a.bary[2 * lp + 1] = vv; }
             if (a.normal) {
-                // n = cross(e1, e2) (glm order), normalised: each op one rounded f32 op
-                const float *tp = sc.tris + 9ull * r.bi;
-                const float e1x = tp[3], e1y = tp[4], e1z = tp[5];
-                const float e2x = tp[6], e2y = tp[7], e2z = tp[8];
-                const float nx = e1y * e2z - e2y * e1z;
-                const float ny = e1z * e2x - e2z * e1x;
-                const float nz = e1x * e2y - e2x * e1y;
-                const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
-                a.normal[3 * lp] = nx / len;
-                a.normal[3 * lp + 1] = ny / len;
-                a.normal[3 * lp + 2] = nz / len;
+                float n[3];
+                dev::tri_normal(sc.tris + 9ull * r.bi, n);
+                a.normal[3 * lp] = n[0];
+                a.normal[3 * lp + 1] = n[1];
+                a.normal[3 * lp + 2] = n[2];
             }
             if (a.coverage) a.coverage[lp] = cov;
         }
@@ -210,7 +195,7 @@ uint64_t gbuffer_tiles(uint32_t w, uint32_t nrows, uint32_t spp, uint32_t *tiles
 
 int launch_gbuffer(const DeviceTree &t, const RenderArgs &ra, const GBufferPlanes &p,
                    const unsigned long long *hit_mask, uint32_t lds_slots, uint32_t *cursor, uint32_t *spill,
-                   uint32_t max_blocks, void *stream) {
+                   uint32_t max_blocks, void *stream, bool sorted_prim) {
     const hipStream_t st = (hipStream_t)stream;
     if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0 || ra.spp > 64) return 0;
     const bool pow2 = (ra.spp & (ra.spp - 1)) == 0;
@@ -233,7 +218,7 @@ int launch_gbuffer(const DeviceTree &t, const RenderArgs &ra, const GBufferPlane
     a.nodes = t.nodes;
     a.tris = t.tris_s;
     a.dup = t.dup_cnt;
-    a.tri_idx = t.vals;
+    a.tri_idx = sorted_prim ? nullptr : t.vals;
     a.rng_in = ra.rng_in;
     a.hit_mask = pow2 ? hit_mask : nullptr;
     a.hits = reinterpret_cast<uint4 *>(p.hits);

@@ -344,6 +344,8 @@ int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, bool occlu
 // power of two): per tile the samples that can hit (RenderArgs::hit_mask); the
 // others get the miss record unwalked.  cursor, spill, max_blocks, lds_slots:
 // as launch_trace (the kernel borrows the trace's cursor and spill area).
+// sorted_prim: the records' prim is the triangle's sorted position, not its
+// file-order index (bih_direct.hip's scratch records).
 struct GBufferPlanes {
     void *hits = nullptr;
     float *depth = nullptr;
@@ -355,7 +357,25 @@ struct GBufferPlanes {
 uint64_t gbuffer_tiles(uint32_t w, uint32_t nrows, uint32_t spp, uint32_t *tiles_x);
 int launch_gbuffer(const DeviceTree &t, const RenderArgs &a, const GBufferPlanes &p,
                    const unsigned long long *hit_mask, uint32_t lds_slots, uint32_t *cursor, uint32_t *spill,
-                   uint32_t max_blocks, void *stream);
+                   uint32_t max_blocks, void *stream, bool sorted_prim = false);
+// Direct lighting (bih_direct.hip), behind a launch_gbuffer of the same frame
+// `a` on the same stream that left its hit records, sorted_prim, in rec
+// (bih_hit[P*spp]): per sample the lights (n_lights of {dir[3], weight}, host
+// memory, copied into the kernel arguments) that face its hit triangle and
+// reach its hit point, to p.lit (u64[P*spp], never null), and the pixel sums
+// resolved from them (a null plane is not written).  list (u32[P*spp]), face
+// (u64[P*spp]): the hit samples with a facing light.  count (one u32) and
+// cursor (one u64) are zeroed by the launch; spill, max_blocks, lds_slots: as
+// launch_trace.
+constexpr uint32_t kMaxLights = 64;   // BIH_MAX_LIGHTS: one bit each of a sample's lit word
+struct DirectPlanes {
+    unsigned long long *lit = nullptr;
+    float *irradiance = nullptr;
+    uint32_t *rgba = nullptr;
+};
+int launch_direct(const DeviceTree &t, const RenderArgs &a, const DirectPlanes &p, const float *lights,
+                  uint32_t n_lights, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
+                  uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream);
 int launch_rng_init(uint32_t *rng, uint32_t w, uint32_t row0, uint32_t nrows, uint32_t band_h,
                     uint32_t band_step, uint64_t seed, uint64_t skip, int device, void *stream);
 // dst = src's per-pixel state advanced by `steps` draws (planes of `pixels`; dst may be src)

@@ -37,7 +37,8 @@ extern "C" {
 #define BIH_ABI_VERSION 4   /* 2: bih_tree_info.device_allocs, bih_reserve, bih_tree_set_param;
                                3: bih_whitted_work, BIH_PARAM_WHITTED_COUNTERS;
                                4: bih_host_register / bih_host_unregister, bih_render_history;
-                               (4, added since: bih_trace*, bih_render_gbuffer*, BIH_PARAM_GBUFFER_MASK) */
+                               (4, added since: bih_trace*, bih_render_gbuffer*, BIH_PARAM_GBUFFER_MASK,
+                                bih_render_direct*) */
 
 /* error codes */
 #define BIH_OK               0
@@ -395,6 +396,77 @@ int bih_render_gbuffer_device(const bih_tree *tree, const bih_camera *camera, ui
 int bih_render_gbuffer(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
                        uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
                        const bih_gbuffer *host_planes);                     /* synchronous, host memory */
+
+/* Direct-lighting render: which of up to BIH_MAX_LIGHTS directional lights
+ * reach each primary sample's hit point (hard shadows, sky visibility), and
+ * the pixel's irradiance and grey shade summed from them -- the G-buffer's
+ * closest hit, then shadow rays, in one call.
+ *
+ * Any plane may be NULL (not written); all NULL -> BIH_ERR_INVALID.
+ * P = rows->nrows * w local pixels, local pixel p = local_row * w + x. */
+#define BIH_MAX_LIGHTS   64
+#define BIH_SHADOW_T_LO  1e-4f            /* Whitted's bounce epsilon */
+/* A directional light: dir points from the surface TOWARDS the light (the
+ * shadow ray's direction); it is used as given, not normalised. */
+typedef struct bih_light { float dir[3]; float weight; } bih_light;   /* 16 B */
+typedef struct bih_direct {
+    uint64_t *lit;         /* u64[P*spp], sample p*spp + s: bit k = light k reaches it; 8-byte aligned */
+    float    *irradiance;  /* f32[P] */
+    uint32_t *rgba;        /* u32[P] 0x00BBGGRR */
+} bih_direct;
+
+/* Semantics: the G-buffer's closest hit, then bih_trace's BIH_QUERY_OCCLUDED
+ * on rays stated here bit for bit, then sums in a stated order; no new rule.
+ * Every f32 operation below is one separately rounded IEEE operation.
+ *  - Sample (x, y, s) of frame f has bih_render_gbuffer's ray (o = origin, d)
+ *    and its bih_hit {t, u, v, prim}.  A missed sample has lit = 0.
+ *  - Hit point: P[a] = o[a] + t*d[a] (one multiply, then one add).
+ *  - Normal: n = the G-buffer's `normal` formula on the sample's own triangle
+ *    `prim` (cross(e1, e2) in glm order, divided by its length).
+ *  - Facing test of light k, L = lights[k].dir as given:
+ *    c_k = (n.x*L.x + n.y*L.y) + n.z*L.z; the light is facing exactly when
+ *    c_k > 0.0f.  L is not normalised by the library (normalise it to make c_k
+ *    a cosine); a zero or NaN direction never lights a sample.
+ *  - Bit k of lit is 1 exactly when light k is facing and
+ *    bih_trace(.., BIH_QUERY_OCCLUDED) of the ray {o = P, t_lo =
+ *    BIH_SHADOW_T_LO, d = L} returns 0.  Bits n_lights and above are 0.
+ *    Triangles are one-sided, as everywhere in this library: a triangle blocks
+ *    a shadow ray only when its front faces the ray (det > 1e-6).  The
+ *    In exact arithmetic the originating triangle has det = e1.cross(L, e2)
+ *    = -(L.cross(e1, e2)) < 0 for a facing light, so it cannot block its own
+ *    ray, whatever t_lo.  In f32 c_k comes from the normalised normal and det
+ *    from the edges and L as given, so for a light almost in the triangle's
+ *    plane, or a huge L, the two signs can disagree; the result is then
+ *    whatever bih_trace answers for the ray above, by definition.
+ *  - Per sample e_s = 0, then for k ascending over the lit bits
+ *    e_s = e_s + lights[k].weight * c_k.  Per pixel
+ *    E = (((e_0 + e_1) + ..) + e_{spp-1}) / (float)spp; a miss contributes 0.
+ *    irradiance = E.  rgba: g = (int)fmaxf(0, fminf(255, 255.0f*E)) (a NaN E
+ *    gives 255), pixel = g | g<<8 | g<<16; a pixel none of whose samples hit
+ *    gets 0x00281414, bih_render_whitted's miss shade (20, 20, 40).
+ * lights is HOST memory in both entries, copied by the call (it may be freed
+ * or changed as soon as the call returns).
+ * Errors, checked in this order before a device is touched: the checks of
+ * bih_render_gbuffer_device, "all planes NULL" being about the three planes
+ * here; lights == NULL, n_lights == 0 or n_lights > BIH_MAX_LIGHTS ->
+ * BIH_ERR_INVALID; lit not 8-byte aligned -> BIH_ERR_INVALID; nrows == 0 ->
+ * BIH_OK, nothing launched.
+ * RNG, ordering, memory: exactly the G-buffer call's.  The call counts as the
+ * render of frame f; it runs after the last bih_build / bih_rebuild and a
+ * rebuild waits for it; it borrows the ray queries' cursor and spill area, so
+ * it orders with G-buffer calls and traces of the tree.  Its scratch is the
+ * tree's, sized by the call's shape and counted in bih_tree_info: 28 bytes
+ * per sample of the rows (a hit record, a facing mask, a list entry), and 8
+ * more (the lit word) once a call passes no `lit`.  After the first call of a
+ * shape, light count and choice of planes further calls allocate nothing. */
+int bih_render_direct_device(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                             uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                             const bih_light *lights, uint32_t n_lights,
+                             const bih_direct *d_planes, void *stream);     /* async; bih_sync waits */
+int bih_render_direct(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                      uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                      const bih_light *lights, uint32_t n_lights,
+                      const bih_direct *host_planes);                       /* synchronous, host memory */
 
 /* The drop-in host loop (bih_render into a caller's framebuffer) ends in a
  * device-to-host copy of w*h*4 bytes.  Into pageable memory the runtime
