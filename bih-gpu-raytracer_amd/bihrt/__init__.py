@@ -21,7 +21,8 @@ import numpy as np
 from . import scenes  # noqa: F401
 from ._lib import (PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_STATIC_SOUP,
                    PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS, PARAM_GBUFFER_MASK,
-                   NO_HIT, LIGHT_DTYPE, MAX_LIGHTS, SHADOW_T_LO, QUERY_CLOSEST, QUERY_OCCLUDED, Direct, GBuffer, Hit, Light, Ray, TRAVERSE_ANYHIT,
+                   NO_HIT, LIGHT_DTYPE, POINT_LIGHT_DTYPE, MAX_LIGHTS, SHADOW_T_LO, QUERY_CLOSEST, QUERY_OCCLUDED,
+                   QUERY_T_HI, QUERY_CLOSEST_WITHIN, QUERY_OCCLUDED_WITHIN, PointLight, Direct, GBuffer, Hit, Light, Ray, TRAVERSE_ANYHIT,
                    TRAVERSE_REFERENCE, BihError, Camera, Framebuffer, Rows, Scene, TreeInfo, check, load)
 from . import _lib
 
@@ -46,8 +47,10 @@ def camera_ray_bound(cam: Camera) -> np.ndarray:
     return np.array(out[:], np.float32)
 
 
-# numpy views of bih_ray / bih_hit arrays
-RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_lo", np.float32), ("d", np.float32, 3), ("reserved", np.float32)])
+# numpy views of bih_ray / bih_hit arrays (`reserved` and `t_hi`: two names of the last float)
+RAY_DTYPE = np.dtype({"names": ["o", "t_lo", "d", "reserved", "t_hi"],
+                      "formats": [(np.float32, 3), np.float32, (np.float32, 3), np.float32, np.float32],
+                      "offsets": [0, 12, 16, 28, 28], "itemsize": 32})
 HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("prim", np.uint32)])
 
 
@@ -70,8 +73,19 @@ def pack_lights(lights) -> np.ndarray:
     return np.ascontiguousarray(a).reshape(-1)
 
 
-def pack_rays(orig, dirs, t_lo=0.0) -> np.ndarray:
-    """(n,) RAY_DTYPE array (bih_ray records) of origins, directions and t_lo."""
+def pack_point_lights(lights) -> np.ndarray:
+    """(k,) POINT_LIGHT_DTYPE array (bih_point_light records) of such an array or
+    of (k, 4) rows {pos.x, pos.y, pos.z, weight}."""
+    a = np.asarray(lights)
+    if a.dtype != POINT_LIGHT_DTYPE:
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 4).view(POINT_LIGHT_DTYPE).reshape(-1)
+    return np.ascontiguousarray(a).reshape(-1)
+
+
+def pack_rays(orig, dirs, t_lo=0.0, t_hi=None) -> np.ndarray:
+    """(n,) RAY_DTYPE array (bih_ray records) of origins, directions and t_lo;
+    t_hi (a scalar or (n,), for the segment queries) goes into the last float,
+    which stays 0 when it is not given."""
     orig = np.asarray(orig, np.float32).reshape(-1, 3)
     dirs = np.asarray(dirs, np.float32).reshape(-1, 3)
     if orig.shape != dirs.shape:
@@ -79,6 +93,8 @@ def pack_rays(orig, dirs, t_lo=0.0) -> np.ndarray:
     rays = np.zeros(orig.shape[0], RAY_DTYPE)
     rays["o"], rays["d"] = orig, dirs
     rays["t_lo"] = np.broadcast_to(np.asarray(t_lo, np.float32), (orig.shape[0],))
+    if t_hi is not None:
+        rays["t_hi"] = np.broadcast_to(np.asarray(t_hi, np.float32), (orig.shape[0],))
     return rays
 
 
@@ -138,17 +154,20 @@ class GPUArrayManager:
         check(load().bih_tree_export(self._tree, which, out.ctypes.data, C.byref(n)), "bih_tree_export")
         return out
 
-    def trace(self, orig, dirs, t_lo=0.0, query: int = QUERY_CLOSEST):
+    def trace(self, orig, dirs, t_lo=0.0, query: int = QUERY_CLOSEST, t_hi=None):
         """Ray queries for host rays (bih_trace; synchronous).  orig, dirs: (n, 3)
         float32; t_lo: a scalar or (n,).  QUERY_CLOSEST returns a dict of `t`, `u`,
         `v` (float32) and `prim` (uint32 file-order triangle, NO_HIT on a miss);
-        QUERY_OCCLUDED a uint8 array (1: some triangle is hit)."""
-        rays = pack_rays(orig, dirs, t_lo)
+        QUERY_OCCLUDED a uint8 array (1: some triangle is hit).  The segment
+        queries QUERY_CLOSEST_WITHIN / QUERY_OCCLUDED_WITHIN answer the same for
+        hits with t < t_hi (a scalar or (n,)) only."""
+        rays = pack_rays(orig, dirs, t_lo, t_hi)
         n = rays.shape[0]
-        out = np.zeros(n, HIT_DTYPE if query == QUERY_CLOSEST else np.uint8)
+        closest = (query & ~QUERY_T_HI) == QUERY_CLOSEST
+        out = np.zeros(n, HIT_DTYPE if closest else np.uint8)
         check(load().bih_trace(self._tree, C.c_void_p(rays.ctypes.data), n, query,
                                C.c_void_p(out.ctypes.data)), "bih_trace")
-        if query != QUERY_CLOSEST:
+        if not closest:
             return out
         return {k: np.ascontiguousarray(out[k]) for k in ("t", "u", "v", "prim")}
 
@@ -344,6 +363,50 @@ class Renderer:
                                               C.c_void_p(lt.ctypes.data), lt.shape[0], C.byref(dp),
                                               C.c_void_p(stream or 0)), "bih_render_direct_device")
 
+    def _lights_args(self, dir_lights, point_lights):
+        dl = pack_lights(dir_lights if dir_lights is not None else np.zeros((0, 4), np.float32))
+        pl = pack_point_lights(point_lights if point_lights is not None else np.zeros((0, 4), np.float32))
+        return (dl, pl, C.c_void_p(dl.ctypes.data if dl.shape[0] else 0), dl.shape[0],
+                C.c_void_p(pl.ctypes.data if pl.shape[0] else 0), pl.shape[0])
+
+    def render_lights(self, dir_lights, point_lights, frame: int | None = None, rows: Rows | None = None,
+                      planes=("lit", "irradiance", "rgba")) -> dict:
+        """render_direct with point lights next to the directional ones
+        (bih_render_lights; synchronous).  dir_lights as render_direct's lights,
+        point_lights a POINT_LIGHT_DTYPE array or (k, 4) rows {pos, weight}
+        (scenes.lamps makes some); either may be None or empty, together 1 ..
+        MAX_LIGHTS.  Bit k of "lit" is directional light k, bit len(dir_lights)
+        + j point light j, which a triangle behind it does not shadow."""
+        f = self.frame if frame is None else frame
+        nrows = rows.nrows if rows is not None else self.h
+        dl, pl, dptr, nd, pptr, npt = self._lights_args(dir_lights, point_lights)
+        out, dp = {}, Direct()
+        for name in planes:
+            dt, k = DIRECT_PLANES[name]
+            out[name] = np.zeros((nrows, self.w) if k else nrows * self.w * self.spp, dt)
+            setattr(dp, name, out[name].ctypes.data)
+        check(load().bih_render_lights(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
+                                       self.seed, C.byref(rows) if rows is not None else None,
+                                       dptr, nd, pptr, npt, C.byref(dp)), "bih_render_lights")
+        self.frame = f + 1
+        return out
+
+    def render_lights_device(self, ptrs: dict, dir_lights, point_lights, frame: int, rows: Rows | None = None,
+                             stream: int | None = None):
+        """Asynchronous render_lights into device memory (bih_render_lights_device);
+        ptrs as render_direct_device's.  Both light arrays are host memory, copied
+        by the call."""
+        dp = Direct()
+        for name, ptr in ptrs.items():
+            if name not in DIRECT_PLANES:
+                raise KeyError(name)
+            setattr(dp, name, ptr or None)
+        dl, pl, dptr, nd, pptr, npt = self._lights_args(dir_lights, point_lights)
+        check(load().bih_render_lights_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
+                                              frame, self.seed, C.byref(rows) if rows is not None else None,
+                                              dptr, nd, pptr, npt, C.byref(dp), C.c_void_p(stream or 0)),
+              "bih_render_lights_device")
+
     def whitted_work(self) -> dict:
         """Per bounce d = 0..8 of the last Whitted render (run with
         PARAM_WHITTED_COUNTERS on): rays traced, BIH nodes entered, triangles
@@ -440,4 +503,6 @@ __all__ = ["GPUArrayManager", "Renderer", "Model", "load_obj", "host_register", 
            "TRAVERSE_REFERENCE", "PARAM_ITEM_TILES", "PARAM_PAIR_CAP", "PARAM_BINS_CAP", "PARAM_FORCE_FALLBACK",
            "PARAM_WHITTED_COUNTERS", "PARAM_STATIC_SOUP", "PARAM_TEST_ALLOC_FAIL", "PARAM_TRACE_LDS_SLOTS",
            "PARAM_GBUFFER_MASK", "GBuffer", "GBUFFER_PLANES", "QUERY_CLOSEST", "QUERY_OCCLUDED", "NO_HIT", "Ray", "Hit", "RAY_DTYPE", "HIT_DTYPE", "pack_rays",
-           "Light", "Direct", "LIGHT_DTYPE", "DIRECT_PLANES", "MAX_LIGHTS", "SHADOW_T_LO", "pack_lights"]
+           "Light", "Direct", "LIGHT_DTYPE", "DIRECT_PLANES", "MAX_LIGHTS", "SHADOW_T_LO", "pack_lights",
+           "QUERY_T_HI", "QUERY_CLOSEST_WITHIN", "QUERY_OCCLUDED_WITHIN", "PointLight", "POINT_LIGHT_DTYPE",
+           "pack_point_lights"]

@@ -30,10 +30,13 @@ PARAM_TEST_ALLOC_FAIL = 7   # tests: the next allocating build fails at its k-th
 PARAM_TRACE_LDS_SLOTS = 8   # tests: 2 = ray queries keep only 2 stack slots per lane on chip
 PARAM_GBUFFER_MASK = 9      # tests / A-B: 0 = G-buffer renders walk every sample (no bins hit mask)
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1   # bih_trace / bih_trace_device
+QUERY_T_HI = 0x10                      # flag: the ray ends at its t_hi (segment queries)
+QUERY_CLOSEST_WITHIN, QUERY_OCCLUDED_WITHIN = QUERY_CLOSEST | QUERY_T_HI, QUERY_OCCLUDED | QUERY_T_HI
 NO_HIT = 0xFFFFFFFF
 MAX_RAYS = 1 << 30
 MAX_LIGHTS = 64           # bih_render_direct*: one bit each of a sample's lit word
 LIGHT_DTYPE = np.dtype([("dir", np.float32, 3), ("weight", np.float32)])   # numpy view of a bih_light array
+POINT_LIGHT_DTYPE = np.dtype([("pos", np.float32, 3), ("weight", np.float32)])   # ... of a bih_point_light array
 SHADOW_T_LO = 1e-4        # BIH_SHADOW_T_LO
 (ARR_MORTON_SORTED, ARR_TRI_INDEX, ARR_UNIQUE_MC, ARR_DUP_COUNT, ARR_FIRST_IDX, ARR_LEAF_PARENT,
  ARR_CLIP, ARR_AXIS, ARR_CHILDREN, ARR_IS_LEAF, ARR_PARENT, ARR_TRI_LO, ARR_TRI_HI) = range(13)
@@ -78,9 +81,14 @@ class Rows(C.Structure):
                 ("band_step", C.c_uint32)]
 
 
+class _RayEnd(C.Union):
+    _fields_ = [("reserved", C.c_float), ("t_hi", C.c_float)]
+
+
 class Ray(C.Structure):
-    """bih_ray (32 bytes)."""
-    _fields_ = [("o", C.c_float * 3), ("t_lo", C.c_float), ("d", C.c_float * 3), ("reserved", C.c_float)]
+    """bih_ray (32 bytes); the last float is `reserved` or `t_hi` (one member)."""
+    _anonymous_ = ("_end",)
+    _fields_ = [("o", C.c_float * 3), ("t_lo", C.c_float), ("d", C.c_float * 3), ("_end", _RayEnd)]
 
 
 class Hit(C.Structure):
@@ -97,6 +105,11 @@ class GBuffer(C.Structure):
 class Light(C.Structure):
     """bih_light (16 bytes): a directional light, dir towards the light."""
     _fields_ = [("dir", C.c_float * 3), ("weight", C.c_float)]
+
+
+class PointLight(C.Structure):
+    """bih_point_light (16 bytes): a lamp at pos."""
+    _fields_ = [("pos", C.c_float * 3), ("weight", C.c_float)]
 
 
 class Direct(C.Structure):
@@ -189,13 +202,18 @@ def load():
                                            vp, u32, C.POINTER(Direct), vp]
     L.bih_render_direct.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
                                     vp, u32, C.POINTER(Direct)]
+    L.bih_render_lights_device.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                           vp, u32, vp, u32, C.POINTER(Direct), vp]
+    L.bih_render_lights.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                    vp, u32, vp, u32, C.POINTER(Direct)]
     for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
                  "bih_render_whitted_device", "bih_render_whitted", "bih_render_device_frames",
                  "bih_bins_get_stats", "bih_reserve", "bih_tree_set_param", "bih_whitted_work",
                  "bih_host_register", "bih_host_unregister", "bih_render_history", "bih_trace_device", "bih_trace",
-                 "bih_render_gbuffer_device", "bih_render_gbuffer", "bih_render_direct_device", "bih_render_direct"):
+                 "bih_render_gbuffer_device", "bih_render_gbuffer", "bih_render_direct_device", "bih_render_direct",
+                 "bih_render_lights_device", "bih_render_lights"):
         getattr(L, name).restype = i32
     _lib = L
     return L

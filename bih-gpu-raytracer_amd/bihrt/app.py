@@ -16,6 +16,7 @@ usage:  python -m bihrt --mesh sponza --resources path/to/resources --frames 10 
             --out frames/f%04d.ppm [--width 640 --height 480 --no-rebuild]
             [--gbuffer frames/g%04d.npz]   (depth, prim, bary, normal, coverage per written frame)
             [--direct frames/d%04d.ppm [--sun X,Y,Z] [--sky K]]   (sky- and sun-lit grey preview per written frame)
+                     [--lamp X,Y,Z[,W]]...            (point lights next to them; --sky 0: lamps only)
         python -m bihrt --obj file.obj ...     (explicit path)
         python -m bihrt --scene cornell|torus|soup[:N] ...   (built-in scenes)
 """
@@ -73,13 +74,14 @@ class App:
 
     def run(self, frames: int, out_pattern: str | None = None, rebuild: bool = True,
             every: int = 1, gbuffer_pattern: str | None = None, direct_pattern: str | None = None,
-            lights=None):
+            lights=None, lamps=None):
         """App::Run for a fixed number of frames: Renderer::Render each frame
         (BIH rebuild + render), optional PPM output; returns the frames.
         gbuffer_pattern: one .npz of the frame's G-buffer planes
         (Renderer.render_gbuffer) per written frame.  direct_pattern: one PPM
         of the frame's direct lighting under `lights` (Renderer.render_direct's
-        rgba plane) per written frame; lights = None: scenes.sky_dome(8)."""
+        rgba plane) per written frame; lights = None: scenes.sky_dome(8).
+        lamps: point lights {pos, weight} next to them (Renderer.render_lights)."""
         assert self.renderer is not None, "load_models first"
         if direct_pattern and lights is None:
             lights = scenes.sky_dome(8)
@@ -110,7 +112,11 @@ class App:
                 d = os.path.dirname(path)
                 if d:
                     os.makedirs(d, exist_ok=True)
-                write_ppm(path, self.renderer.render_direct(lights, f, planes=("rgba",))["rgba"])
+                if lamps is not None and len(lamps):
+                    shade = self.renderer.render_lights(lights, lamps, f, planes=("rgba",))["rgba"]
+                else:
+                    shade = self.renderer.render_direct(lights, f, planes=("rgba",))["rgba"]
+                write_ppm(path, shade)
             imgs.append(img)
         return imgs
 
@@ -134,6 +140,8 @@ def main(argv=None) -> int:
                     help="PPM path of the direct-lighting preview of each written frame; '%%d' formats the frame number")
     ap.add_argument("--sun", default=None, metavar="X,Y,Z", help="--direct: direction towards the sun")
     ap.add_argument("--sky", type=int, default=None, metavar="K", help="--direct: sky directions (default 8; 0: none)")
+    ap.add_argument("--lamp", action="append", default=None, metavar="X,Y,Z[,W]",
+                    help="--direct: a point light at X,Y,Z of weight W (default 1); repeatable")
     ap.add_argument("--every", type=int, default=1, help="write every k-th frame")
     ap.add_argument("--no-rebuild", action="store_true",
                     help="build once (the reference rebuilds every frame)")
@@ -150,21 +158,40 @@ def main(argv=None) -> int:
     else:
         scene = builtin_scene(a.scene)
     lights = None
+    lamps = None
     if not a.direct and (a.sun is not None or a.sky is not None):
         ap.error("--sun and --sky belong to --direct")
+    if not a.direct and a.lamp:
+        ap.error("--lamp belongs to --direct")
     if a.direct:
         a.sky = 8 if a.sky is None else a.sky
         sun = [float(x) for x in a.sun.split(",")] if a.sun else None
         if sun is not None and len(sun) != 3:
             ap.error("--sun takes X,Y,Z")
-        if a.sky < 0 or a.sky + (sun is not None) > 64 or a.sky + (sun is not None) == 0:
-            ap.error("--direct needs 1..64 lights (--sky K, --sun)")
+        if a.lamp:
+            rows = []
+            for spec in a.lamp:
+                try:
+                    v = [float(x) for x in spec.split(",")]
+                except ValueError:
+                    v = []
+                if len(v) not in (3, 4):
+                    ap.error("--lamp takes X,Y,Z[,W]")
+                rows.append(v + [1.0] if len(v) == 3 else v)
+            lamps = np.array(rows, np.float32)
+        n_lamps = 0 if lamps is None else lamps.shape[0]
+        n_dir = a.sky + (sun is not None)
+        if a.sky < 0 or n_dir + n_lamps > 64 or n_dir + n_lamps == 0:
+            ap.error("--direct needs 1..64 lights (--sky K, --sun, --lamp)" if n_lamps else
+                     "--direct needs 1..64 lights (--sky K, --sun)")
         if a.sky:
             lights = scenes.sky_dome(a.sky, sun)
-        else:
+        elif sun is not None:
             lights = scenes.sky_dome(1, sun)[:1]
+        else:
+            lights = np.zeros(0, scenes.LIGHT_DTYPE)   # lamps only
     app = App(a.width, a.height, a.spp, device=a.device)
     app.load_models(scene)
     app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every, gbuffer_pattern=a.gbuffer,
-            direct_pattern=a.direct, lights=lights)
+            direct_pattern=a.direct, lights=lights, lamps=lamps)
     return 0

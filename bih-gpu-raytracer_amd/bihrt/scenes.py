@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import LIGHT_DTYPE
+from ._lib import LIGHT_DTYPE, POINT_LIGHT_DTYPE
 
 _GOLD = np.uint64(0x9E3779B97F4A7C15)
 
@@ -236,3 +236,25 @@ def sky_dome(k: int, sun=None) -> np.ndarray:
             raise ValueError("sun direction must be non-zero")
         out = np.concatenate([[[*(s / n), 1.0]], out])
     return np.ascontiguousarray(out, np.float32).view(LIGHT_DTYPE).reshape(-1)
+
+
+def lamps(lo, hi, k: int, scale: float = 0.6, weight=None) -> np.ndarray:
+    """Point lights for Renderer.render_lights: k lamps on an ellipsoid inside
+    (scale < 1) or around the box [lo, hi] -- centre + scale * half_extent * u_i,
+    u_i = k Fibonacci points over the whole unit sphere -- as (k,) float32
+    records {pos[3], weight} (bihrt.POINT_LIGHT_DTYPE); computed in f64.
+    weight: of each lamp; default |half_extent|^2 / k, which makes a surface
+    that faces the lamps from about a half-diagonal away sum to the order of 1."""
+    if k < 1:
+        raise ValueError("lamps needs at least one lamp")
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    centre, half = (lo + hi) / 2.0, (hi - lo) / 2.0
+    i = np.arange(k, dtype=np.float64) + 0.5
+    z = 1.0 - 2.0 * i / k
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    r = np.sqrt(1.0 - z * z)
+    u = np.stack([r * np.cos(phi), z, r * np.sin(phi)], 1)
+    out = np.zeros((k, 4), np.float64)
+    out[:, :3] = centre + scale * half * u
+    out[:, 3] = float(half @ half) / k if weight is None else float(weight)
+    return np.ascontiguousarray(out, np.float32).view(POINT_LIGHT_DTYPE).reshape(-1)

@@ -2165,7 +2165,8 @@ static int trace_locked(bih_tree *tr, const void *d_rays, uint32_t n, uint32_t q
     // the cursor and the spill area are shared: after the trace before this one
     rc = wait_traces(tr, st);
     if (rc) return rc;
-    rc = map_hip(bih::launch_trace(tr->t, d_rays, n, query == BIH_QUERY_OCCLUDED, d_out, tr->prm.trace_lds,
+    static_assert(BIH_QUERY_T_HI == bih::kQueryTHi, "BIH_QUERY_T_HI / kQueryTHi");
+    rc = map_hip(bih::launch_trace(tr->t, d_rays, n, query, d_out, tr->prm.trace_lds,
                                    tr->tq_cursor, tr->tq_spill, tr->tq_blocks, st));
     // (a failed launch may have left work on st that uses the cursor: the event covers it)
     const hipError_t e = hipEventRecord(tr->ev_trace, st);
@@ -2174,11 +2175,15 @@ static int trace_locked(bih_tree *tr, const void *d_rays, uint32_t n, uint32_t q
     return map_hip((int)e);
 }
 
+// A (checked) query whose results are bih_hit records: CLOSEST, CLOSEST_WITHIN.
+static bool query_closest(uint32_t query) { return (query & ~BIH_QUERY_T_HI) == BIH_QUERY_CLOSEST; }
+
 // Argument checks of both entries, in the header's order; none touches the
 // tree or a device.
 static int trace_check(const bih_tree *tr, const void *rays, uint64_t n_rays, uint32_t query, const void *out) {
     if (!tr) return BIH_ERR_INVALID;
-    if (query != BIH_QUERY_CLOSEST && query != BIH_QUERY_OCCLUDED) return BIH_ERR_INVALID;
+    if ((query & ~BIH_QUERY_T_HI) != BIH_QUERY_CLOSEST && (query & ~BIH_QUERY_T_HI) != BIH_QUERY_OCCLUDED)
+        return BIH_ERR_INVALID;
     if (n_rays > BIH_MAX_RAYS) return BIH_ERR_TOO_LARGE;
     if (n_rays > 0 && (!rays || !out)) return BIH_ERR_INVALID;
     return BIH_OK;
@@ -2189,7 +2194,7 @@ int bih_trace_device(const bih_tree *ctr, const bih_ray *d_rays, uint64_t n_rays
     const int rc = trace_check(ctr, d_rays, n_rays, query, d_out);
     if (rc || n_rays == 0) return rc;
     // the kernel moves rays and hits as 16-byte words
-    if (((uintptr_t)d_rays & 15u) || (query == BIH_QUERY_CLOSEST && ((uintptr_t)d_out & 15u))) return BIH_ERR_INVALID;
+    if (((uintptr_t)d_rays & 15u) || (query_closest(query) && ((uintptr_t)d_out & 15u))) return BIH_ERR_INVALID;
     bih_tree *tr = const_cast<bih_tree *>(ctr);
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
@@ -2203,7 +2208,7 @@ int bih_trace(const bih_tree *ctr, const bih_ray *rays, uint64_t n_rays, uint32_
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
     const size_t in_bytes = (size_t)n_rays * sizeof(bih_ray);
-    const size_t out_bytes = (size_t)n_rays * (query == BIH_QUERY_CLOSEST ? sizeof(bih_hit) : 1);
+    const size_t out_bytes = (size_t)n_rays * (query_closest(query) ? sizeof(bih_hit) : 1);
     if (tr->tq_stage_cap < in_bytes + out_bytes) {
         // (its only users are calls of this function, which wait for their work)
         if (tr->tq_stage) (void)hipFree(tr->tq_stage);
@@ -2250,8 +2255,8 @@ static int gbuffer_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, 
 // What a direct-lighting call adds to its G-buffer launch: the lights (host
 // memory) and the caller's planes.  The launch's hits go to dr_mem.
 struct DirectJob {
-    const bih_light *lights;
-    uint32_t n_lights;
+    const float *lights;    // n_lights x 4 floats: n_dir bih_light, then bih_point_light
+    uint32_t n_lights, n_dir;
     bih_direct planes;
 };
 
@@ -2366,7 +2371,7 @@ static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
         dp.lit = dj->planes.lit ? reinterpret_cast<unsigned long long *>(dj->planes.lit) : tr->dr_lit;
         dp.irradiance = dj->planes.irradiance;
         dp.rgba = dj->planes.rgba;
-        rc = bih::launch_direct(tr->t, a, dp, &dj->lights[0].dir[0], dj->n_lights, rec,
+        rc = bih::launch_direct(tr->t, a, dp, dj->lights, dj->n_lights, dj->n_dir, rec,
                                 reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
                                 tr->prm.trace_lds, tr->tq_cursor + 4,
                                 reinterpret_cast<unsigned long long *>(tr->tq_cursor + 2), tr->tq_spill,
@@ -2473,8 +2478,9 @@ static int direct_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, u
 }
 
 // bih_render_direct_device under the tree's lock, arguments checked, nrows > 0.
+// lights: n_lights x 4 floats, the first n_dir directional, the rest point lights.
 static int direct_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t frame,
-                         uint64_t seed, const bih_rows &rows, const bih_light *lights, uint32_t n_lights,
+                         uint64_t seed, const bih_rows &rows, const float *lights, uint32_t n_lights, uint32_t n_dir,
                          const bih_direct &pl, void *stream) {
     const size_t S = (size_t)rows.nrows * w * spp;
     const bool own_lit = !pl.lit && tr->dr_lit_cap < S;
@@ -2500,9 +2506,10 @@ static int direct_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32
         tr->dr_cap = S;
     }
     static_assert(sizeof(bih_light) == 16 && BIH_MAX_LIGHTS == bih::kMaxLights, "bih_light / kMaxLights");
+    static_assert(sizeof(bih_point_light) == 16, "bih_point_light shares bih_light's slots");
     bih_gbuffer g = {};
     g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
-    const DirectJob dj{lights, n_lights, pl};
+    const DirectJob dj{lights, n_lights, n_dir, pl};
     return gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, g, stream, &dj);
 }
 
@@ -2515,18 +2522,16 @@ int bih_render_direct_device(const bih_tree *ctr, const bih_camera *cam, uint32_
     bih_tree *tr = const_cast<bih_tree *>(ctr);
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
-    return direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_lights, *d_planes, stream);
+    return direct_locked(tr, cam, w, h, spp, frame, seed, rows, &lights[0].dir[0], n_lights, n_lights, *d_planes,
+                         stream);
 }
 
-int bih_render_direct(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                      uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light *lights,
-                      uint32_t n_lights, const bih_direct *host_planes) {
-    bih_rows rows;
-    int rc = direct_check(ctr, cam, w, h, spp, rows_in, lights, n_lights, host_planes, &rows);
-    if (rc || rows.nrows == 0) return rc;
-    bih_tree *tr = const_cast<bih_tree *>(ctr);
-    DeviceGuard g(tr->t.device);
-    std::lock_guard<std::mutex> lk(tr->mu);
+// bih_render_direct / bih_render_lights under the tree's lock, arguments
+// checked, nrows > 0: direct_locked into device planes, copied to the host's.
+static int direct_host_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                              uint32_t frame, uint64_t seed, const bih_rows &rows, const float *lights,
+                              uint32_t n_lights, uint32_t n_dir, const bih_direct *host_planes) {
+    int rc;
     // device planes of the ones asked for, each at a multiple of 16 bytes
     const size_t P = (size_t)rows.nrows * w;
     void *const host[3] = {host_planes->lit, host_planes->irradiance, host_planes->rgba};
@@ -2550,7 +2555,7 @@ int bih_render_direct(const bih_tree *ctr, const bih_camera *cam, uint32_t w, ui
     d.lit = static_cast<uint64_t *>(dev_plane(0));
     d.irradiance = static_cast<float *>(dev_plane(1));
     d.rgba = static_cast<uint32_t *>(dev_plane(2));
-    rc = direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_lights, d, nullptr);
+    rc = direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_lights, n_dir, d, nullptr);
     hipError_t e = hipSuccess;
     for (int k = 0; k < 3 && rc == BIH_OK; ++k)
         if (host[k]) {
@@ -2559,6 +2564,76 @@ int bih_render_direct(const bih_tree *ctr, const bih_camera *cam, uint32_t w, ui
         }
     e = hipStreamSynchronize(tr->stream);
     return rc ? rc : map_hip((int)e);
+}
+
+int bih_render_direct(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                      uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light *lights,
+                      uint32_t n_lights, const bih_direct *host_planes) {
+    bih_rows rows;
+    const int rc = direct_check(ctr, cam, w, h, spp, rows_in, lights, n_lights, host_planes, &rows);
+    if (rc || rows.nrows == 0) return rc;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    return direct_host_locked(tr, cam, w, h, spp, frame, seed, rows, &lights[0].dir[0], n_lights, n_lights,
+                              host_planes);
+}
+
+// Argument checks of both bih_render_lights entries: direct_check's, its light
+// checks replaced (the header's order); none touches the tree or a device.
+static int lights_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                        const bih_rows *rows_in, const bih_light *dir_lights, uint32_t n_dir,
+                        const bih_point_light *point_lights, uint32_t n_point, const bih_direct *pl,
+                        bih_rows *rows) {
+    static float some_plane;
+    bih_gbuffer g = {};
+    if (pl && (pl->lit || pl->irradiance || pl->rgba)) g.depth = &some_plane;
+    const int rc = gbuffer_check(tr, cam, w, h, spp, rows_in, pl ? &g : nullptr, rows);
+    if (rc) return rc;
+    const uint64_t n = (uint64_t)n_dir + n_point;
+    if (n == 0 || n > BIH_MAX_LIGHTS) return BIH_ERR_INVALID;
+    if ((n_dir && !dir_lights) || (n_point && !point_lights)) return BIH_ERR_INVALID;
+    if ((uintptr_t)pl->lit & 7u) return BIH_ERR_INVALID;   // the lit words take 64-bit atomics
+    return BIH_OK;
+}
+
+// The call's lights in the kernels' slot order: directional, then point.
+static void merge_lights(const bih_light *dir_lights, uint32_t n_dir, const bih_point_light *point_lights,
+                         uint32_t n_point, float *out) {
+    if (n_dir) memcpy(out, dir_lights, (size_t)n_dir * sizeof(bih_light));
+    if (n_point) memcpy(out + 4 * (size_t)n_dir, point_lights, (size_t)n_point * sizeof(bih_point_light));
+}
+
+int bih_render_lights_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                             uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light *dir_lights,
+                             uint32_t n_dir, const bih_point_light *point_lights, uint32_t n_point,
+                             const bih_direct *d_planes, void *stream) {
+    bih_rows rows;
+    const int rc = lights_check(ctr, cam, w, h, spp, rows_in, dir_lights, n_dir, point_lights, n_point, d_planes,
+                                &rows);
+    if (rc || rows.nrows == 0) return rc;
+    float lights[4 * BIH_MAX_LIGHTS];
+    merge_lights(dir_lights, n_dir, point_lights, n_point, lights);
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    return direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_dir + n_point, n_dir, *d_planes, stream);
+}
+
+int bih_render_lights(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                      uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light *dir_lights,
+                      uint32_t n_dir, const bih_point_light *point_lights, uint32_t n_point,
+                      const bih_direct *host_planes) {
+    bih_rows rows;
+    const int rc = lights_check(ctr, cam, w, h, spp, rows_in, dir_lights, n_dir, point_lights, n_point,
+                                host_planes, &rows);
+    if (rc || rows.nrows == 0) return rc;
+    float lights[4 * BIH_MAX_LIGHTS];
+    merge_lights(dir_lights, n_dir, point_lights, n_point, lights);
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    return direct_host_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_dir + n_point, n_dir, host_planes);
 }
 
 int bih_sync(const bih_tree *tr, void *stream) {

@@ -11,6 +11,14 @@
 // ANY ends the same walk at the first accepted triangle: until then it has
 // the closest walk's visit order, interval clamp and accept test, so "some
 // triangle was accepted" is exactly (closest bi != kNoHit).
+// WITHIN (segment queries, a ray with a far end t_hi) is the closest walk too
+// -- the same accepts, the same bt / bi updates and interval clamp, also for
+// hits at or beyond t_hi -- ended at the first accepted triangle with
+// t < t_hi.  bt only decreases, so the closest walk's final t is below t_hi
+// exactly when some accepted t was: (bi != kNoHit && bt < t_hi) after this
+// walk is that of the whole closest walk, and the walk is a prefix of it.
+// t_hi bounds no interval and seeds no best hit (the walk culls with f32
+// plane distances: that would be another visit set).
 //
 // The ray's origin and t_lo are arguments, not walk state: a caller whose
 // origin is wave-uniform (the G-buffer: kernel arguments) keeps it in SGPRs,
@@ -25,6 +33,11 @@ namespace dev {
 
 constexpr uint32_t kNoHit = 0xFFFFFFFFu;
 constexpr uint32_t kLanes = 64;          // the walk's kernels run one-wave blocks
+
+// Where the walk ends (compile time; false / true of the two first read as before).
+constexpr int kWalkClosest = 0;          // when no node is left
+constexpr int kWalkAny = 1;              // at the first accepted triangle
+constexpr int kWalkWithin = 2;           // at the first accepted triangle with t < ClosestRay::t_hi
 
 __device__ __forceinline__ float pick3(uint32_t ax, float a, float b, float c) {
     return ax == 0 ? a : (ax == 1 ? b : c);
@@ -118,11 +131,17 @@ struct ClosestRay {
     float d[3], ix, iy, iz, tMin, tMax, bt;
     uint32_t sg, cur, sp, bi;
     uint4 nd;
+    float t_hi;                 // kWalkWithin only (set by the caller; the other modes never touch it)
 };
 
-// Leaf triangles [b, e): the (t, i) rule with t_lo < t < FLT_MAX.  ANY: ends
-// at the first accepted triangle (true).
-template <bool ANY>
+// kWalkWithin's answer once its walk has ended (one strict f32 compare: a NaN
+// t_hi gives false).
+__device__ __forceinline__ bool within_hit(const ClosestRay &r) { return r.bi != kNoHit && r.bt < r.t_hi; }
+
+// Leaf triangles [b, e): the (t, i) rule with t_lo < t < FLT_MAX.  kWalkAny:
+// ends at the first accepted triangle (true); kWalkWithin: at the first
+// accepted one below t_hi.
+template <int MODE>
 __device__ __forceinline__ bool closest_leaf(const ClosestScene &s, ClosestRay &r, const float *o, float t_lo,
                                              uint32_t b, uint32_t e) {
     for (uint32_t i = b; i < e; ++i) {
@@ -131,7 +150,8 @@ __device__ __forceinline__ bool closest_leaf(const ClosestScene &s, ClosestRay &
             (t < r.bt || (t == r.bt && i < r.bi))) {
             r.bt = t;
             r.bi = i;
-            if (ANY) return true;
+            if (MODE == kWalkAny) return true;
+            if (MODE == kWalkWithin && t < r.t_hi) return true;
         }
     }
     return false;
@@ -141,7 +161,7 @@ __device__ __forceinline__ bool closest_leaf(const ClosestScene &s, ClosestRay &
 // has nodes to walk, false when its result is final (it misses the scene box,
 // or the tree has no internal node: U <= 1 is one leaf of all N triangles and
 // has no node record to read).
-template <bool ANY>
+template <int MODE>
 __device__ __forceinline__ bool closest_start(const ClosestScene &s, ClosestRay &r, const float *o, float t_lo) {
     r.bt = FLT_MAX;
     r.bi = kNoHit;
@@ -166,7 +186,7 @@ __device__ __forceinline__ bool closest_start(const ClosestScene &s, ClosestRay 
     if (tzmax < tMax) tMax = tzmax;
     if (t_lo > 0.0f && tMin < t_lo) tMin = t_lo;   // the walk starts at t_lo (oracle)
     if (s.U < 2) {   // single leaf (reference: UB; defined as the oracle's)
-        (void)closest_leaf<ANY>(s, r, o, t_lo, 0, s.U ? s.N : 0u);
+        (void)closest_leaf<MODE>(s, r, o, t_lo, 0, s.U ? s.N : 0u);
         return false;
     }
     r.tMin = tMin;
@@ -181,7 +201,7 @@ __device__ __forceinline__ bool closest_start(const ClosestScene &s, ClosestRay 
 // together (they are still tested before the next node's decisions read the
 // best hit: the same decisions, the same hit).  COUNT: nodes entered (cn) and
 // triangles tested (ct), for the work counters.
-template <bool ANY, bool COUNT, int LDS>
+template <int MODE, bool COUNT, int LDS>
 __device__ __forceinline__ bool closest_step(const ClosestScene &s, ClosestRay &r, const float *o, float t_lo,
                                              const LaneStack<LDS> &stk, uint32_t &cn, uint32_t &ct) {
     const float best = r.bi != kNoHit ? r.bt : __builtin_inff();
@@ -250,16 +270,16 @@ __device__ __forceinline__ bool closest_step(const ClosestScene &s, ClosestRay &
     }
     if (!fin) r.nd = s.nodes[r.cur];
     if (COUNT) ct += (l0e - l0b) + (l1e - l1b);
-    if (closest_leaf<ANY>(s, r, o, t_lo, l0b, l0e)) return true;   // (ANY only) the first accepted triangle ends the walk
-    if (closest_leaf<ANY>(s, r, o, t_lo, l1b, l1e)) return true;
+    if (closest_leaf<MODE>(s, r, o, t_lo, l0b, l0e)) return true;   // (kWalkAny, kWalkWithin) an accepted triangle ends the walk
+    if (closest_leaf<MODE>(s, r, o, t_lo, l1b, l1e)) return true;
     return fin;
 }
 
-template <bool ANY, int LDS>
+template <int MODE, int LDS>
 __device__ __forceinline__ bool closest_step(const ClosestScene &s, ClosestRay &r, const float *o, float t_lo,
                                              const LaneStack<LDS> &stk) {
     uint32_t cn = 0, ct = 0;
-    return closest_step<ANY, false>(s, r, o, t_lo, stk, cn, ct);
+    return closest_step<MODE, false>(s, r, o, t_lo, stk, cn, ct);
 }
 
 }  // namespace dev

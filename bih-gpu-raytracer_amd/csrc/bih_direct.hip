@@ -29,8 +29,17 @@
 //   k_direct_resolve  per pixel: the sums, in the header's order.
 // The lights travel in the kernel arguments (the call's copy of the caller's
 // host array): no device buffer of them exists.
+//
+// Point lights (bih_render_lights*, n_dir < n_lights) share the 64 light slots
+// and take instantiations of their own of the three kernels (k_lights_setup,
+// k_shadow_lights, k_lights_resolve); calls without one launch the kernels
+// above, unchanged.  A lamp's L = Q - P is one expression (lamp_dir) on the
+// same bits of P in all three; its shadow ray is a segment query (t_hi = 1:
+// a triangle at or beyond the lamp does not shadow), the walk bih_closest.h's
+// kWalkWithin, a directional item riding along with t_hi = +inf.
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <stddef.h>
 
 #include "bih_closest.h"
 #include "bih_internal.h"
@@ -50,7 +59,16 @@ constexpr int kDSteps = 256;             // walk steps per lane between refill c
 constexpr float kShadowTLo = 1e-4f;      // BIH_SHADOW_T_LO
 constexpr uint32_t kMissShade = 0x00281414u;   // (20, 20, 40): Whitted's miss shade
 
-struct DLight { float x, y, z, w; };     // bih_light
+struct DLight { float x, y, z, w; };     // bih_light {dir, weight} or bih_point_light {pos, weight}
+
+// A point light's L at the hit point P: one expression for the facing mask
+// (setup), the shadow ray's direction (k_shadow) and the contribution
+// (resolve), each from the same bits of P (a listed sample's record).
+__device__ __forceinline__ void lamp_dir(const DLight &q, const float *p, float *l) {
+    l[0] = q.x - p[0];
+    l[1] = q.y - p[1];
+    l[2] = q.z - p[2];
+}
 
 struct DArgs {
     float cam[12];              // origin, lower_left, horizontal, vertical
@@ -58,6 +76,7 @@ struct DArgs {
     uint32_t row0, nrows, band_h, band_step;
     uint32_t d_base;            // XORWOW Weyl counter at the start of the frame
     uint32_t n_lights;
+    uint32_t n_dir;             // lights [0, n_dir) are directional, [n_dir, n_lights) point lights
     const TreeHeader *hdr;
     const uint4 *nodes;
     const float *tris;          // sorted {v0, e1, e2}
@@ -75,7 +94,9 @@ struct DArgs {
     DLight lights[kMaxLights];
 };
 
-__global__ void __launch_bounds__(kDSetupT) k_direct_setup(const DArgs a) {
+// POINT (compile time): the call has point lights (a.n_dir < a.n_lights).
+template <bool POINT>
+__device__ __forceinline__ void direct_setup_body(const DArgs &a) {
     const uint64_t P = (uint64_t)a.nrows * a.w;
     const uint64_t n = P * a.spp;
     const uint64_t i = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
@@ -95,9 +116,18 @@ __global__ void __launch_bounds__(kDSetupT) k_direct_setup(const DArgs a) {
             const float t = __uint_as_float(h.x);
             for (int k = 0; k < 3; ++k) pt[k] = a.cam[k] + t * d[k];
             dev::tri_normal(a.tris + 9ull * bi, nrm);
-            for (uint32_t k = 0; k < a.n_lights; ++k) {   // (k is uniform: the lights come as scalars)
+            const uint32_t n_dir = POINT ? a.n_dir : a.n_lights;
+            for (uint32_t k = 0; k < n_dir; ++k) {   // (k is uniform: the lights come as scalars)
                 const float c = (nrm[0] * a.lights[k].x + nrm[1] * a.lights[k].y) + nrm[2] * a.lights[k].z;
                 if (c > 0.0f) face |= 1ull << k;
+            }
+            if (POINT) {
+                for (uint32_t k = n_dir; k < a.n_lights; ++k) {
+                    float l[3];
+                    lamp_dir(a.lights[k], pt, l);
+                    const float c = (nrm[0] * l[0] + nrm[1] * l[1]) + nrm[2] * l[2];
+                    if (c > 0.0f) face |= 1ull << k;
+                }
             }
         }
         a.lit[i] = 0ull;
@@ -118,6 +148,9 @@ __global__ void __launch_bounds__(kDSetupT) k_direct_setup(const DArgs a) {
     }
 }
 
+__global__ void __launch_bounds__(kDSetupT) k_direct_setup(const DArgs a) { direct_setup_body<false>(a); }
+__global__ void __launch_bounds__(kDSetupT) k_lights_setup(const DArgs a) { direct_setup_body<true>(a); }
+
 // A work item: where its ray starts, whose bit it decides, and its walk.
 struct SRay {
     float o[3];
@@ -125,16 +158,22 @@ struct SRay {
     ClosestRay w;
 };
 
+// POINT: the item's ray is a segment (within_hit: hit below its t_hi).
+template <bool POINT>
 __device__ __forceinline__ void sray_write(const DArgs &a, const SRay &r) {
-    if (r.w.bi == kNoHit) atomicOr(a.lit + r.i, 1ull << r.k);
+    const bool occluded = POINT ? dev::within_hit(r.w) : r.w.bi != kNoHit;
+    if (!occluded) atomicOr(a.lit + r.i, 1ull << r.k);
 }
 
-// LDS: stack slots per lane kept in LDS (the rest in this thread's HBM area).
-template <int LDS>
-__global__ void __launch_bounds__(kDT) k_shadow(const DArgs a) {
-    __shared__ uint32_t s_node[LDS * kDT];
-    __shared__ float s_min[LDS * kDT];
-    __shared__ float s_max[LDS * kDT];
+// The shadow kernels' body.  LDS: stack slots per lane kept in LDS (the rest
+// in this thread's HBM area; s_node, s_min, s_max: LDS * kDT words each).
+// POINT (compile time): the call has point lights.  An item then carries its
+// own t_hi -- 1.0f for a lamp (it sits at t = 1 of d = Q - P), +inf for a
+// directional light -- and the walk is kWalkWithin, which with t_hi = +inf is
+// exactly the ANY walk (every accepted t is below FLT_MAX).
+template <int LDS, bool POINT>
+__device__ __forceinline__ void shadow_body(const DArgs &a, uint32_t *s_node, float *s_min, float *s_max) {
+    constexpr int MODE = POINT ? dev::kWalkWithin : dev::kWalkAny;
     const uint32_t lane = threadIdx.x;
     const dev::LaneStack<LDS> stk(s_node, s_min, s_max, a.spill);
     const ClosestScene sc = dev::load_closest_scene(a.hdr, a.nodes, a.tris, a.dup);
@@ -171,8 +210,15 @@ __global__ void __launch_bounds__(kDT) k_shadow(const DArgs a) {
                     // costs the walk three waves per CU, 175 against 164 ms)
                     const DLight l = a.lights[k];
                     r.w.d[0] = l.x; r.w.d[1] = l.y; r.w.d[2] = l.z;
-                    has = dev::closest_start<true>(sc, r.w, r.o, kShadowTLo);
-                    if (!has) sray_write(a, r);   // missed the box / one-leaf tree: final
+                    if (POINT) {
+                        r.w.t_hi = __builtin_inff();
+                        if (k >= a.n_dir) {
+                            lamp_dir(l, r.o, r.w.d);
+                            r.w.t_hi = 1.0f;
+                        }
+                    }
+                    has = dev::closest_start<MODE>(sc, r.w, r.o, kShadowTLo);
+                    if (!has) sray_write<POINT>(a, r);   // missed the box / one-leaf tree: final
                 }
             }
             idle = __ballot(!has);
@@ -183,17 +229,34 @@ __global__ void __launch_bounds__(kDT) k_shadow(const DArgs a) {
         }
         if (has) {
             bool fin = false;
-            for (int k = 0; k < kDSteps && !fin; ++k) fin = dev::closest_step<true>(sc, r.w, r.o, kShadowTLo, stk);
+            for (int k = 0; k < kDSteps && !fin; ++k) fin = dev::closest_step<MODE>(sc, r.w, r.o, kShadowTLo, stk);
             if (fin) {
-                sray_write(a, r);
+                sray_write<POINT>(a, r);
                 has = false;
             }
         }
     }
 }
 
-__global__ void __launch_bounds__(kDSetupT) k_direct_resolve(const DArgs a) {
-    __shared__ DLight s_light[kMaxLights];
+template <int LDS>
+__global__ void __launch_bounds__(kDT) k_shadow(const DArgs a) {
+    __shared__ uint32_t s_node[LDS * kDT];
+    __shared__ float s_min[LDS * kDT];
+    __shared__ float s_max[LDS * kDT];
+    shadow_body<LDS, false>(a, s_node, s_min, s_max);
+}
+
+// bih_render_lights* with point lights: the same LDS per block.
+template <int LDS>
+__global__ void __launch_bounds__(kDT) k_shadow_lights(const DArgs a) {
+    __shared__ uint32_t s_node[LDS * kDT];
+    __shared__ float s_min[LDS * kDT];
+    __shared__ float s_max[LDS * kDT];
+    shadow_body<LDS, true>(a, s_node, s_min, s_max);
+}
+
+template <bool POINT>
+__device__ __forceinline__ void direct_resolve_body(const DArgs &a, DLight *s_light) {
     if (threadIdx.x < a.n_lights) s_light[threadIdx.x] = a.lights[threadIdx.x];
     __syncthreads();
     const uint64_t P = (uint64_t)a.nrows * a.w;
@@ -211,10 +274,22 @@ __global__ void __launch_bounds__(kDSetupT) k_direct_resolve(const DArgs a) {
             float nrm[3];
             dev::tri_normal(a.tris + 9ull * bi, nrm);
             while (l) {   // k ascending over the lit bits
-                const DLight q = s_light[__builtin_ctzll(l)];
+                const uint32_t k = (uint32_t)__builtin_ctzll(l);
+                const DLight q = s_light[k];
                 l &= l - 1ull;
-                const float c = (nrm[0] * q.x + nrm[1] * q.y) + nrm[2] * q.z;
-                e = e + q.w * c;
+                if (POINT && k >= a.n_dir) {
+                    const uint4 rec = a.rec[i];   // (a lit sample is a listed one: rec.xyz = P)
+                    const float pt[3] = {__uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z)};
+                    float L[3];
+                    lamp_dir(q, pt, L);
+                    const float c = (nrm[0] * L[0] + nrm[1] * L[1]) + nrm[2] * L[2];
+                    const float r2 = (L[0] * L[0] + L[1] * L[1]) + L[2] * L[2];
+                    const float len = sqrtf(r2);
+                    e = e + (q.w * (c / len)) / r2;
+                } else {
+                    const float c = (nrm[0] * q.x + nrm[1] * q.y) + nrm[2] * q.z;
+                    e = e + q.w * c;
+                }
             }
         }
         E = s == 0 ? e : E + e;
@@ -227,14 +302,27 @@ __global__ void __launch_bounds__(kDSetupT) k_direct_resolve(const DArgs a) {
     }
 }
 
+__global__ void __launch_bounds__(kDSetupT) k_direct_resolve(const DArgs a) {
+    __shared__ DLight s_light[kMaxLights];
+    direct_resolve_body<false>(a, s_light);
+}
+
+__global__ void __launch_bounds__(kDSetupT) k_lights_resolve(const DArgs a) {
+    __shared__ DLight s_light[kMaxLights];
+    direct_resolve_body<true>(a, s_light);
+}
+
 }  // namespace
 
 int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes &p, const float *lights,
-                  uint32_t n_lights, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
+                  uint32_t n_lights, uint32_t n_dir, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
                   uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
     if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0 || n_lights == 0) return 0;
-    if (n_lights > kMaxLights) return (int)hipErrorInvalidValue;
+    if (n_lights > kMaxLights || n_dir > n_lights) return (int)hipErrorInvalidValue;
+    static_assert(offsetof(DArgs, n_dir) + 4 == offsetof(DArgs, hdr) && offsetof(DArgs, n_dir) % 8 == 4,
+                  "n_dir sits in what was padding before the pointers: the argument block has not grown");
+    const bool point = n_dir < n_lights;   // else: bih_render_direct's kernels
     DArgs a;
     for (int k = 0; k < 12; ++k) a.cam[k] = ra.cam[k];
     a.w = ra.w;
@@ -246,6 +334,7 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
     a.band_step = ra.band_step;
     a.d_base = ra.d_base;
     a.n_lights = n_lights;
+    a.n_dir = n_dir;
     a.hdr = t.hdr;
     a.nodes = t.nodes;
     a.tris = t.tris_s;
@@ -269,18 +358,25 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
     if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return (int)e;
     const uint64_t P = (uint64_t)ra.nrows * ra.w, n = P * ra.spp;
-    hipLaunchKernelGGL(k_direct_setup, dim3((uint32_t)((n + kDSetupT - 1) / kDSetupT)), dim3(kDSetupT), 0, st, a);
+    const dim3 sgrid((uint32_t)((n + kDSetupT - 1) / kDSetupT));
+    if (point) hipLaunchKernelGGL(k_lights_setup, sgrid, dim3(kDSetupT), 0, st, a);
+    else hipLaunchKernelGGL(k_direct_setup, sgrid, dim3(kDSetupT), 0, st, a);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     // (the listed samples are counted on the device: the grid covers all of them)
     const uint64_t need = (n * n_lights + kDT - 1) / kDT;
     const dim3 grid((uint32_t)(need < max_blocks ? need : max_blocks)), block(kDT);
-    if (lds_slots == (uint32_t)kTraceLdsTest) hipLaunchKernelGGL((k_shadow<kTraceLdsTest>), grid, block, 0, st, a);
+    const bool small = lds_slots == (uint32_t)kTraceLdsTest;
+    if (point && small) hipLaunchKernelGGL((k_shadow_lights<kTraceLdsTest>), grid, block, 0, st, a);
+    else if (point) hipLaunchKernelGGL((k_shadow_lights<kTraceLds>), grid, block, 0, st, a);
+    else if (small) hipLaunchKernelGGL((k_shadow<kTraceLdsTest>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((k_shadow<kTraceLds>), grid, block, 0, st, a);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     if (p.irradiance || p.rgba) {
-        hipLaunchKernelGGL(k_direct_resolve, dim3((uint32_t)((P + kDSetupT - 1) / kDSetupT)), dim3(kDSetupT), 0, st, a);
+        const dim3 rgrid((uint32_t)((P + kDSetupT - 1) / kDSetupT));
+        if (point) hipLaunchKernelGGL(k_lights_resolve, rgrid, dim3(kDSetupT), 0, st, a);
+        else hipLaunchKernelGGL(k_direct_resolve, rgrid, dim3(kDSetupT), 0, st, a);
         e = hipGetLastError();
     }
     return (int)e;

@@ -335,7 +335,9 @@ constexpr int kTraceLds = 10;       // as kWLds (bih_whitted.hip)
 constexpr int kTraceLdsTest = 2;
 uint32_t trace_grid_blocks(int device);
 size_t trace_spill_words(uint32_t blocks);
-int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, bool occluded, void *d_out,
+// query: BIH_QUERY_CLOSEST / _OCCLUDED, with kQueryTHi for the segment queries
+constexpr uint32_t kQueryTHi = 0x10u;   // BIH_QUERY_T_HI
+int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, uint32_t query, void *d_out,
                  uint32_t lds_slots, uint32_t *cursor, uint32_t *spill, uint32_t max_blocks, void *stream);
 // G-buffer render (bih_gbuffer.hip): the closest hit of every primary sample
 // of the frame `a` describes (cam, w, h, spp, rows, d_base, rng_in), to
@@ -360,8 +362,9 @@ int launch_gbuffer(const DeviceTree &t, const RenderArgs &a, const GBufferPlanes
                    uint32_t max_blocks, void *stream, bool sorted_prim = false);
 // Direct lighting (bih_direct.hip), behind a launch_gbuffer of the same frame
 // `a` on the same stream that left its hit records, sorted_prim, in rec
-// (bih_hit[P*spp]): per sample the lights (n_lights of {dir[3], weight}, host
-// memory, copied into the kernel arguments) that face its hit triangle and
+// (bih_hit[P*spp]): per sample the lights (n_lights of 4 floats, host memory,
+// copied into the kernel arguments: the first n_dir {dir[3], weight}, the rest
+// point lights {pos[3], weight}) that face its hit triangle and
 // reach its hit point, to p.lit (u64[P*spp], never null), and the pixel sums
 // resolved from them (a null plane is not written).  list (u32[P*spp]), face
 // (u64[P*spp]): the hit samples with a facing light.  count (one u32) and
@@ -374,7 +377,7 @@ struct DirectPlanes {
     uint32_t *rgba = nullptr;
 };
 int launch_direct(const DeviceTree &t, const RenderArgs &a, const DirectPlanes &p, const float *lights,
-                  uint32_t n_lights, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
+                  uint32_t n_lights, uint32_t n_dir, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
                   uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream);
 int launch_rng_init(uint32_t *rng, uint32_t w, uint32_t row0, uint32_t nrows, uint32_t band_h,
                     uint32_t band_step, uint64_t seed, uint64_t skip, int device, void *stream);

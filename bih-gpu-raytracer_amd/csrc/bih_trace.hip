@@ -5,6 +5,11 @@
 // traverse_closest: the walk of bih_closest.h, with each ray's own origin and
 // t_lo.  The occlusion query is the same walk ended at the first accepted
 // triangle (ANY), so its flag is exactly (closest prim != BIH_NO_HIT).
+// The segment queries (BIH_QUERY_T_HI: the ray ends at its t_hi) are defined on
+// the closest query's result: OCCLUDED_WITHIN is the same walk ended at the
+// first accepted triangle below t_hi (kWalkWithin, a prefix of the closest
+// walk), CLOSEST_WITHIN the closest kernel with the t < t_hi filter at its
+// write.  The two older queries do not read that float.
 //
 // Caller rays are incoherent and their walks very unequal, so the kernel has
 // k_wh_trace's shape (bih_whitted.hip): persistent one-wave blocks; a lane
@@ -35,7 +40,7 @@ struct TraceArgs {
     const float *tris;
     const uint32_t *dup;
     const uint32_t *tri_idx;    // sorted position -> file order (BIH_ARR_TRI_INDEX)
-    const float4 *rays;         // bih_ray: {o, t_lo}, {d, reserved}
+    const float4 *rays;         // bih_ray: {o, t_lo}, {d, t_hi}
     void *out;                  // bih_hit[n] or u8[n]
     uint32_t n;
     uint32_t *cursor;           // rays taken so far (zero at launch)
@@ -52,27 +57,30 @@ struct TRay {
 // The ray's result into its own slot: bih_hit {t, u, v, prim} as one 16-byte
 // store (u, v: the accepted triangle's test once more -- the same inputs and
 // expressions, the same bits), or the occlusion byte.
-template <bool ANY>
+// T_HI: a segment query; the answer is the closest one's when its t < t_hi.
+template <bool ANY, bool T_HI>
 __device__ __forceinline__ void tray_write(const TraceArgs &a, const ClosestScene &s, const TRay &r) {
+    const bool hit = T_HI ? dev::within_hit(r.w) : r.w.bi != kNoHit;
     if (ANY) {
-        reinterpret_cast<uint8_t *>(a.out)[r.id] = r.w.bi != kNoHit ? 1 : 0;
+        reinterpret_cast<uint8_t *>(a.out)[r.id] = hit ? 1 : 0;
         return;
     }
     float t = FLT_MAX, u = 0.0f, v = 0.0f;
     uint32_t prim = kNoHit;
-    if (r.w.bi != kNoHit) {
+    if (hit) {
         (void)dev::mt_tuv(s.tris + 9ull * r.w.bi, r.o, r.w.d, t, u, v);
         prim = a.tri_idx[r.w.bi];
     }
     reinterpret_cast<uint4 *>(a.out)[r.id] = make_uint4(__float_as_uint(t), __float_as_uint(u), __float_as_uint(v), prim);
 }
 
-// LDS: stack slots per lane kept in LDS (the rest in this thread's HBM area).
-template <int LDS, bool ANY>
-__global__ void __launch_bounds__(kTT) k_trace(const TraceArgs a) {
-    __shared__ uint32_t s_node[LDS * kTT];
-    __shared__ float s_min[LDS * kTT];
-    __shared__ float s_max[LDS * kTT];
+// The kernels' body.  LDS: stack slots per lane kept in LDS (the rest in this
+// thread's HBM area; s_node, s_min, s_max: LDS * kTT words each).  T_HI: the
+// rays' last float is read.
+template <int LDS, bool ANY, bool T_HI>
+__device__ __forceinline__ void trace_body(const TraceArgs &a, uint32_t *s_node, float *s_min, float *s_max) {
+    // (CLOSEST_WITHIN walks the whole closest walk: its record needs the closest hit)
+    constexpr int MODE = !ANY ? dev::kWalkClosest : (T_HI ? dev::kWalkWithin : dev::kWalkAny);
     const uint32_t lane = threadIdx.x;
     const dev::LaneStack<LDS> stk(s_node, s_min, s_max, a.spill);
     const ClosestScene sc = dev::load_closest_scene(a.hdr, a.nodes, a.tris, a.dup);
@@ -96,10 +104,11 @@ __global__ void __launch_bounds__(kTT) k_trace(const TraceArgs a) {
                 if (i < n) {
                     const float4 q0 = a.rays[2 * i], q1 = a.rays[2 * i + 1];   // two 16-byte loads
                     r.o[0] = q0.x; r.o[1] = q0.y; r.o[2] = q0.z; r.t_lo = q0.w;
-                    r.w.d[0] = q1.x; r.w.d[1] = q1.y; r.w.d[2] = q1.z;         // (q1.w: reserved, not read)
+                    r.w.d[0] = q1.x; r.w.d[1] = q1.y; r.w.d[2] = q1.z;
+                    if (T_HI) r.w.t_hi = q1.w;                                 // (else q1.w: reserved, not read)
                     r.id = (uint32_t)i;
-                    has = dev::closest_start<ANY>(sc, r.w, r.o, r.t_lo);
-                    if (!has) tray_write<ANY>(a, sc, r);   // missed the box / one-leaf tree: final
+                    has = dev::closest_start<MODE>(sc, r.w, r.o, r.t_lo);
+                    if (!has) tray_write<ANY, T_HI>(a, sc, r);   // missed the box / one-leaf tree: final
                 }
             }
         }
@@ -109,13 +118,30 @@ __global__ void __launch_bounds__(kTT) k_trace(const TraceArgs a) {
         }
         if (has) {
             bool fin = false;
-            for (int k = 0; k < kTSteps && !fin; ++k) fin = dev::closest_step<ANY>(sc, r.w, r.o, r.t_lo, stk);
+            for (int k = 0; k < kTSteps && !fin; ++k) fin = dev::closest_step<MODE>(sc, r.w, r.o, r.t_lo, stk);
             if (fin) {
-                tray_write<ANY>(a, sc, r);
+                tray_write<ANY, T_HI>(a, sc, r);
                 has = false;
             }
         }
     }
+}
+
+template <int LDS, bool ANY>
+__global__ void __launch_bounds__(kTT) k_trace(const TraceArgs a) {
+    __shared__ uint32_t s_node[LDS * kTT];
+    __shared__ float s_min[LDS * kTT];
+    __shared__ float s_max[LDS * kTT];
+    trace_body<LDS, ANY, false>(a, s_node, s_min, s_max);
+}
+
+// The segment queries (BIH_QUERY_T_HI).
+template <int LDS, bool ANY>
+__global__ void __launch_bounds__(kTT) k_trace_within(const TraceArgs a) {
+    __shared__ uint32_t s_node[LDS * kTT];
+    __shared__ float s_min[LDS * kTT];
+    __shared__ float s_max[LDS * kTT];
+    trace_body<LDS, ANY, true>(a, s_node, s_min, s_max);
 }
 
 }  // namespace
@@ -131,7 +157,7 @@ size_t trace_spill_words(uint32_t blocks) {
     return (size_t)blocks * kTT * (kStackDepth - kTraceLdsTest) * 3;
 }
 
-int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, bool occluded, void *d_out,
+int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, uint32_t query, void *d_out,
                  uint32_t lds_slots, uint32_t *cursor, uint32_t *spill, uint32_t max_blocks, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
     if (n == 0) return 0;
@@ -151,7 +177,13 @@ int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, bool occlu
     const uint32_t need = (n + kTT - 1) / kTT;
     const dim3 grid(need < max_blocks ? need : max_blocks), block(kTT);
     const bool small = lds_slots == (uint32_t)kTraceLdsTest;
-    if (small && occluded) hipLaunchKernelGGL((k_trace<kTraceLdsTest, true>), grid, block, 0, st, a);
+    const bool occluded = (query & ~kQueryTHi) == 1u;   // BIH_QUERY_OCCLUDED
+    if (query & kQueryTHi) {
+        if (small && occluded) hipLaunchKernelGGL((k_trace_within<kTraceLdsTest, true>), grid, block, 0, st, a);
+        else if (small) hipLaunchKernelGGL((k_trace_within<kTraceLdsTest, false>), grid, block, 0, st, a);
+        else if (occluded) hipLaunchKernelGGL((k_trace_within<kTraceLds, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_trace_within<kTraceLds, false>), grid, block, 0, st, a);
+    } else if (small && occluded) hipLaunchKernelGGL((k_trace<kTraceLdsTest, true>), grid, block, 0, st, a);
     else if (small) hipLaunchKernelGGL((k_trace<kTraceLdsTest, false>), grid, block, 0, st, a);
     else if (occluded) hipLaunchKernelGGL((k_trace<kTraceLds, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((k_trace<kTraceLds, false>), grid, block, 0, st, a);

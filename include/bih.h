@@ -38,7 +38,7 @@ extern "C" {
                                3: bih_whitted_work, BIH_PARAM_WHITTED_COUNTERS;
                                4: bih_host_register / bih_host_unregister, bih_render_history;
                                (4, added since: bih_trace*, bih_render_gbuffer*, BIH_PARAM_GBUFFER_MASK,
-                                bih_render_direct*) */
+                                bih_render_direct*, BIH_QUERY_T_HI and bih_ray.t_hi, bih_render_lights*) */
 
 /* error codes */
 #define BIH_OK               0
@@ -273,7 +273,25 @@ int bih_tree_set_param(bih_tree *tree, int param, uint64_t value);
  *    prim != BIH_NO_HIT, else 0.  The walk stops at the first accepted
  *    triangle; until then it is the closest walk (same visit order, interval
  *    clamp and accept test).
- *  - Rays: d need not be normalised.  `reserved` is not read; set it to 0.
+ *  - Segment queries (BIH_QUERY_T_HI: the ray ends at t_hi, Embree's tfar; the
+ *    last float of bih_ray).  Both are defined on the BIH_QUERY_CLOSEST result
+ *    of the same {o, t_lo, d}; there is no new walk rule, and t_hi bounds no
+ *    walk interval.
+ *    BIH_QUERY_OCCLUDED_WITHIN: 1 exactly when that result has
+ *    prim != BIH_NO_HIT and t < t_hi (one strict f32 compare), else 0.  So a
+ *    NaN t_hi gives 0, t_hi <= t_lo gives 0, and t_hi = FLT_MAX or +inf gives
+ *    exactly BIH_QUERY_OCCLUDED's byte.  The walk is the closest walk (the
+ *    same accepts, best-hit updates and interval clamp, also for hits at or
+ *    beyond t_hi) ended at the first accepted triangle with t < t_hi: the best
+ *    t only decreases, so the closest walk's final t is below t_hi exactly
+ *    when some accepted t was.  It is a prefix of the closest walk.
+ *    BIH_QUERY_CLOSEST_WITHIN: that record when its t < t_hi, else the miss
+ *    record {FLT_MAX, 0, 0, BIH_NO_HIT}.
+ *    Output sizes, alignment, errors, ordering and memory are those of
+ *    BIH_QUERY_CLOSEST resp. BIH_QUERY_OCCLUDED.
+ *  - Rays: d need not be normalised.  BIH_QUERY_CLOSEST and BIH_QUERY_OCCLUDED
+ *    do not read the last float (`reserved`; set it to 0, which does NOT mean
+ *    "infinite" to the segment queries).
  *    Like the reference's test, triangles are one-sided (det > 1e-6 only).
  *    Non-finite or zero directions and origins are legal: the result is
  *    whatever the arithmetic above gives (the walk descends or pops on every
@@ -293,14 +311,22 @@ int bih_tree_set_param(bih_tree *tree, int param, uint64_t value);
 #define BIH_MAX_RAYS    (1u << 30)
 #define BIH_QUERY_CLOSEST   0u
 #define BIH_QUERY_OCCLUDED  1u
+#define BIH_QUERY_T_HI      0x10u   /* flag: the ray ends at bih_ray.t_hi */
+#define BIH_QUERY_CLOSEST_WITHIN   (BIH_QUERY_CLOSEST | BIH_QUERY_T_HI)    /* 0x10 */
+#define BIH_QUERY_OCCLUDED_WITHIN  (BIH_QUERY_OCCLUDED | BIH_QUERY_T_HI)   /* 0x11 */
 
-typedef struct bih_ray { float o[3]; float t_lo; float d[3]; float reserved; } bih_ray; /* 32 B */
+/* The last float: `reserved` to the two first queries, `t_hi` to the segment
+ * queries (one member, two names). */
+typedef struct bih_ray {
+    float o[3]; float t_lo; float d[3];
+    union { float reserved; float t_hi; };
+} bih_ray;                                                                              /* 32 B */
 typedef struct bih_hit { float t, u, v; uint32_t prim; } bih_hit;                       /* 16 B */
 
 /* d_rays, d_out: device memory on the tree's device, 16-byte aligned (else
  * BIH_ERR_INVALID).  Asynchronous on `stream` (NULL = the tree's stream);
- * bih_sync waits.  d_out: bih_hit[n_rays] (CLOSEST) or uint8_t[n_rays]
- * (OCCLUDED: 1 / 0), in the rays' order. */
+ * bih_sync waits.  d_out: bih_hit[n_rays] (CLOSEST, CLOSEST_WITHIN) or
+ * uint8_t[n_rays] (OCCLUDED, OCCLUDED_WITHIN: 1 / 0), in the rays' order. */
 int bih_trace_device(const bih_tree *tree, const bih_ray *d_rays, uint64_t n_rays,
                      uint32_t query, void *d_out, void *stream);
 /* Host rays in, host results out; synchronous.  Stages through device buffers
@@ -466,6 +492,48 @@ int bih_render_direct_device(const bih_tree *tree, const bih_camera *camera, uin
 int bih_render_direct(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
                       uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
                       const bih_light *lights, uint32_t n_lights,
+                      const bih_direct *host_planes);                       /* synchronous, host memory */
+
+/* Direct lighting with point lights (lamps) next to directional ones, in one
+ * call.  A triangle BEHIND a lamp does not shadow it, which BIH_QUERY_OCCLUDED
+ * cannot say: a lamp's shadow ray is a segment query.
+ *
+ * Bit k < n_dir of lit is directional light k; bit n_dir + j is point light j.
+ * n_dir + n_point is in 1..BIH_MAX_LIGHTS; an array may be NULL exactly when
+ * its count is 0.  Both arrays are HOST memory, copied by the call.
+ *
+ * Semantics: bih_render_direct's, every f32 operation separately rounded;
+ * directional lights work exactly as there.  For a hit sample with hit point P
+ * and normal n (both as bih_render_direct defines them) and a point light
+ * {pos = Q, weight = W}:
+ *  - L[a] = Q[a] - P[a].
+ *  - c = (n.x*L.x + n.y*L.y) + n.z*L.z; the light is facing exactly when
+ *    c > 0.0f.
+ *  - The light is lit when it is facing and BIH_QUERY_OCCLUDED_WITHIN on
+ *    {o = P, t_lo = BIH_SHADOW_T_LO, d = L, t_hi = 1.0f} returns 0: the lamp
+ *    sits at t = 1, and a triangle at or beyond it does not shadow.  A lamp
+ *    exactly at P (L = 0) is never facing.
+ *  - Contribution, in this order: r2 = (L.x*L.x + L.y*L.y) + L.z*L.z;
+ *    len = sqrtf(r2); e_s = e_s + (W * (c / len)) / r2 -- the cosine over the
+ *    squared distance.  Whatever inf or NaN the arithmetic gives is the
+ *    result (rgba's clamp is defined for both).
+ *  - The sum runs over the lit bits in ascending k, so directional lights come
+ *    first.  The per-pixel E, rgba and miss shade are bih_render_direct's.
+ *  - With n_point == 0 every plane is bit-identical to bih_render_direct's.
+ * Errors, in bih_render_direct's order, its light checks replaced by: n_dir +
+ * n_point == 0 or > BIH_MAX_LIGHTS -> BIH_ERR_INVALID; an array NULL with a
+ * non-zero count -> BIH_ERR_INVALID.
+ * Planes, RNG accounting, ordering and scratch: exactly bih_render_direct's. */
+typedef struct bih_point_light { float pos[3]; float weight; } bih_point_light;  /* 16 B */
+int bih_render_lights_device(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                             uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                             const bih_light *dir_lights, uint32_t n_dir,
+                             const bih_point_light *point_lights, uint32_t n_point,
+                             const bih_direct *d_planes, void *stream);     /* async; bih_sync waits */
+int bih_render_lights(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                      uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                      const bih_light *dir_lights, uint32_t n_dir,
+                      const bih_point_light *point_lights, uint32_t n_point,
                       const bih_direct *host_planes);                       /* synchronous, host memory */
 
 /* The drop-in host loop (bih_render into a caller's framebuffer) ends in a
