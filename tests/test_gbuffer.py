@@ -404,10 +404,11 @@ def test_edge_scenes(name, gpu, bihrt_mod):
 
 @pytest.mark.gpu
 def test_shapes(gpu, bihrt_mod):
-    """Partial tiles, every tile shape (spp 1, 4, 16, 64), one pixel per wave,
+    """Partial tiles, every tile shape (spp 1, 2, 4, .. 64), one pixel per wave,
     and spp that are no power of two."""
     g = tree("cornell")
-    for w, h, spp in ((1, 1, 1), (37, 29, 1), (37, 29, 4), (16, 8, 16), (8, 8, 64), (37, 29, 3), (20, 12, 5)):
+    for w, h, spp in ((1, 1, 1), (37, 29, 1), (37, 29, 4), (16, 8, 16), (8, 8, 64), (37, 29, 3), (20, 12, 5),
+                      (37, 29, 2), (37, 29, 8), (20, 12, 32)):
         exp = expected("cornell", "K1", w, h, spp, 1)
         if (w, h) != (1, 1):
             balanced("cornell", exp)

@@ -920,16 +920,9 @@ def test_failed_back_tree_allocation_leaves_tree_usable(gpu, bihrt_mod, oracle_m
         g.close()
 
 
-@pytest.mark.gpu
-def test_stamped_state_panning_sequence_matches_oracle(gpu, bihrt_mod, oracle_mod):
-    """Frustum-bin launches on one stream keep each tile's XORWOW state with
-    a stamp (bih_capi.cpp stamped mode): a tile no triangle covers is not
-    stepped and catches up when it turns live, every 64 frames all tiles are
-    brought level (k_rng_sync), and a render of another kind takes the state
-    back into the ring.  A small object crosses the view over 160 frames in
-    calls of 1 .. 16 frames, so tiles turn live after long background runs;
-    sampled frames equal the oracle's, then a Whitted frame, a jump back and
-    a frame after it continue the sequence."""
+def stamped_panning_sequence(bihrt_mod, oracle_mod, w, h, spp):
+    """The body of test_stamped_state_panning_sequence_matches_oracle at a w x h
+    image and spp samples (tests/test_tile_shapes.py runs it at other tile shapes)."""
     import torch
     S = bihrt_mod.scenes
     tris = S.soup(20_000, seed=3).copy()
@@ -937,8 +930,7 @@ def test_stamped_state_panning_sequence_matches_oracle(gpu, bihrt_mod, oracle_mo
     v[:] = 0.25 * (v - v.mean(0)) + v.mean(0)     # the object covers a small part of the view
     g = bihrt_mod.GPUArrayManager(tris)
     ot = oracle_mod.OracleTree(tris)
-    w, h = 96, 64
-    r = bihrt_mod.Renderer(g, w, h)
+    r = bihrt_mod.Renderer(g, w, h, spp=spp)
     sizes = [1, 16, 3, 1, 8, 16, 2, 1, 16, 5]
     stride = h * w
     shapes, frame = [], 0
@@ -966,7 +958,7 @@ def test_stamped_state_panning_sequence_matches_oracle(gpu, bihrt_mod, oracle_mo
             continue
         b = buf.cpu().numpy().view(np.uint32)
         for j in sorted({0, n - 1}):
-            ref, _ = ot.render(w, h, frame=f0 + j, cam=np.array(cam.as_list(), np.float32))
+            ref, _ = ot.render(w, h, spp=spp, frame=f0 + j, cam=np.array(cam.as_list(), np.float32))
             got = b[j * stride:(j + 1) * stride].reshape(h, w)
             assert np.array_equal(got, ref), (f0 + j, int((got != ref).sum()))
             checked += 1
@@ -986,16 +978,29 @@ def test_stamped_state_panning_sequence_matches_oracle(gpu, bihrt_mod, oracle_mo
     for f, kind, stream in plan:
         if kind == "whitted":
             r.render_whitted_device(out.data_ptr(), f)
-            ref, _ = ot.render_whitted(w, h, frame=f, cam=camf)
+            ref, _ = ot.render_whitted(w, h, spp=spp, frame=f, cam=camf)
         else:
             r.render_device(out.data_ptr(), f, stream=stream.cuda_stream if stream else None)
-            ref, _ = ot.render(w, h, frame=f, cam=camf)
+            ref, _ = ot.render(w, h, spp=spp, frame=f, cam=camf)
         if stream is not None:
             stream.synchronize()
         r.sync()
         got = out.cpu().numpy().view(np.uint32).reshape(h, w)
         assert np.array_equal(got, ref), (f, kind, int((got != ref).sum()))
     g.close()
+
+
+@pytest.mark.gpu
+def test_stamped_state_panning_sequence_matches_oracle(gpu, bihrt_mod, oracle_mod):
+    """Frustum-bin launches on one stream keep each tile's XORWOW state with
+    a stamp (bih_capi.cpp stamped mode): a tile no triangle covers is not
+    stepped and catches up when it turns live, every 64 frames all tiles are
+    brought level (k_rng_sync), and a render of another kind takes the state
+    back into the ring.  A small object crosses the view over 160 frames in
+    calls of 1 .. 16 frames, so tiles turn live after long background runs;
+    sampled frames equal the oracle's, then a Whitted frame, a jump back and
+    a frame after it continue the sequence."""
+    stamped_panning_sequence(bihrt_mod, oracle_mod, 96, 64, 4)
 
 
 @pytest.mark.gpu
