@@ -21,6 +21,7 @@ import numpy as np
 from . import scenes  # noqa: F401
 from ._lib import (PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_STATIC_SOUP,
                    PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS, PARAM_GBUFFER_MASK,
+                   AREA_LIGHT_DTYPE, MAX_AREA_LIGHTS, AreaLight, LightSet,
                    NO_HIT, LIGHT_DTYPE, POINT_LIGHT_DTYPE, MAX_LIGHTS, SHADOW_T_LO, QUERY_CLOSEST, QUERY_OCCLUDED,
                    QUERY_T_HI, QUERY_CLOSEST_WITHIN, QUERY_OCCLUDED_WITHIN, PointLight, Direct, GBuffer, Hit, Light, Ray, TRAVERSE_ANYHIT,
                    TRAVERSE_REFERENCE, BihError, Camera, Framebuffer, Rows, Scene, TreeInfo, check, load)
@@ -80,6 +81,30 @@ def pack_point_lights(lights) -> np.ndarray:
     if a.dtype != POINT_LIGHT_DTYPE:
         a = np.ascontiguousarray(a, np.float32).reshape(-1, 4).view(POINT_LIGHT_DTYPE).reshape(-1)
     return np.ascontiguousarray(a).reshape(-1)
+
+
+def pack_area_lights(lights) -> np.ndarray:
+    """(k,) AREA_LIGHT_DTYPE array (bih_area_light records) of such an array or
+    of (k, 10) rows {corner, edge_u, edge_v, weight}."""
+    a = np.asarray(lights)
+    if a.dtype != AREA_LIGHT_DTYPE:
+        rows = np.ascontiguousarray(a, np.float32).reshape(-1, 10)
+        a = np.zeros(rows.shape[0], AREA_LIGHT_DTYPE)
+        a["corner"], a["edge_u"], a["edge_v"], a["weight"] = rows[:, 0:3], rows[:, 3:6], rows[:, 6:9], rows[:, 9]
+    return np.ascontiguousarray(a).reshape(-1)
+
+
+def area_light_sample(light, j: int, seed: int, pixel: int, frame: int, spp: int, s: int) -> np.ndarray:
+    """bih_area_light_sample (host only): the point (3,) float32 of area light
+    j -- `light`, one AREA_LIGHT_DTYPE record or a 10-float row -- that sample s
+    of global pixel `pixel` = y*w + x uses in frame `frame` at spp samples."""
+    lt = pack_area_lights(light)
+    if lt.shape[0] != 1:
+        raise ValueError("area_light_sample takes one light")
+    q = (C.c_float * 3)()
+    check(load().bih_area_light_sample(C.c_void_p(lt.ctypes.data), j, seed, pixel, frame, spp, s, q),
+          "bih_area_light_sample")
+    return np.array(q[:], np.float32)
 
 
 def pack_rays(orig, dirs, t_lo=0.0, t_hi=None) -> np.ndarray:
@@ -407,6 +432,54 @@ class Renderer:
                                               dptr, nd, pptr, npt, C.byref(dp), C.c_void_p(stream or 0)),
               "bih_render_lights_device")
 
+    def _light_set(self, dir_lights, point_lights, area_lights):
+        dl, pl, dptr, nd, pptr, npt = self._lights_args(dir_lights, point_lights)
+        al = pack_area_lights(area_lights if area_lights is not None else np.zeros((0, 10), np.float32))
+        ls = LightSet(dptr, nd, pptr, npt, C.c_void_p(al.ctypes.data if al.shape[0] else 0), al.shape[0])
+        return (dl, pl, al), ls   # (the arrays stay alive as long as the first element does)
+
+    def render_area_lights(self, dir_lights, point_lights, area_lights, frame: int | None = None,
+                           rows: Rows | None = None, planes=("lit", "irradiance", "rgba")) -> dict:
+        """render_lights with area lights (soft shadows) next to the others
+        (bih_render_area_lights; synchronous).  area_lights: an AREA_LIGHT_DTYPE
+        array or (k, 10) rows {corner, edge_u, edge_v, weight}, k <=
+        MAX_AREA_LIGHTS (scenes.panels makes two); any of the three may be None
+        or empty, together 1 .. MAX_LIGHTS.  Bit len(dir_lights) +
+        len(point_lights) + j of "lit" is area light j: per sample one shadow
+        ray to a point of the panel (area_light_sample)."""
+        f = self.frame if frame is None else frame
+        nrows = rows.nrows if rows is not None else self.h
+        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
+        out, dp = {}, Direct()
+        for name in planes:
+            dt, k = DIRECT_PLANES[name]
+            out[name] = np.zeros((nrows, self.w) if k else nrows * self.w * self.spp, dt)
+            setattr(dp, name, out[name].ctypes.data)
+        check(load().bih_render_area_lights(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
+                                            self.seed, C.byref(rows) if rows is not None else None,
+                                            C.byref(ls), C.byref(dp)), "bih_render_area_lights")
+        del keep
+        self.frame = f + 1
+        return out
+
+    def render_area_lights_device(self, ptrs: dict, dir_lights, point_lights, area_lights, frame: int,
+                                  rows: Rows | None = None, stream: int | None = None):
+        """Asynchronous render_area_lights into device memory
+        (bih_render_area_lights_device); ptrs as render_direct_device's.  The
+        light arrays are host memory, copied by the call."""
+        dp = Direct()
+        for name, ptr in ptrs.items():
+            if name not in DIRECT_PLANES:
+                raise KeyError(name)
+            setattr(dp, name, ptr or None)
+        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
+        check(load().bih_render_area_lights_device(self.arrays.handle, C.byref(self.camera), self.w, self.h,
+                                                   self.spp, frame, self.seed,
+                                                   C.byref(rows) if rows is not None else None,
+                                                   C.byref(ls), C.byref(dp), C.c_void_p(stream or 0)),
+              "bih_render_area_lights_device")
+        del keep
+
     def whitted_work(self) -> dict:
         """Per bounce d = 0..8 of the last Whitted render (run with
         PARAM_WHITTED_COUNTERS on): rays traced, BIH nodes entered, triangles
@@ -505,4 +578,5 @@ __all__ = ["GPUArrayManager", "Renderer", "Model", "load_obj", "host_register", 
            "PARAM_GBUFFER_MASK", "GBuffer", "GBUFFER_PLANES", "QUERY_CLOSEST", "QUERY_OCCLUDED", "NO_HIT", "Ray", "Hit", "RAY_DTYPE", "HIT_DTYPE", "pack_rays",
            "Light", "Direct", "LIGHT_DTYPE", "DIRECT_PLANES", "MAX_LIGHTS", "SHADOW_T_LO", "pack_lights",
            "QUERY_T_HI", "QUERY_CLOSEST_WITHIN", "QUERY_OCCLUDED_WITHIN", "PointLight", "POINT_LIGHT_DTYPE",
-           "pack_point_lights"]
+           "pack_point_lights", "AreaLight", "LightSet", "AREA_LIGHT_DTYPE", "MAX_AREA_LIGHTS",
+           "pack_area_lights", "area_light_sample"]

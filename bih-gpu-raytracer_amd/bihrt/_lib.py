@@ -38,6 +38,10 @@ MAX_LIGHTS = 64           # bih_render_direct*: one bit each of a sample's lit w
 LIGHT_DTYPE = np.dtype([("dir", np.float32, 3), ("weight", np.float32)])   # numpy view of a bih_light array
 POINT_LIGHT_DTYPE = np.dtype([("pos", np.float32, 3), ("weight", np.float32)])   # ... of a bih_point_light array
 SHADOW_T_LO = 1e-4        # BIH_SHADOW_T_LO
+MAX_AREA_LIGHTS = 16      # bih_render_area_lights*: area lights of one call
+AREA_LIGHT_DTYPE = np.dtype([("corner", np.float32, 3), ("weight", np.float32),       # numpy view of a
+                             ("edge_u", np.float32, 3), ("reserved0", np.float32),    # bih_area_light array
+                             ("edge_v", np.float32, 3), ("reserved1", np.float32)])
 (ARR_MORTON_SORTED, ARR_TRI_INDEX, ARR_UNIQUE_MC, ARR_DUP_COUNT, ARR_FIRST_IDX, ARR_LEAF_PARENT,
  ARR_CLIP, ARR_AXIS, ARR_CHILDREN, ARR_IS_LEAF, ARR_PARENT, ARR_TRI_LO, ARR_TRI_HI) = range(13)
 
@@ -110,6 +114,19 @@ class Light(C.Structure):
 class PointLight(C.Structure):
     """bih_point_light (16 bytes): a lamp at pos."""
     _fields_ = [("pos", C.c_float * 3), ("weight", C.c_float)]
+
+
+class AreaLight(C.Structure):
+    """bih_area_light (48 bytes): a parallelogram corner + a*edge_u + b*edge_v that
+    emits to the side cross(edge_u, edge_v) points to; weight = its radiance."""
+    _fields_ = [("corner", C.c_float * 3), ("weight", C.c_float), ("edge_u", C.c_float * 3),
+                ("reserved0", C.c_float), ("edge_v", C.c_float * 3), ("reserved1", C.c_float)]
+
+
+class LightSet(C.Structure):
+    """bih_light_set: the three light arrays of bih_render_area_lights* (host memory)."""
+    _fields_ = [("dir", C.c_void_p), ("n_dir", C.c_uint32), ("point", C.c_void_p), ("n_point", C.c_uint32),
+                ("area", C.c_void_p), ("n_area", C.c_uint32)]
 
 
 class Direct(C.Structure):
@@ -206,6 +223,11 @@ def load():
                                            vp, u32, vp, u32, C.POINTER(Direct), vp]
     L.bih_render_lights.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
                                     vp, u32, vp, u32, C.POINTER(Direct)]
+    L.bih_render_area_lights_device.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                                C.POINTER(LightSet), C.POINTER(Direct), vp]
+    L.bih_render_area_lights.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                         C.POINTER(LightSet), C.POINTER(Direct)]
+    L.bih_area_light_sample.argtypes = [vp, u32, u64, u32, u32, u32, u32, C.POINTER(C.c_float)]
     for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
@@ -213,7 +235,8 @@ def load():
                  "bih_bins_get_stats", "bih_reserve", "bih_tree_set_param", "bih_whitted_work",
                  "bih_host_register", "bih_host_unregister", "bih_render_history", "bih_trace_device", "bih_trace",
                  "bih_render_gbuffer_device", "bih_render_gbuffer", "bih_render_direct_device", "bih_render_direct",
-                 "bih_render_lights_device", "bih_render_lights"):
+                 "bih_render_lights_device", "bih_render_lights", "bih_render_area_lights_device",
+                 "bih_render_area_lights", "bih_area_light_sample"):
         getattr(L, name).restype = i32
     _lib = L
     return L

@@ -17,6 +17,7 @@ usage:  python -m bihrt --mesh sponza --resources path/to/resources --frames 10 
             [--gbuffer frames/g%04d.npz]   (depth, prim, bary, normal, coverage per written frame)
             [--direct frames/d%04d.ppm [--sun X,Y,Z] [--sky K]]   (sky- and sun-lit grey preview per written frame)
                      [--lamp X,Y,Z[,W]]...            (point lights next to them; --sky 0: lamps only)
+                     [--panel CX,CY,CZ,UX,UY,UZ,VX,VY,VZ[,W]]...   (area lights: soft shadows)
         python -m bihrt --obj file.obj ...     (explicit path)
         python -m bihrt --scene cornell|torus|soup[:N] ...   (built-in scenes)
 """
@@ -74,14 +75,16 @@ class App:
 
     def run(self, frames: int, out_pattern: str | None = None, rebuild: bool = True,
             every: int = 1, gbuffer_pattern: str | None = None, direct_pattern: str | None = None,
-            lights=None, lamps=None):
+            lights=None, lamps=None, panels=None):
         """App::Run for a fixed number of frames: Renderer::Render each frame
         (BIH rebuild + render), optional PPM output; returns the frames.
         gbuffer_pattern: one .npz of the frame's G-buffer planes
         (Renderer.render_gbuffer) per written frame.  direct_pattern: one PPM
         of the frame's direct lighting under `lights` (Renderer.render_direct's
         rgba plane) per written frame; lights = None: scenes.sky_dome(8).
-        lamps: point lights {pos, weight} next to them (Renderer.render_lights)."""
+        lamps: point lights {pos, weight} next to them (Renderer.render_lights).
+        panels: area lights, (k, 10) rows {corner, edge_u, edge_v, weight}, next
+        to both (Renderer.render_area_lights)."""
         assert self.renderer is not None, "load_models first"
         if direct_pattern and lights is None:
             lights = scenes.sky_dome(8)
@@ -112,7 +115,9 @@ class App:
                 d = os.path.dirname(path)
                 if d:
                     os.makedirs(d, exist_ok=True)
-                if lamps is not None and len(lamps):
+                if panels is not None and len(panels):
+                    shade = self.renderer.render_area_lights(lights, lamps, panels, f, planes=("rgba",))["rgba"]
+                elif lamps is not None and len(lamps):
                     shade = self.renderer.render_lights(lights, lamps, f, planes=("rgba",))["rgba"]
                 else:
                     shade = self.renderer.render_direct(lights, f, planes=("rgba",))["rgba"]
@@ -142,6 +147,9 @@ def main(argv=None) -> int:
     ap.add_argument("--sky", type=int, default=None, metavar="K", help="--direct: sky directions (default 8; 0: none)")
     ap.add_argument("--lamp", action="append", default=None, metavar="X,Y,Z[,W]",
                     help="--direct: a point light at X,Y,Z of weight W (default 1); repeatable")
+    ap.add_argument("--panel", action="append", default=None, metavar="CX,CY,CZ,UX,UY,UZ,VX,VY,VZ[,W]",
+                    help="--direct: an area light corner + a*U + b*V of radiance W (default 1) that emits to the "
+                         "side cross(U, V) points to; repeatable, up to 16")
     ap.add_argument("--every", type=int, default=1, help="write every k-th frame")
     ap.add_argument("--no-rebuild", action="store_true",
                     help="build once (the reference rebuilds every frame)")
@@ -159,6 +167,9 @@ def main(argv=None) -> int:
         scene = builtin_scene(a.scene)
     lights = None
     lamps = None
+    panels = None
+    if not a.direct and a.panel:
+        ap.error("--panel belongs to --direct")
     if not a.direct and (a.sun is not None or a.sky is not None):
         ap.error("--sun and --sky belong to --direct")
     if not a.direct and a.lamp:
@@ -179,10 +190,24 @@ def main(argv=None) -> int:
                     ap.error("--lamp takes X,Y,Z[,W]")
                 rows.append(v + [1.0] if len(v) == 3 else v)
             lamps = np.array(rows, np.float32)
+        if a.panel:
+            rows = []
+            for spec in a.panel:
+                try:
+                    v = [float(x) for x in spec.split(",")]
+                except ValueError:
+                    v = []
+                if len(v) not in (9, 10):
+                    ap.error("--panel takes CX,CY,CZ,UX,UY,UZ,VX,VY,VZ[,W]")
+                rows.append(v + [1.0] if len(v) == 9 else v)
+            if len(rows) > 16:
+                ap.error("--direct takes up to 16 panels")
+            panels = np.array(rows, np.float32)
         n_lamps = 0 if lamps is None else lamps.shape[0]
+        n_panels = 0 if panels is None else panels.shape[0]
         n_dir = a.sky + (sun is not None)
-        if a.sky < 0 or n_dir + n_lamps > 64 or n_dir + n_lamps == 0:
-            ap.error("--direct needs 1..64 lights (--sky K, --sun, --lamp)" if n_lamps else
+        if a.sky < 0 or n_dir + n_lamps + n_panels > 64 or n_dir + n_lamps + n_panels == 0:
+            ap.error("--direct needs 1..64 lights (--sky K, --sun, --lamp, --panel)" if n_lamps or n_panels else
                      "--direct needs 1..64 lights (--sky K, --sun)")
         if a.sky:
             lights = scenes.sky_dome(a.sky, sun)
@@ -193,5 +218,5 @@ def main(argv=None) -> int:
     app = App(a.width, a.height, a.spp, device=a.device)
     app.load_models(scene)
     app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every, gbuffer_pattern=a.gbuffer,
-            direct_pattern=a.direct, lights=lights, lamps=lamps)
+            direct_pattern=a.direct, lights=lights, lamps=lamps, panels=panels)
     return 0

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import LIGHT_DTYPE, POINT_LIGHT_DTYPE
+from ._lib import AREA_LIGHT_DTYPE, LIGHT_DTYPE, POINT_LIGHT_DTYPE
 
 _GOLD = np.uint64(0x9E3779B97F4A7C15)
 
@@ -258,3 +258,37 @@ def lamps(lo, hi, k: int, scale: float = 0.6, weight=None) -> np.ndarray:
     out[:, :3] = centre + scale * half * u
     out[:, 3] = float(half @ half) / k if weight is None else float(weight)
     return np.ascontiguousarray(out, np.float32).view(POINT_LIGHT_DTYPE).reshape(-1)
+
+
+def _panel_rows(rows) -> np.ndarray:
+    out = np.zeros(len(rows), AREA_LIGHT_DTYPE)
+    for k, (corner, u, v, w) in enumerate(rows):
+        out[k]["corner"], out[k]["edge_u"], out[k]["edge_v"] = corner, u, v
+        out[k]["weight"] = w
+    return out
+
+
+def panels(lo, hi, weight=None) -> np.ndarray:
+    """Area lights for Renderer.render_area_lights: two horizontal panels
+    inside the box [lo, hi] of centre c and half extent h, as (2,) float32
+    records (bihrt.AREA_LIGHT_DTYPE); computed in f64, then rounded.  The first
+    {c - (0.3hx, -0.2hy, 0.3hz), U = (0.6hx, 0, 0), V = (0, 0, 0.6hz)} lies above
+    the centre and faces down (cross(U, V) points to -y); the second
+    {c - (0.3hx, 0.2hy, 0.3hz), U = (0, 0, 0.6hz), V = (0.6hx, 0, 0)} lies below
+    it and faces up.  weight: each panel's radiance; default |h|^2 / area, which
+    makes a surface that faces a panel from about a half-diagonal away get the
+    order of 1."""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    c, h = (lo + hi) / 2.0, (hi - lo) / 2.0
+    area = 0.36 * h[0] * h[2]
+    w = (float(h @ h) / area if area > 0 else 0.0) if weight is None else float(weight)
+    eu, ev = np.array([0.6 * h[0], 0.0, 0.0]), np.array([0.0, 0.0, 0.6 * h[2]])
+    return _panel_rows([(c - np.array([0.3 * h[0], -0.2 * h[1], 0.3 * h[2]]), eu, ev, w),
+                        (c - np.array([0.3 * h[0], 0.2 * h[1], 0.3 * h[2]]), ev, eu, w)])
+
+
+def cornell_panel(weight: float = 1.0) -> np.ndarray:
+    """cornell()'s ceiling lamp as an area light: the lamp quad's outline one
+    centimetre below it (geometry coincident with a panel may or may not shadow
+    it), facing down; (1,) bihrt.AREA_LIGHT_DTYPE."""
+    return _panel_rows([((0.1, 0.98, 1.0), (0.6, 0.0, 0.0), (0.0, 0.0, 0.6), weight)])

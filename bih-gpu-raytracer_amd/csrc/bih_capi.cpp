@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/bih.h"
+#include "bih_area.h"
 #include "bih_internal.h"
 
 // Up to kSlots renders through one tree may be in flight together (issued
@@ -2258,6 +2259,7 @@ struct DirectJob {
     const float *lights;    // n_lights x 4 floats: n_dir bih_light, then bih_point_light
     uint32_t n_lights, n_dir;
     bih_direct planes;
+    const bih::AreaLights *area = nullptr;   // the last area->n lights are area lights (else null)
 };
 
 // bih_render_gbuffer_device under the tree's lock, arguments checked, nrows > 0.
@@ -2375,7 +2377,7 @@ static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
                                 reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
                                 tr->prm.trace_lds, tr->tq_cursor + 4,
                                 reinterpret_cast<unsigned long long *>(tr->tq_cursor + 2), tr->tq_spill,
-                                tr->tq_blocks, st);
+                                tr->tq_blocks, st, dj->area);
     }
     // (a failed launch may have left work on st that uses the cursor: the event covers it)
     e = hipEventRecord(tr->ev_trace, st);
@@ -2481,7 +2483,7 @@ static int direct_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, u
 // lights: n_lights x 4 floats, the first n_dir directional, the rest point lights.
 static int direct_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t frame,
                          uint64_t seed, const bih_rows &rows, const float *lights, uint32_t n_lights, uint32_t n_dir,
-                         const bih_direct &pl, void *stream) {
+                         const bih_direct &pl, void *stream, const bih::AreaLights *area = nullptr) {
     const size_t S = (size_t)rows.nrows * w * spp;
     const bool own_lit = !pl.lit && tr->dr_lit_cap < S;
     if ((tr->dr_cap < S || own_lit) && tr->trace_used) {
@@ -2509,7 +2511,7 @@ static int direct_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32
     static_assert(sizeof(bih_point_light) == 16, "bih_point_light shares bih_light's slots");
     bih_gbuffer g = {};
     g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
-    const DirectJob dj{lights, n_lights, n_dir, pl};
+    const DirectJob dj{lights, n_lights, n_dir, pl, area};
     return gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, g, stream, &dj);
 }
 
@@ -2530,7 +2532,8 @@ int bih_render_direct_device(const bih_tree *ctr, const bih_camera *cam, uint32_
 // checked, nrows > 0: direct_locked into device planes, copied to the host's.
 static int direct_host_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                               uint32_t frame, uint64_t seed, const bih_rows &rows, const float *lights,
-                              uint32_t n_lights, uint32_t n_dir, const bih_direct *host_planes) {
+                              uint32_t n_lights, uint32_t n_dir, const bih_direct *host_planes,
+                              const bih::AreaLights *area = nullptr) {
     int rc;
     // device planes of the ones asked for, each at a multiple of 16 bytes
     const size_t P = (size_t)rows.nrows * w;
@@ -2555,7 +2558,7 @@ static int direct_host_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, u
     d.lit = static_cast<uint64_t *>(dev_plane(0));
     d.irradiance = static_cast<float *>(dev_plane(1));
     d.rgba = static_cast<uint32_t *>(dev_plane(2));
-    rc = direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_lights, n_dir, d, nullptr);
+    rc = direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_lights, n_dir, d, nullptr, area);
     hipError_t e = hipSuccess;
     for (int k = 0; k < 3 && rc == BIH_OK; ++k)
         if (host[k]) {
@@ -2634,6 +2637,92 @@ int bih_render_lights(const bih_tree *ctr, const bih_camera *cam, uint32_t w, ui
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
     return direct_host_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_dir + n_point, n_dir, host_planes);
+}
+
+// Argument checks of both bih_render_area_lights entries: lights_check's, its
+// light checks replaced (the header's order); none touches the tree or a device.
+static int area_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                      const bih_rows *rows_in, const bih_light_set *ls, const bih_direct *pl, bih_rows *rows) {
+    static float some_plane;
+    bih_gbuffer g = {};
+    if (pl && (pl->lit || pl->irradiance || pl->rgba)) g.depth = &some_plane;
+    const int rc = gbuffer_check(tr, cam, w, h, spp, rows_in, pl ? &g : nullptr, rows);
+    if (rc) return rc;
+    if (!ls) return BIH_ERR_INVALID;
+    const uint64_t n = (uint64_t)ls->n_dir + ls->n_point + ls->n_area;
+    if (n == 0 || n > BIH_MAX_LIGHTS) return BIH_ERR_INVALID;
+    if (ls->n_area > BIH_MAX_AREA_LIGHTS) return BIH_ERR_INVALID;
+    if ((ls->n_dir && !ls->dir) || (ls->n_point && !ls->point) || (ls->n_area && !ls->area)) return BIH_ERR_INVALID;
+    if ((uintptr_t)pl->lit & 7u) return BIH_ERR_INVALID;   // the lit words take 64-bit atomics
+    return BIH_OK;
+}
+
+// nl = cross(U, V) in the header's order, every operation separately rounded.
+static void area_normal(const float *u, const float *v, float *nl) {
+    nl[0] = u[1] * v[2] - v[1] * u[2];
+    nl[1] = u[2] * v[0] - v[2] * u[0];
+    nl[2] = u[0] * v[1] - v[0] * u[1];
+}
+
+// The call's lights in the kernels' slot order: directional, point, then the
+// area lights' {corner, weight}; *al: what else the area kernels need.
+static void merge_light_set(const bih_light_set *ls, uint32_t spp, uint32_t frame, uint64_t seed, float *out,
+                            bih::AreaLights *al) {
+    static_assert(sizeof(bih_area_light) == 48 && BIH_MAX_AREA_LIGHTS == bih::kMaxAreaLights,
+                  "bih_area_light / kMaxAreaLights");
+    merge_lights(ls->dir, ls->n_dir, ls->point, ls->n_point, out);
+    float *slot = out + 4 * ((size_t)ls->n_dir + ls->n_point);
+    al->n = ls->n_area;
+    al->hseed = bih::area_seed_hash(seed);
+    al->fs0 = frame * spp;
+    for (uint32_t j = 0; j < ls->n_area; ++j) {
+        const bih_area_light &a = ls->area[j];
+        memcpy(slot + 4 * j, a.corner, 3 * sizeof(float));
+        slot[4 * j + 3] = a.weight;
+        memcpy(al->uvn[j], a.edge_u, 3 * sizeof(float));
+        memcpy(al->uvn[j] + 3, a.edge_v, 3 * sizeof(float));
+        area_normal(a.edge_u, a.edge_v, al->uvn[j] + 6);
+    }
+}
+
+int bih_render_area_lights_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                                  uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light_set *ls,
+                                  const bih_direct *d_planes, void *stream) {
+    bih_rows rows;
+    const int rc = area_check(ctr, cam, w, h, spp, rows_in, ls, d_planes, &rows);
+    if (rc || rows.nrows == 0) return rc;
+    float lights[4 * BIH_MAX_LIGHTS];
+    bih::AreaLights al;
+    merge_light_set(ls, spp, frame, seed, lights, &al);
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    return direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, ls->n_dir + ls->n_point + ls->n_area,
+                         ls->n_dir, *d_planes, stream, al.n ? &al : nullptr);
+}
+
+int bih_render_area_lights(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                           uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light_set *ls,
+                           const bih_direct *host_planes) {
+    bih_rows rows;
+    const int rc = area_check(ctr, cam, w, h, spp, rows_in, ls, host_planes, &rows);
+    if (rc || rows.nrows == 0) return rc;
+    float lights[4 * BIH_MAX_LIGHTS];
+    bih::AreaLights al;
+    merge_light_set(ls, spp, frame, seed, lights, &al);
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    return direct_host_locked(tr, cam, w, h, spp, frame, seed, rows, lights,
+                              ls->n_dir + ls->n_point + ls->n_area, ls->n_dir, host_planes, al.n ? &al : nullptr);
+}
+
+int bih_area_light_sample(const bih_area_light *light, uint32_t j, uint64_t seed, uint32_t pixel, uint32_t frame,
+                          uint32_t spp, uint32_t s, float q[3]) {
+    if (!light || !q || spp == 0 || s >= spp) return BIH_ERR_INVALID;
+    bih::area_point(bih::area_seed_hash(seed), pixel, frame * spp + s, j, light->corner, light->edge_u,
+                    light->edge_v, q);
+    return BIH_OK;
 }
 
 int bih_sync(const bih_tree *tr, void *stream) {

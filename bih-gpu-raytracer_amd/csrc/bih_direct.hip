@@ -37,10 +37,19 @@
 // same bits of P in all three; its shadow ray is a segment query (t_hi = 1:
 // a triangle at or beyond the lamp does not shadow), the walk bih_closest.h's
 // kWalkWithin, a directional item riding along with t_hi = +inf.
+//
+// Area lights (bih_render_area_lights*, n_area > 0) take the last slots and a
+// third instantiation (k_area_setup, k_shadow_area, k_area_resolve) with an
+// argument block of their own (AArgs: DArgs plus the panels); calls without
+// one launch the kernels above with DArgs, unchanged.  An area light is a lamp
+// whose position Q differs per sample: Q is bih_area.h's hash of (seed, global
+// pixel, frame*spp + s, light), recomputed from the item's sample index in all
+// three kernels (area_dir), so a lane's walk state stays SRay's {o, d, i, k}.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stddef.h>
 
+#include "bih_area.h"
 #include "bih_closest.h"
 #include "bih_internal.h"
 #include "bih_primary.h"
@@ -94,9 +103,46 @@ struct DArgs {
     DLight lights[kMaxLights];
 };
 
-// POINT (compile time): the call has point lights (a.n_dir < a.n_lights).
-template <bool POINT>
-__device__ __forceinline__ void direct_setup_body(const DArgs &a) {
+// The kernels' instantiations: what kinds of light the call has.
+constexpr int kDir = 0;     // directional only (bih_render_direct's kernels)
+constexpr int kPoint = 1;   // point lights too (a.n_dir < a.n_lights)
+constexpr int kArea = 2;    // area lights too (ax.n_area > 0)
+
+struct APanel { float u[3], v[3], nl[3]; };   // edges; nl = cross(u, v) in the header's order (host, f32)
+
+// The area kernels' argument block.  Slots [d.n_lights - n_area, d.n_lights)
+// of d.lights are area lights {corner, weight}, the point lights end before.
+struct AArgs {
+    DArgs d;
+    uint32_t n_area;
+    uint32_t hseed;             // area_seed_hash(seed)
+    uint32_t fs0;               // frame * spp (wrapping)
+    APanel panel[kMaxAreaLights];
+};
+
+// Sample i of the call's rows: its global pixel y*w + x (y the global row) and s.
+__device__ __forceinline__ uint32_t sample_pixel(const DArgs &a, uint32_t i, uint32_t *s) {
+    const uint32_t lp = i / a.spp;
+    *s = i - lp * a.spp;
+    const uint32_t lr = lp / a.w, x = lp - lr * a.w;
+    return dev::global_row(lr, a.row0, a.band_h, a.band_step) * a.w + x;
+}
+
+// Area light j's L = Q - P for sample s of global pixel gp: as lamp_dir, one
+// expression for all three kernels (q: the light's slot, {corner, weight}).
+__device__ __forceinline__ void area_dir(const AArgs &ax, uint32_t j, const DLight &q, uint32_t gp, uint32_t s,
+                                         const float *p, float *l) {
+    const float c[3] = {q.x, q.y, q.z};
+    float pt[3];
+    area_point(ax.hseed, gp, ax.fs0 + s, j, c, ax.panel[j].u, ax.panel[j].v, pt);
+    l[0] = pt[0] - p[0];
+    l[1] = pt[1] - p[1];
+    l[2] = pt[2] - p[2];
+}
+
+// KIND (compile time): kDir, kPoint or kArea; ax: the area lights (kArea only).
+template <int KIND>
+__device__ __forceinline__ void direct_setup_body(const DArgs &a, const AArgs *ax) {
     const uint64_t P = (uint64_t)a.nrows * a.w;
     const uint64_t n = P * a.spp;
     const uint64_t i = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
@@ -116,17 +162,29 @@ __device__ __forceinline__ void direct_setup_body(const DArgs &a) {
             const float t = __uint_as_float(h.x);
             for (int k = 0; k < 3; ++k) pt[k] = a.cam[k] + t * d[k];
             dev::tri_normal(a.tris + 9ull * bi, nrm);
-            const uint32_t n_dir = POINT ? a.n_dir : a.n_lights;
+            const uint32_t n_dir = KIND != kDir ? a.n_dir : a.n_lights;
             for (uint32_t k = 0; k < n_dir; ++k) {   // (k is uniform: the lights come as scalars)
                 const float c = (nrm[0] * a.lights[k].x + nrm[1] * a.lights[k].y) + nrm[2] * a.lights[k].z;
                 if (c > 0.0f) face |= 1ull << k;
             }
-            if (POINT) {
-                for (uint32_t k = n_dir; k < a.n_lights; ++k) {
+            if (KIND != kDir) {
+                const uint32_t n_lamp = KIND == kArea ? a.n_lights - ax->n_area : a.n_lights;
+                for (uint32_t k = n_dir; k < n_lamp; ++k) {
                     float l[3];
                     lamp_dir(a.lights[k], pt, l);
                     const float c = (nrm[0] * l[0] + nrm[1] * l[1]) + nrm[2] * l[2];
                     if (c > 0.0f) face |= 1ull << k;
+                }
+            }
+            if (KIND == kArea) {
+                const uint32_t k0 = a.n_lights - ax->n_area, gp = y * a.w + x;
+                for (uint32_t j = 0; j < ax->n_area; ++j) {
+                    float l[3];
+                    area_dir(*ax, j, a.lights[k0 + j], gp, s, pt, l);
+                    const float *nl = ax->panel[j].nl;
+                    const float c = (nrm[0] * l[0] + nrm[1] * l[1]) + nrm[2] * l[2];
+                    const float g = -((nl[0] * l[0] + nl[1] * l[1]) + nl[2] * l[2]);
+                    if (c > 0.0f && g > 0.0f) face |= 1ull << (k0 + j);   // it faces the panel's emitting side
                 }
             }
         }
@@ -148,8 +206,9 @@ __device__ __forceinline__ void direct_setup_body(const DArgs &a) {
     }
 }
 
-__global__ void __launch_bounds__(kDSetupT) k_direct_setup(const DArgs a) { direct_setup_body<false>(a); }
-__global__ void __launch_bounds__(kDSetupT) k_lights_setup(const DArgs a) { direct_setup_body<true>(a); }
+__global__ void __launch_bounds__(kDSetupT) k_direct_setup(const DArgs a) { direct_setup_body<kDir>(a, nullptr); }
+__global__ void __launch_bounds__(kDSetupT) k_lights_setup(const DArgs a) { direct_setup_body<kPoint>(a, nullptr); }
+__global__ void __launch_bounds__(kDSetupT) k_area_setup(const AArgs a) { direct_setup_body<kArea>(a.d, &a); }
 
 // A work item: where its ray starts, whose bit it decides, and its walk.
 struct SRay {
@@ -158,21 +217,25 @@ struct SRay {
     ClosestRay w;
 };
 
-// POINT: the item's ray is a segment (within_hit: hit below its t_hi).
-template <bool POINT>
+// SEG: the item's ray is a segment (within_hit: hit below its t_hi).
+template <bool SEG>
 __device__ __forceinline__ void sray_write(const DArgs &a, const SRay &r) {
-    const bool occluded = POINT ? dev::within_hit(r.w) : r.w.bi != kNoHit;
+    const bool occluded = SEG ? dev::within_hit(r.w) : r.w.bi != kNoHit;
     if (!occluded) atomicOr(a.lit + r.i, 1ull << r.k);
 }
 
 // The shadow kernels' body.  LDS: stack slots per lane kept in LDS (the rest
 // in this thread's HBM area; s_node, s_min, s_max: LDS * kDT words each).
-// POINT (compile time): the call has point lights.  An item then carries its
-// own t_hi -- 1.0f for a lamp (it sits at t = 1 of d = Q - P), +inf for a
-// directional light -- and the walk is kWalkWithin, which with t_hi = +inf is
-// exactly the ANY walk (every accepted t is below FLT_MAX).
-template <int LDS, bool POINT>
-__device__ __forceinline__ void shadow_body(const DArgs &a, uint32_t *s_node, float *s_min, float *s_max) {
+// KIND (compile time) kPoint or kArea: the call has point or area lights.  An
+// item then carries its own t_hi -- 1.0f for a lamp or an area light's point
+// (it sits at t = 1 of d = Q - P), +inf for a directional light -- and the
+// walk is kWalkWithin, which with t_hi = +inf is exactly the ANY walk (every
+// accepted t is below FLT_MAX).  An area item's Q is recomputed here from its
+// sample index: past the fetch it is a lamp item.
+template <int LDS, int KIND>
+__device__ __forceinline__ void shadow_body(const DArgs &a, const AArgs *ax, uint32_t *s_node, float *s_min,
+                                            float *s_max) {
+    constexpr bool POINT = KIND != kDir;
     constexpr int MODE = POINT ? dev::kWalkWithin : dev::kWalkAny;
     const uint32_t lane = threadIdx.x;
     const dev::LaneStack<LDS> stk(s_node, s_min, s_max, a.spill);
@@ -213,7 +276,13 @@ __device__ __forceinline__ void shadow_body(const DArgs &a, uint32_t *s_node, fl
                     if (POINT) {
                         r.w.t_hi = __builtin_inff();
                         if (k >= a.n_dir) {
-                            lamp_dir(l, r.o, r.w.d);
+                            if (KIND == kArea && k >= a.n_lights - ax->n_area) {
+                                uint32_t s;
+                                const uint32_t gp = sample_pixel(a, r.i, &s);
+                                area_dir(*ax, k - (a.n_lights - ax->n_area), l, gp, s, r.o, r.w.d);
+                            } else {
+                                lamp_dir(l, r.o, r.w.d);
+                            }
                             r.w.t_hi = 1.0f;
                         }
                     }
@@ -243,7 +312,7 @@ __global__ void __launch_bounds__(kDT) k_shadow(const DArgs a) {
     __shared__ uint32_t s_node[LDS * kDT];
     __shared__ float s_min[LDS * kDT];
     __shared__ float s_max[LDS * kDT];
-    shadow_body<LDS, false>(a, s_node, s_min, s_max);
+    shadow_body<LDS, kDir>(a, nullptr, s_node, s_min, s_max);
 }
 
 // bih_render_lights* with point lights: the same LDS per block.
@@ -252,11 +321,21 @@ __global__ void __launch_bounds__(kDT) k_shadow_lights(const DArgs a) {
     __shared__ uint32_t s_node[LDS * kDT];
     __shared__ float s_min[LDS * kDT];
     __shared__ float s_max[LDS * kDT];
-    shadow_body<LDS, true>(a, s_node, s_min, s_max);
+    shadow_body<LDS, kPoint>(a, nullptr, s_node, s_min, s_max);
 }
 
-template <bool POINT>
-__device__ __forceinline__ void direct_resolve_body(const DArgs &a, DLight *s_light) {
+// bih_render_area_lights* with area lights: the same LDS per block.
+template <int LDS>
+__global__ void __launch_bounds__(kDT) k_shadow_area(const AArgs a) {
+    __shared__ uint32_t s_node[LDS * kDT];
+    __shared__ float s_min[LDS * kDT];
+    __shared__ float s_max[LDS * kDT];
+    shadow_body<LDS, kArea>(a.d, &a, s_node, s_min, s_max);
+}
+
+template <int KIND>
+__device__ __forceinline__ void direct_resolve_body(const DArgs &a, const AArgs *ax, DLight *s_light) {
+    constexpr bool POINT = KIND != kDir;
     if (threadIdx.x < a.n_lights) s_light[threadIdx.x] = a.lights[threadIdx.x];
     __syncthreads();
     const uint64_t P = (uint64_t)a.nrows * a.w;
@@ -264,6 +343,11 @@ __device__ __forceinline__ void direct_resolve_body(const DArgs &a, DLight *s_li
     if (lp >= P) return;
     float E = 0.0f;
     bool any = false;
+    uint32_t gp = 0;   // (kArea) the global pixel
+    if (KIND == kArea) {
+        const uint32_t lr = (uint32_t)(lp / a.w), px = (uint32_t)(lp - (uint64_t)lr * a.w);
+        gp = dev::global_row(lr, a.row0, a.band_h, a.band_step) * a.w + px;
+    }
     for (uint32_t s = 0; s < a.spp; ++s) {
         const uint64_t i = lp * a.spp + s;
         const uint32_t bi = a.rec[i].w;
@@ -281,11 +365,19 @@ __device__ __forceinline__ void direct_resolve_body(const DArgs &a, DLight *s_li
                     const uint4 rec = a.rec[i];   // (a lit sample is a listed one: rec.xyz = P)
                     const float pt[3] = {__uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z)};
                     float L[3];
-                    lamp_dir(q, pt, L);
+                    const bool area = KIND == kArea && k >= a.n_lights - ax->n_area;
+                    if (area) area_dir(*ax, k - (a.n_lights - ax->n_area), q, gp, s, pt, L);
+                    else lamp_dir(q, pt, L);
                     const float c = (nrm[0] * L[0] + nrm[1] * L[1]) + nrm[2] * L[2];
                     const float r2 = (L[0] * L[0] + L[1] * L[1]) + L[2] * L[2];
                     const float len = sqrtf(r2);
-                    e = e + (q.w * (c / len)) / r2;
+                    if (area) {   // the emitter's own cosine times its area: g = -(nl . L)
+                        const float *nl = ax->panel[k - (a.n_lights - ax->n_area)].nl;
+                        const float g = -((nl[0] * L[0] + nl[1] * L[1]) + nl[2] * L[2]);
+                        e = e + ((q.w * (c / len)) * (g / len)) / r2;
+                    } else {
+                        e = e + (q.w * (c / len)) / r2;
+                    }
                 } else {
                     const float c = (nrm[0] * q.x + nrm[1] * q.y) + nrm[2] * q.z;
                     e = e + q.w * c;
@@ -304,26 +396,35 @@ __device__ __forceinline__ void direct_resolve_body(const DArgs &a, DLight *s_li
 
 __global__ void __launch_bounds__(kDSetupT) k_direct_resolve(const DArgs a) {
     __shared__ DLight s_light[kMaxLights];
-    direct_resolve_body<false>(a, s_light);
+    direct_resolve_body<kDir>(a, nullptr, s_light);
 }
 
 __global__ void __launch_bounds__(kDSetupT) k_lights_resolve(const DArgs a) {
     __shared__ DLight s_light[kMaxLights];
-    direct_resolve_body<true>(a, s_light);
+    direct_resolve_body<kPoint>(a, nullptr, s_light);
+}
+
+__global__ void __launch_bounds__(kDSetupT) k_area_resolve(const AArgs a) {
+    __shared__ DLight s_light[kMaxLights];
+    direct_resolve_body<kArea>(a.d, &a, s_light);
 }
 
 }  // namespace
 
 int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes &p, const float *lights,
                   uint32_t n_lights, uint32_t n_dir, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
-                  uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream) {
+                  uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream,
+                  const AreaLights *area) {
     const hipStream_t st = (hipStream_t)stream;
     if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0 || n_lights == 0) return 0;
     if (n_lights > kMaxLights || n_dir > n_lights) return (int)hipErrorInvalidValue;
+    const uint32_t n_area = area ? area->n : 0u;
+    if (n_area > kMaxAreaLights || n_area > n_lights - n_dir) return (int)hipErrorInvalidValue;
     static_assert(offsetof(DArgs, n_dir) + 4 == offsetof(DArgs, hdr) && offsetof(DArgs, n_dir) % 8 == 4,
                   "n_dir sits in what was padding before the pointers: the argument block has not grown");
     const bool point = n_dir < n_lights;   // else: bih_render_direct's kernels
-    DArgs a;
+    AArgs aa;                              // (n_area == 0: only its DArgs is filled and passed on)
+    DArgs &a = aa.d;
     for (int k = 0; k < 12; ++k) a.cam[k] = ra.cam[k];
     a.w = ra.w;
     a.h = ra.h;
@@ -354,12 +455,24 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
         a.lights[k] = DLight{on ? lights[4 * k] : 0.0f, on ? lights[4 * k + 1] : 0.0f, on ? lights[4 * k + 2] : 0.0f,
                              on ? lights[4 * k + 3] : 0.0f};
     }
+    if (n_area) {
+        aa.n_area = n_area;
+        aa.hseed = area->hseed;
+        aa.fs0 = area->fs0;
+        for (uint32_t j = 0; j < kMaxAreaLights; ++j)
+            for (int c = 0; c < 3; ++c) {
+                aa.panel[j].u[c] = j < n_area ? area->uvn[j][c] : 0.0f;
+                aa.panel[j].v[c] = j < n_area ? area->uvn[j][3 + c] : 0.0f;
+                aa.panel[j].nl[c] = j < n_area ? area->uvn[j][6 + c] : 0.0f;
+            }
+    }
     hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), st);
     if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return (int)e;
     const uint64_t P = (uint64_t)ra.nrows * ra.w, n = P * ra.spp;
     const dim3 sgrid((uint32_t)((n + kDSetupT - 1) / kDSetupT));
-    if (point) hipLaunchKernelGGL(k_lights_setup, sgrid, dim3(kDSetupT), 0, st, a);
+    if (n_area) hipLaunchKernelGGL(k_area_setup, sgrid, dim3(kDSetupT), 0, st, aa);
+    else if (point) hipLaunchKernelGGL(k_lights_setup, sgrid, dim3(kDSetupT), 0, st, a);
     else hipLaunchKernelGGL(k_direct_setup, sgrid, dim3(kDSetupT), 0, st, a);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
@@ -367,7 +480,9 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
     const uint64_t need = (n * n_lights + kDT - 1) / kDT;
     const dim3 grid((uint32_t)(need < max_blocks ? need : max_blocks)), block(kDT);
     const bool small = lds_slots == (uint32_t)kTraceLdsTest;
-    if (point && small) hipLaunchKernelGGL((k_shadow_lights<kTraceLdsTest>), grid, block, 0, st, a);
+    if (n_area && small) hipLaunchKernelGGL((k_shadow_area<kTraceLdsTest>), grid, block, 0, st, aa);
+    else if (n_area) hipLaunchKernelGGL((k_shadow_area<kTraceLds>), grid, block, 0, st, aa);
+    else if (point && small) hipLaunchKernelGGL((k_shadow_lights<kTraceLdsTest>), grid, block, 0, st, a);
     else if (point) hipLaunchKernelGGL((k_shadow_lights<kTraceLds>), grid, block, 0, st, a);
     else if (small) hipLaunchKernelGGL((k_shadow<kTraceLdsTest>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((k_shadow<kTraceLds>), grid, block, 0, st, a);
@@ -375,7 +490,8 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
     if (e != hipSuccess) return (int)e;
     if (p.irradiance || p.rgba) {
         const dim3 rgrid((uint32_t)((P + kDSetupT - 1) / kDSetupT));
-        if (point) hipLaunchKernelGGL(k_lights_resolve, rgrid, dim3(kDSetupT), 0, st, a);
+        if (n_area) hipLaunchKernelGGL(k_area_resolve, rgrid, dim3(kDSetupT), 0, st, aa);
+        else if (point) hipLaunchKernelGGL(k_lights_resolve, rgrid, dim3(kDSetupT), 0, st, a);
         else hipLaunchKernelGGL(k_direct_resolve, rgrid, dim3(kDSetupT), 0, st, a);
         e = hipGetLastError();
     }

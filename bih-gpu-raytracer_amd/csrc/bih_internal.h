@@ -371,6 +371,15 @@ int launch_gbuffer(const DeviceTree &t, const RenderArgs &a, const GBufferPlanes
 // cursor (one u64) are zeroed by the launch; spill, max_blocks, lds_slots: as
 // launch_trace.
 constexpr uint32_t kMaxLights = 64;   // BIH_MAX_LIGHTS: one bit each of a sample's lit word
+constexpr uint32_t kMaxAreaLights = 16;   // BIH_MAX_AREA_LIGHTS
+// The area lights of a call (bih_render_area_lights*): the last n of its light
+// slots, which hold {corner, weight}; here the rest, in host memory.
+struct AreaLights {
+    uint32_t n = 0;
+    uint32_t hseed = 0;         // area_seed_hash(seed), bih_area.h
+    uint32_t fs0 = 0;           // frame * spp (wrapping)
+    float uvn[kMaxAreaLights][9];   // edge_u, edge_v, nl = cross(edge_u, edge_v) in the header's order
+};
 struct DirectPlanes {
     unsigned long long *lit = nullptr;
     float *irradiance = nullptr;
@@ -378,7 +387,8 @@ struct DirectPlanes {
 };
 int launch_direct(const DeviceTree &t, const RenderArgs &a, const DirectPlanes &p, const float *lights,
                   uint32_t n_lights, uint32_t n_dir, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
-                  uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream);
+                  uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream,
+                  const AreaLights *area = nullptr);
 int launch_rng_init(uint32_t *rng, uint32_t w, uint32_t row0, uint32_t nrows, uint32_t band_h,
                     uint32_t band_step, uint64_t seed, uint64_t skip, int device, void *stream);
 // dst = src's per-pixel state advanced by `steps` draws (planes of `pixels`; dst may be src)

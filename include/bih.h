@@ -38,7 +38,8 @@ extern "C" {
                                3: bih_whitted_work, BIH_PARAM_WHITTED_COUNTERS;
                                4: bih_host_register / bih_host_unregister, bih_render_history;
                                (4, added since: bih_trace*, bih_render_gbuffer*, BIH_PARAM_GBUFFER_MASK,
-                                bih_render_direct*, BIH_QUERY_T_HI and bih_ray.t_hi, bih_render_lights*) */
+                                bih_render_direct*, BIH_QUERY_T_HI and bih_ray.t_hi, bih_render_lights*,
+                                bih_render_area_lights*, bih_area_light_sample) */
 
 /* error codes */
 #define BIH_OK               0
@@ -535,6 +536,87 @@ int bih_render_lights(const bih_tree *tree, const bih_camera *camera, uint32_t w
                       const bih_light *dir_lights, uint32_t n_dir,
                       const bih_point_light *point_lights, uint32_t n_point,
                       const bih_direct *host_planes);                       /* synchronous, host memory */
+
+/* Direct lighting with area lights (soft shadows) next to directional and
+ * point lights, in one call.  An area light is a
+ * lamp whose position differs per sample, plus the emitter's own cosine: one
+ * shadow ray per (sample, light) to a point of the panel, no new walk rule.
+ *
+ * Bit k < n_dir of lit is directional light k; bit n_dir + i is point light i;
+ * bit n_dir + n_point + j is area light j.  n_dir + n_point + n_area is in
+ * 1..BIH_MAX_LIGHTS and n_area <= BIH_MAX_AREA_LIGHTS; an array may be NULL
+ * exactly when its count is 0.  The set and its arrays are HOST memory, copied
+ * by the call.
+ *
+ * Semantics: bih_render_lights', every f32 operation one separately rounded
+ * IEEE operation; directional and point lights work exactly as there.  For a
+ * hit sample s of global pixel gp = y*w + x (y the global row under bih_rows,
+ * so bands reassemble) with hit point P and normal n (both as
+ * bih_render_direct defines them) and area light j {corner = C, weight = W,
+ * edge_u = U, edge_v = V}:
+ *  - Sample point, all arithmetic u32 and wrapping.  It does not come from the
+ *    pixel's XORWOW subsequence (no draw of any frame moves) but from a
+ *    counter-based hash:
+ *      mix(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16
+ *      h = mix((uint32_t)seed); h = mix(h ^ (uint32_t)(seed>>32)); h = mix(h ^ gp);
+ *      h = mix(h ^ (frame*spp + s)); h = mix(h ^ j);
+ *      ha = mix(h + 0x9E3779B9); hb = mix(h + 0x3C6EF372);
+ *      a = (float)(ha>>8) * 0x1p-24f; b = (float)(hb>>8) * 0x1p-24f
+ *    (both exact, in [0,1)); Q[c] = (C[c] + a*U[c]) + b*V[c].
+ *    bih_area_light_sample returns exactly this Q.
+ *  - L[c] = Q[c] - P[c].  nl = (U.y*V.z - V.y*U.z, U.z*V.x - V.z*U.x,
+ *    U.x*V.y - V.x*U.y): cross(U, V), not normalised, so |nl| is the area.
+ *  - c = (n.x*L.x + n.y*L.y) + n.z*L.z; g = -((nl.x*L.x + nl.y*L.y) + nl.z*L.z).
+ *    The light is facing exactly when c > 0.0f and g > 0.0f: a panel emits
+ *    from ONE side, the side nl points to.  A zero-area panel (nl = 0), a NaN
+ *    panel and a panel seen from behind never light a sample.
+ *  - The light is lit when it is facing and BIH_QUERY_OCCLUDED_WITHIN on
+ *    {o = P, t_lo = BIH_SHADOW_T_LO, d = L, t_hi = 1.0f} returns 0: a lamp's
+ *    ray.  Geometry coincident with the panel (its fixture) has t = 1 up to
+ *    rounding and may or may not shadow it: set a panel a little in front of
+ *    its fixture.
+ *  - Contribution, in this order: r2 = (L.x*L.x + L.y*L.y) + L.z*L.z;
+ *    len = sqrtf(r2); e_s = e_s + ((W * (c / len)) * (g / len)) / r2 --
+ *    radiance x cosine at the surface x (area x cosine at the emitter) over the
+ *    squared distance, the one-sample estimator with pdf 1/area.  Whatever inf
+ *    or NaN the arithmetic gives is the result.
+ *  - The sums run over the lit bits in ascending k.  The per-pixel E, rgba and
+ *    miss shade are bih_render_direct's.
+ *  - With n_area == 0 every plane is byte-identical to bih_render_lights' (and
+ *    the call launches its kernels).
+ * Errors, in bih_render_lights' order, its light checks replaced by: lights ==
+ * NULL -> BIH_ERR_INVALID; n_dir + n_point + n_area == 0 or > BIH_MAX_LIGHTS
+ * -> BIH_ERR_INVALID; n_area > BIH_MAX_AREA_LIGHTS -> BIH_ERR_INVALID; an
+ * array NULL with a non-zero count -> BIH_ERR_INVALID.
+ * Planes, RNG accounting, ordering and scratch: exactly bih_render_direct's. */
+#define BIH_MAX_AREA_LIGHTS 16
+/* A parallelogram: the points corner + a*edge_u + b*edge_v, a, b in [0,1).  It
+ * emits from ONE side, the side its normal cross(edge_u, edge_v) points to.
+ * weight = its radiance. */
+typedef struct bih_area_light {
+    float corner[3]; float weight;
+    float edge_u[3]; float reserved0;
+    float edge_v[3]; float reserved1;
+} bih_area_light;                                                            /* 48 B */
+typedef struct bih_light_set {
+    const bih_light *dir;          uint32_t n_dir;
+    const bih_point_light *point;  uint32_t n_point;
+    const bih_area_light *area;    uint32_t n_area;
+} bih_light_set;                                        /* host memory, copied by the call */
+int bih_render_area_lights_device(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                                  uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                                  const bih_light_set *lights,
+                                  const bih_direct *d_planes, void *stream); /* async; bih_sync waits */
+int bih_render_area_lights(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                           uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                           const bih_light_set *lights,
+                           const bih_direct *host_planes);                  /* synchronous, host memory */
+/* Host only, no device: the point Q of area light j (`light`, the j-th of its
+ * call) that sample s of global pixel `pixel` = y*w + x uses in frame `frame`
+ * of a render with `spp` samples per pixel.  light or q NULL, spp == 0 or
+ * s >= spp -> BIH_ERR_INVALID. */
+int bih_area_light_sample(const bih_area_light *light, uint32_t j, uint64_t seed, uint32_t pixel,
+                          uint32_t frame, uint32_t spp, uint32_t s, float q[3]);
 
 /* The drop-in host loop (bih_render into a caller's framebuffer) ends in a
  * device-to-host copy of w*h*4 bytes.  Into pageable memory the runtime
