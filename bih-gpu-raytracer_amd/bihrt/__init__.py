@@ -65,6 +65,21 @@ GBUFFER_PLANES = {"depth": (np.float32, 1), "prim": (np.uint32, 1), "bary": (np.
 DIRECT_PLANES = {"lit": (np.uint64, 0), "irradiance": (np.float32, 1), "rgba": (np.uint32, 1)}
 
 
+def _rows_ref(rows: Rows | None):
+    """The bih_rows * argument of an optional Rows (NULL: the whole image)."""
+    return C.byref(rows) if rows is not None else None
+
+
+def _device_planes(st, known, ptrs: dict):
+    """Fills the plane struct `st` (GBuffer, Direct) from {name: device pointer};
+    KeyError on a name not in `known`."""
+    for name, ptr in ptrs.items():
+        if name not in known:
+            raise KeyError(name)
+        setattr(st, name, ptr or None)
+    return st
+
+
 def pack_lights(lights) -> np.ndarray:
     """(k,) LIGHT_DTYPE array (bih_light records) of a LIGHT_DTYPE array or of
     (k, 4) rows {dir.x, dir.y, dir.z, weight}."""
@@ -162,8 +177,7 @@ class GPUArrayManager:
     def reserve(self, w: int, h: int, spp: int, rows: Rows | None = None, max_frames: int = 1):
         """bih_reserve: size every per-call buffer of renders of this shape (calls
         of up to max_frames frames) now, so that a frame loop allocates nothing."""
-        check(load().bih_reserve(self._tree, w, h, spp, C.byref(rows) if rows is not None else None,
-                                 max_frames), "bih_reserve")
+        check(load().bih_reserve(self._tree, w, h, spp, _rows_ref(rows), max_frames), "bih_reserve")
 
     def bins_stats(self):
         """Frustum bins of the current camera and image (bih_bins_get_stats)."""
@@ -276,8 +290,7 @@ class Renderer:
                       stream: int | None = None):
         """Asynchronous device-resident render into out_ptr (u32, nrows*w)."""
         check(load().bih_render_device(self.arrays.handle, C.byref(self.camera), self.w, self.h,
-                                       self.spp, frame, self.seed,
-                                       C.byref(rows) if rows is not None else None, traverse,
+                                       self.spp, frame, self.seed, _rows_ref(rows), traverse,
                                        C.c_void_p(out_ptr), C.c_void_p(stats_ptr or 0),
                                        C.c_void_p(stream or 0)), "bih_render_device")
 
@@ -286,8 +299,7 @@ class Renderer:
         """Frames frame0 .. frame0+nframes-1 (any-hit) in one call
         (bih_render_device_frames); frame j at out_ptr + 4*j*out_stride bytes."""
         check(load().bih_render_device_frames(self.arrays.handle, C.byref(self.camera), self.w, self.h,
-                                              self.spp, frame0, nframes, self.seed,
-                                              C.byref(rows) if rows is not None else None,
+                                              self.spp, frame0, nframes, self.seed, _rows_ref(rows),
                                               C.c_void_p(out_ptr), out_stride, C.c_void_p(stream or 0)),
               "bih_render_device_frames")
 
@@ -308,8 +320,7 @@ class Renderer:
         """Asynchronous C4 render into out_ptr (u32, nrows*w); hits_ptr (optional,
         u32 per sample) receives each sample's hit count along its mirror path."""
         check(load().bih_render_whitted_device(self.arrays.handle, C.byref(self.camera), self.w, self.h,
-                                               self.spp, frame, self.seed,
-                                               C.byref(rows) if rows is not None else None,
+                                               self.spp, frame, self.seed, _rows_ref(rows),
                                                C.c_void_p(out_ptr), C.c_void_p(hits_ptr or 0),
                                                C.c_void_p(stream or 0)), "bih_render_whitted_device")
 
@@ -331,7 +342,7 @@ class Renderer:
             out["hits"] = np.zeros(nrows * self.w * self.spp, HIT_DTYPE)
             gb.hits = out["hits"].ctypes.data
         check(load().bih_render_gbuffer(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
-                                        self.seed, C.byref(rows) if rows is not None else None, C.byref(gb)),
+                                        self.seed, _rows_ref(rows), C.byref(gb)),
               "bih_render_gbuffer")
         self.frame = f + 1
         return out
@@ -340,14 +351,21 @@ class Renderer:
         """Asynchronous G-buffer render into device memory (bih_render_gbuffer_device):
         ptrs maps plane names ("hits", "depth", "prim", "bary", "normal", "coverage")
         to device pointers; planes left out are not written."""
-        gb = GBuffer()
-        for name, ptr in ptrs.items():
-            if name != "hits" and name not in GBUFFER_PLANES:
-                raise KeyError(name)
-            setattr(gb, name, ptr or None)
+        gb = _device_planes(GBuffer(), ("hits", *GBUFFER_PLANES), ptrs)
         check(load().bih_render_gbuffer_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
-                                               frame, self.seed, C.byref(rows) if rows is not None else None,
+                                               frame, self.seed, _rows_ref(rows),
                                                C.byref(gb), C.c_void_p(stream or 0)), "bih_render_gbuffer_device")
+
+    def _host_direct(self, rows, planes):
+        """Zeroed host arrays of the DIRECT_PLANES asked for, by name, and the
+        bih_direct that points at them."""
+        nrows = rows.nrows if rows is not None else self.h
+        out, dp = {}, Direct()
+        for name in planes:
+            dt, k = DIRECT_PLANES[name]
+            out[name] = np.zeros((nrows, self.w) if k else nrows * self.w * self.spp, dt)
+            setattr(dp, name, out[name].ctypes.data)
+        return out, dp
 
     def render_direct(self, lights, frame: int | None = None, rows: Rows | None = None,
                       planes=("lit", "irradiance", "rgba")) -> dict:
@@ -358,15 +376,10 @@ class Renderer:
         (nrows*w*spp,) uint64, bit k = light k reaches sample p*spp + s;
         "irradiance" (nrows, w) float32; "rgba" (nrows, w) uint32 grey."""
         f = self.frame if frame is None else frame
-        nrows = rows.nrows if rows is not None else self.h
         lt = pack_lights(lights)
-        out, dp = {}, Direct()
-        for name in planes:
-            dt, k = DIRECT_PLANES[name]
-            out[name] = np.zeros((nrows, self.w) if k else nrows * self.w * self.spp, dt)
-            setattr(dp, name, out[name].ctypes.data)
+        out, dp = self._host_direct(rows, planes)
         check(load().bih_render_direct(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
-                                       self.seed, C.byref(rows) if rows is not None else None,
+                                       self.seed, _rows_ref(rows),
                                        C.c_void_p(lt.ctypes.data), lt.shape[0], C.byref(dp)), "bih_render_direct")
         self.frame = f + 1
         return out
@@ -377,14 +390,10 @@ class Renderer:
         (bih_render_direct_device): ptrs maps plane names ("lit", "irradiance",
         "rgba") to device pointers; planes left out are not written.  lights is
         host memory (as render_direct's), copied by the call."""
-        dp = Direct()
-        for name, ptr in ptrs.items():
-            if name not in DIRECT_PLANES:
-                raise KeyError(name)
-            setattr(dp, name, ptr or None)
+        dp = _device_planes(Direct(), DIRECT_PLANES, ptrs)
         lt = pack_lights(lights)
         check(load().bih_render_direct_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
-                                              frame, self.seed, C.byref(rows) if rows is not None else None,
+                                              frame, self.seed, _rows_ref(rows),
                                               C.c_void_p(lt.ctypes.data), lt.shape[0], C.byref(dp),
                                               C.c_void_p(stream or 0)), "bih_render_direct_device")
 
@@ -403,15 +412,10 @@ class Renderer:
         MAX_LIGHTS.  Bit k of "lit" is directional light k, bit len(dir_lights)
         + j point light j, which a triangle behind it does not shadow."""
         f = self.frame if frame is None else frame
-        nrows = rows.nrows if rows is not None else self.h
         dl, pl, dptr, nd, pptr, npt = self._lights_args(dir_lights, point_lights)
-        out, dp = {}, Direct()
-        for name in planes:
-            dt, k = DIRECT_PLANES[name]
-            out[name] = np.zeros((nrows, self.w) if k else nrows * self.w * self.spp, dt)
-            setattr(dp, name, out[name].ctypes.data)
+        out, dp = self._host_direct(rows, planes)
         check(load().bih_render_lights(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
-                                       self.seed, C.byref(rows) if rows is not None else None,
+                                       self.seed, _rows_ref(rows),
                                        dptr, nd, pptr, npt, C.byref(dp)), "bih_render_lights")
         self.frame = f + 1
         return out
@@ -421,14 +425,10 @@ class Renderer:
         """Asynchronous render_lights into device memory (bih_render_lights_device);
         ptrs as render_direct_device's.  Both light arrays are host memory, copied
         by the call."""
-        dp = Direct()
-        for name, ptr in ptrs.items():
-            if name not in DIRECT_PLANES:
-                raise KeyError(name)
-            setattr(dp, name, ptr or None)
+        dp = _device_planes(Direct(), DIRECT_PLANES, ptrs)
         dl, pl, dptr, nd, pptr, npt = self._lights_args(dir_lights, point_lights)
         check(load().bih_render_lights_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
-                                              frame, self.seed, C.byref(rows) if rows is not None else None,
+                                              frame, self.seed, _rows_ref(rows),
                                               dptr, nd, pptr, npt, C.byref(dp), C.c_void_p(stream or 0)),
               "bih_render_lights_device")
 
@@ -448,15 +448,10 @@ class Renderer:
         len(point_lights) + j of "lit" is area light j: per sample one shadow
         ray to a point of the panel (area_light_sample)."""
         f = self.frame if frame is None else frame
-        nrows = rows.nrows if rows is not None else self.h
         keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        out, dp = {}, Direct()
-        for name in planes:
-            dt, k = DIRECT_PLANES[name]
-            out[name] = np.zeros((nrows, self.w) if k else nrows * self.w * self.spp, dt)
-            setattr(dp, name, out[name].ctypes.data)
+        out, dp = self._host_direct(rows, planes)
         check(load().bih_render_area_lights(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
-                                            self.seed, C.byref(rows) if rows is not None else None,
+                                            self.seed, _rows_ref(rows),
                                             C.byref(ls), C.byref(dp)), "bih_render_area_lights")
         del keep
         self.frame = f + 1
@@ -467,15 +462,10 @@ class Renderer:
         """Asynchronous render_area_lights into device memory
         (bih_render_area_lights_device); ptrs as render_direct_device's.  The
         light arrays are host memory, copied by the call."""
-        dp = Direct()
-        for name, ptr in ptrs.items():
-            if name not in DIRECT_PLANES:
-                raise KeyError(name)
-            setattr(dp, name, ptr or None)
+        dp = _device_planes(Direct(), DIRECT_PLANES, ptrs)
         keep, ls = self._light_set(dir_lights, point_lights, area_lights)
         check(load().bih_render_area_lights_device(self.arrays.handle, C.byref(self.camera), self.w, self.h,
-                                                   self.spp, frame, self.seed,
-                                                   C.byref(rows) if rows is not None else None,
+                                                   self.spp, frame, self.seed, _rows_ref(rows),
                                                    C.byref(ls), C.byref(dp), C.c_void_p(stream or 0)),
               "bih_render_area_lights_device")
         del keep

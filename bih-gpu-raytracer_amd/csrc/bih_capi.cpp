@@ -5,6 +5,12 @@
 // per-pixel curandState (src/Renderer.cpp:762-797).  Here a bih_tree owns
 // both, per device, and errors are returned instead of exit(99)
 // (src/Renderer.cpp:63-73).
+//
+// Shared by the entries: grow (every buffer of a tree that follows the calls'
+// shapes), Stage (the host entries' device copies), wait_tree (a launch after
+// the last rebuild), base_render_args / finish_slot (the Whitted and G-buffer
+// launches), and light_set_check / render_light_set (the one path of the six
+// direct-lighting entries).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -319,6 +325,56 @@ int map_hip(int e) {
     return BIH_ERR_HIP;
 }
 
+// Grows a tree-owned device buffer to `bytes`, recorded as the capacity
+// `need` (in the site's own unit); nothing when *cap >= need.  The old buffer
+// is freed first: the caller has waited for whatever may still read it.  On
+// failure the pointer is null and the capacity 0.
+template <class T>
+int grow(bih_tree *tr, T **p, size_t *cap, size_t need, size_t bytes) {
+    if (*cap >= need) return BIH_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const hipError_t e = tree_malloc(tr, p, bytes);
+    if (e != hipSuccess) return map_hip((int)e);
+    *cap = need;
+    return BIH_OK;
+}
+
+// A host entry's device copies of up to N host regions (NULL: not asked for,
+// no room), each at a multiple of 16 bytes of one of the tree's stage
+// buffers.  A stage buffer's only users are the calls of its host entry, which
+// wait for their work under the tree's lock.
+template <int N>
+struct Stage {
+    void *host[N];
+    size_t size[N];
+    size_t off[N];
+    char *buf;
+    // lays the regions out and grows the stage buffer to hold them
+    int place(bih_tree *tr, char **stage, size_t *cap) {
+        size_t total = 0;
+        for (int k = 0; k < N; ++k) {
+            off[k] = total;
+            if (host[k]) total += (size[k] + 15) & ~(size_t)15;
+        }
+        const int rc = grow(tr, stage, cap, total, total);
+        buf = *stage;
+        return rc;
+    }
+    void *dev(int k) const { return host[k] ? buf + off[k] : nullptr; }
+    // After the launch, which returned rc: regions first .. N-1 back to the
+    // host on the tree's stream, which is synchronised whatever failed.  The
+    // launch's error comes first, then a copy's, then the wait's.
+    int finish(bih_tree *tr, int rc, int first = 0) const {
+        for (int k = first; k < N && rc == BIH_OK; ++k)
+            if (host[k])
+                rc = map_hip((int)hipMemcpyAsync(host[k], buf + off[k], size[k], hipMemcpyDeviceToHost, tr->stream));
+        const hipError_t e = hipStreamSynchronize(tr->stream);
+        return rc ? rc : map_hip((int)e);
+    }
+};
+
 int check_device(int device) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return BIH_ERR_NO_DEVICE;
@@ -341,6 +397,14 @@ int wait_renders(bih_tree *tr, hipStream_t st) {
 int wait_traces(bih_tree *tr, hipStream_t st) {
     if (!tr->trace_used || hipEventQuery(tr->ev_trace) == hipSuccess) return BIH_OK;
     return map_hip((int)hipStreamWaitEvent(st, tr->ev_trace, 0));
+}
+
+// Orders `st` after the last (re)build (a rebuild does not order ev_rng).  A
+// build that has completed needs no wait (no barrier packet on `st`).
+int wait_tree(bih_tree *tr, hipStream_t st) {
+    if (tr->tree_pending && hipEventQuery(tr->ev_tree) == hipSuccess) tr->tree_pending = false;
+    if (!tr->tree_pending) return BIH_OK;
+    return map_hip((int)hipStreamWaitEvent(st, tr->ev_tree, 0));
 }
 
 // Orders `st` after every render in flight that read camera set `c`.
@@ -389,12 +453,8 @@ int prepare_chunk_order(bih_tree *tr, uint32_t w, uint32_t spp, const bih_rows &
         // every render that may still use the old buffers has finished
         for (int k = 0; k < kSlots; ++k)
             if (tr->used[k]) (void)hipEventSynchronize(tr->evd[k]);
-        if (tr->chunk_buf) (void)hipFree(tr->chunk_buf);
-        tr->chunk_buf = nullptr;
-        tr->chunk_cap = 0;
-        hipError_t e = tree_malloc(tr, &tr->chunk_buf, (size_t)kSlots * 2 * n * sizeof(uint32_t));
-        if (e != hipSuccess) return map_hip((int)e);
-        tr->chunk_cap = n;
+        const int rc = grow(tr, &tr->chunk_buf, &tr->chunk_cap, n, (size_t)kSlots * 2 * n * sizeof(uint32_t));
+        if (rc) return rc;
         memset(tr->chunk_key, 0, sizeof tr->chunk_key);
     }
     uint32_t *cost = tr->chunk_buf + (size_t)slot * 2 * tr->chunk_cap;
@@ -861,14 +921,14 @@ static int ensure_rng(bih_tree *tr, size_t P, hipStream_t st) {
     if (P <= tr->rng_cap) return BIH_OK;
     int rc = drain_renders(tr);
     if (rc) return rc;
-    if (tr->rng) (void)hipFree(tr->rng);
-    tr->rng = nullptr;
-    tr->rng_cap = 0;
     const size_t words = P * (5 * kRngBufs + kSlots);
-    hipError_t e = tree_malloc(tr, &tr->rng, words * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(tr->rng + 5 * kRngBufs * P, 0, kSlots * P * sizeof(uint32_t), st);
-    if (e != hipSuccess) return map_hip((int)e);
-    tr->rng_cap = P;
+    rc = grow(tr, &tr->rng, &tr->rng_cap, P, words * sizeof(uint32_t));
+    if (rc) return rc;
+    const hipError_t e = hipMemsetAsync(tr->rng + 5 * kRngBufs * P, 0, kSlots * P * sizeof(uint32_t), st);
+    if (e != hipSuccess) {
+        tr->rng_cap = 0;   // (grown again, and zeroed, by the next call)
+        return map_hip((int)e);
+    }
     tr->rng_cur = 0;
     tr->rng_valid = false;
     tr->stamped = false;
@@ -944,14 +1004,8 @@ static int ensure_stamps(bih_tree *tr, size_t ntiles, hipStream_t st) {
     }
     int rc = drain_renders(tr);
     if (rc) return rc;
-    if (tr->stamps) (void)hipFree(tr->stamps);
-    tr->stamps = nullptr;
-    tr->stamp_cap = 0;
     tr->stamped = false;
-    hipError_t e = tree_malloc(tr, &tr->stamps, ntiles * sizeof(unsigned long long));
-    if (e != hipSuccess) return map_hip((int)e);
-    tr->stamp_cap = ntiles;
-    return BIH_OK;
+    return grow(tr, &tr->stamps, &tr->stamp_cap, ntiles, ntiles * sizeof(unsigned long long));
 }
 
 static uint32_t next_stamp_seq(bih_tree *tr) {
@@ -984,13 +1038,7 @@ static int ensure_per_slot(bih_tree *tr, uint32_t **buf, size_t *cap, size_t nee
     if (*cap >= need) return BIH_OK;
     int rc = drain_renders(tr);
     if (rc) return rc;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    hipError_t e = tree_malloc(tr, buf, (size_t)kSlots * need * unit * sizeof(uint32_t));
-    if (e != hipSuccess) return map_hip((int)e);
-    *cap = need;
-    return BIH_OK;
+    return grow(tr, buf, cap, need, (size_t)kSlots * need * unit * sizeof(uint32_t));
 }
 
 // Armed after prepare_rng: unless disarmed (the render was issued), the
@@ -1174,12 +1222,8 @@ static int build_bins(bih_tree *tr, CamSet &c, const bih_camera *cam, const floa
     if (c.bins_mem_cap < need) {
         hipError_t e = hipStreamSynchronize(st);   // renders that read the old bins
         if (e != hipSuccess) return map_hip((int)e);
-        if (c.bins_mem) (void)hipFree(c.bins_mem);
-        c.bins_mem = nullptr;
-        c.bins_mem_cap = 0;
-        e = tree_malloc(tr, &c.bins_mem, need);
-        if (e != hipSuccess) return map_hip((int)e);
-        c.bins_mem_cap = need;
+        const int rc = grow(tr, &c.bins_mem, &c.bins_mem_cap, need, need);
+        if (rc) return rc;
         c.bins_layout = 0;
     }
     char *p = c.bins_mem;
@@ -1260,17 +1304,11 @@ static int build_bins(bih_tree *tr, CamSet &c, const bih_camera *cam, const floa
         const uint64_t cap = total + total / 8 + 1024;
         if (cap > 0xFFFFFFFFull || cap * kEntryBytes > (uint64_t)mem_free / 2 + (uint64_t)c.bin_list_cap * kEntryBytes)
             return BIH_OK;
-        if (c.bin_list_cap < total + 1) {
-            if (c.bin_list) (void)hipFree(c.bin_list);   // st waited for every render
+        // (st waited for every render)
+        if (c.bin_list_cap < total + 1 && grow(tr, &c.bin_list, &c.bin_list_cap, cap, cap * kEntryBytes) != BIH_OK) {
+            (void)hipGetLastError();   // not sticky: this camera renders without bins
             c.bin_list = nullptr;
-            c.bin_list_cap = 0;
-            e = tree_malloc(tr, &c.bin_list, cap * kEntryBytes);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();   // not sticky: this camera renders without bins
-                c.bin_list = nullptr;
-                return BIH_OK;
-            }
-            c.bin_list_cap = cap;
+            return BIH_OK;
         }
         le = bih::launch_bin_status(b, c.bin_list_cap, st);
         if (le) return map_hip(le);
@@ -1314,26 +1352,20 @@ static int ensure_queue_mem(bih_tree *tr, CamSet &c, uint32_t ntiles, hipStream_
         // the hit cache: its stamps start at 0, which no queue's hseq is
         int rc = drain_renders(tr);
         if (rc) return rc;
-        if (c.hc) (void)hipFree(c.hc);
-        c.hc = nullptr;
-        c.hc_tiles = 0;
-        hipError_t e = tree_malloc(tr, &c.hc, (size_t)ntiles * 65 * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(c.hc + (size_t)ntiles * 64, 0, (size_t)ntiles * sizeof(uint32_t), st);
-        if (e != hipSuccess) return map_hip((int)e);
-        c.hc_tiles = ntiles;
+        rc = grow(tr, &c.hc, &c.hc_tiles, ntiles, (size_t)ntiles * 65 * sizeof(uint32_t));
+        if (rc) return rc;
+        const hipError_t e = hipMemsetAsync(c.hc + (size_t)ntiles * 64, 0, (size_t)ntiles * sizeof(uint32_t), st);
+        if (e != hipSuccess) {
+            c.hc_tiles = 0;   // (grown again, and zeroed, by the next call)
+            return map_hip((int)e);
+        }
     }
     const size_t need = bih::bin_queue_bytes(ntiles);
     if (c.q_cap >= need) return BIH_OK;
     int rc = drain_renders(tr);
     if (rc) return rc;
-    if (c.q_mem) (void)hipFree(c.q_mem);
-    c.q_mem = nullptr;
-    c.q_cap = 0;
     c.q_valid = false;
-    hipError_t e = tree_malloc(tr, &c.q_mem, need);
-    if (e != hipSuccess) return map_hip((int)e);
-    c.q_cap = need;
-    return BIH_OK;
+    return grow(tr, &c.q_mem, &c.q_cap, need, need);
 }
 
 // The render kernel's tile queue for this launch's rows (launch_bin_queue):
@@ -1498,37 +1530,31 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
     // the last (re)build: waited for right before the first work of this
     // call that reads the tree, so that the XORWOW advance (which does not)
     // runs beside a rebuild still in flight
-    // a build that has completed needs no wait (no barrier packet on `st`)
-    if (tr->tree_pending && hipEventQuery(tr->ev_tree) == hipSuccess) tr->tree_pending = false;
-    bool tree_waited = !tr->tree_pending;
-    auto wait_tree = [&]() -> hipError_t {
-        if (tree_waited) return hipSuccess;
+    bool tree_waited = false;
+    auto wait_tree_once = [&]() -> int {
+        if (tree_waited) return BIH_OK;
         tree_waited = true;
-        return hipStreamWaitEvent(st, tr->ev_tree, 0);
+        return wait_tree(tr, st);
     };
     // primary-ray records follow the camera (the origin; the miss-proof boxes
     // also the direction bounds)
     const uint32_t n_int = tr->t.u > 0 ? tr->t.u - 1 : 0;
     if (bih::render_uses_prim(spp) && tr->t.n > 0) {
         const size_t need = bih::prim_bytes(tr->t.n, n_int);
-        const bool grow = c.prim_cap < need;
+        const bool too_small = c.prim_cap < need;
         // (grown to the size of U = N, the most a soup of N triangles can have:
         // trees of other soups of that size reuse it)
         const size_t alloc = bih::prim_bytes(tr->t.n, tr->t.n > 0 ? tr->t.n - 1 : 0);
-        if (grow || !c.prim_valid || memcmp(ob, c.prim_origin, sizeof ob) != 0) {
+        if (too_small || !c.prim_valid || memcmp(ob, c.prim_origin, sizeof ob) != 0) {
             // rewritten in place: after every render still reading the records
             rc = wait_set_readers(tr, ci, st);
             if (rc) return rc;
         }
-        if (grow) {
+        if (too_small) {
             rc = drain_renders(tr);
             if (rc) return rc;
-            if (c.prim) (void)hipFree(c.prim);
-            c.prim = nullptr;
-            c.prim_cap = 0;
-            e = tree_malloc(tr, &c.prim, std::max(need, alloc));
-            if (e != hipSuccess) return map_hip((int)e);
-            c.prim_cap = std::max(need, alloc);
+            rc = grow(tr, &c.prim, &c.prim_cap, std::max(need, alloc), std::max(need, alloc));
+            if (rc) return rc;
             c.prim_valid = false;
         }
         // the frustum bins' build computes the records itself (k_cam_tris)
@@ -1547,8 +1573,8 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
             if (want_bins) {
                 need_prim = true;
             } else {
-                e = wait_tree();
-                if (e != hipSuccess) return map_hip((int)e);
+                rc = wait_tree_once();
+                if (rc) return rc;
                 int le = bih::launch_prim(tr->t.tris_s, tr->t.n, tr->t.nodes, tr->t.first_idx,
                                           tr->t.dup_cnt, tr->t.leaf_parent, tr->t.parent, n_int,
                                           cam->origin, dmax, c.prim, st);
@@ -1569,8 +1595,8 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
             if (rc) return rc;
             float dmax[3];
             (void)bih_camera_ray_bound(cam, dmax);
-            e = wait_tree();
-            if (e != hipSuccess) return map_hip((int)e);
+            rc = wait_tree_once();
+            if (rc) return rc;
             rc = build_bins(tr, c, cam, dmax, w, h, spp, need_prim, st);
             if (rc) {
                 if (need_prim) c.prim_valid = false;
@@ -1697,8 +1723,8 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
         if (rc) return rc;
     }
     if (!hit_mask) tr->next_frame = frame + nframes;
-    e = wait_tree();
-    if (e != hipSuccess) return map_hip((int)e);
+    rc = wait_tree_once();
+    if (rc) return rc;
     if (use_bins) {
         a.bin_off = c.bins.off;
         a.bin_list = c.bin_list;
@@ -1944,6 +1970,44 @@ int bih_tree_set_param(bih_tree *tr, int param, uint64_t value) {
     return BIH_OK;
 }
 
+// The RenderArgs fields a Whitted and a G-buffer launch fill alike: the
+// camera, the image, the rows and the frame's first draw.
+static bih::RenderArgs base_render_args(const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                                        const bih_rows &rows, uint64_t seed, uint32_t frame) {
+    bih::RenderArgs a;
+    memcpy(a.cam, cam, sizeof a.cam);
+    a.w = w;
+    a.h = h;
+    a.spp = spp;
+    a.row0 = rows.row0;
+    a.nrows = rows.nrows;
+    a.band_h = rows.band_h;
+    a.band_step = rows.band_step;
+    uint32_t v[5], d0;
+    bih::xorwow_seed(seed, v, &d0);
+    a.d_base = d0 + (uint32_t)((uint64_t)2 * spp * frame) * 362437u;
+    return a;
+}
+
+// The slot's accounting once a Whitted or G-buffer launch (neither reads a
+// camera set) is issued on `st`: its evd, the slot rotation, and the ring's
+// buffer `nxt` for the next frame.
+static int finish_slot(bih_tree *tr, int slot, hipStream_t st, int nxt, RngGuard &rng_guard) {
+    tr->last_timed = tr->timing;
+    tr->slot_timed[slot] = tr->timing;
+    const hipError_t e = hipEventRecord(tr->evd[slot], st);
+    if (e != hipSuccess) return map_hip((int)e);
+    tr->used[slot] = true;
+    tr->slot_gen[slot] = tr->gen;
+    note_stream(tr, slot, st);
+    tr->slot_cs[slot] = -1;
+    tr->last_slot = slot;
+    tr->slot = (slot + 1) % kSlots;
+    tr->rng_cur = nxt;
+    rng_guard.armed = false;
+    return BIH_OK;
+}
+
 int bih_render_whitted_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h,
                               uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows_in,
                               uint32_t *d_out, uint32_t *d_hits, void *stream) {
@@ -1987,12 +2051,8 @@ int bih_render_whitted_device(const bih_tree *ctr, const bih_camera *cam, uint32
         if (tr->wh_mask_cap < ntiles) {
             int rc = drain_renders(tr);
             if (rc) return rc;
-            if (tr->wh_mask) (void)hipFree(tr->wh_mask);
-            tr->wh_mask = nullptr;
-            tr->wh_mask_cap = 0;
-            hipError_t e = tree_malloc(tr, &tr->wh_mask, ntiles * 8);
-            if (e != hipSuccess) return map_hip((int)e);
-            tr->wh_mask_cap = ntiles;
+            rc = grow(tr, &tr->wh_mask, &tr->wh_mask_cap, ntiles, ntiles * 8);
+            if (rc) return rc;
         } else if (tr->wh_prev_slot >= 0 && tr->used[tr->wh_prev_slot]) {
             // the mask is rewritten in place: after the last Whitted launch
             // (its k_wh_gen reads the previous mask), whatever stream it ran on
@@ -2012,11 +2072,8 @@ int bih_render_whitted_device(const bih_tree *ctr, const bih_camera *cam, uint32
         hipError_t e = wait_rng(tr, st);
         if (e != hipSuccess) return map_hip((int)e);
     }
-    if (tr->tree_pending && hipEventQuery(tr->ev_tree) == hipSuccess) tr->tree_pending = false;
-    if (tr->tree_pending) {   // the last (re)build (a rebuild does not order ev_rng)
-        hipError_t e = hipStreamWaitEvent(st, tr->ev_tree, 0);
-        if (e != hipSuccess) return map_hip((int)e);
-    }
+    rc = wait_tree(tr, st);
+    if (rc) return rc;
     // bih_whitted_work describes the last Whitted launch issued: none until
     // this one is (a failure below, or a reallocated wh_mem, leaves nothing
     // to read)
@@ -2032,28 +2089,13 @@ int bih_render_whitted_device(const bih_tree *ctr, const bih_camera *cam, uint32
     if (tr->wh_rays < rays) {
         hipError_t e = hipStreamSynchronize(st);   // the previous Whitted render's readers
         if (e != hipSuccess) return map_hip((int)e);
-        if (tr->wh_mem) (void)hipFree(tr->wh_mem);
-        tr->wh_mem = nullptr;
-        tr->wh_rays = 0;
-        e = tree_malloc(tr, &tr->wh_mem, bih::whitted_bytes(rays));
-        if (e != hipSuccess) return map_hip((int)e);
-        tr->wh_rays = rays;
+        rc = grow(tr, &tr->wh_mem, &tr->wh_rays, rays, bih::whitted_bytes(rays));
+        if (rc) return rc;
     }
     hipError_t e = hipEventRecord(tr->ev_rng, st);
     if (e != hipSuccess) return map_hip((int)e);
     tr->rng_pending = true;
-    bih::RenderArgs a;
-    memcpy(a.cam, cam, sizeof a.cam);
-    a.w = w;
-    a.h = h;
-    a.spp = spp;
-    a.row0 = rows.row0;
-    a.nrows = rows.nrows;
-    a.band_h = rows.band_h;
-    a.band_step = rows.band_step;
-    uint32_t v[5], d0;
-    bih::xorwow_seed(seed, v, &d0);
-    a.d_base = d0 + (uint32_t)((uint64_t)2 * spp * frame) * 362437u;
+    bih::RenderArgs a = base_render_args(cam, w, h, spp, rows, seed, frame);
     a.hdr = tr->t.hdr;
     a.hdr_n_tris = tr->t.n;
     a.n_nodes = tr->t.u > 0 ? tr->t.u - 1 : 0;
@@ -2074,19 +2116,7 @@ int bih_render_whitted_device(const bih_tree *ctr, const bih_camera *cam, uint32
         e = hipEventRecord(tr->ev2[slot], st);
         if (e != hipSuccess) return map_hip((int)e);
     }
-    tr->last_timed = tr->timing;
-    tr->slot_timed[slot] = tr->timing;
-    e = hipEventRecord(tr->evd[slot], st);
-    if (e != hipSuccess) return map_hip((int)e);
-    tr->used[slot] = true;
-    tr->slot_gen[slot] = tr->gen;
-    note_stream(tr, slot, st);
-    tr->slot_cs[slot] = -1;            // reads no camera set
-    tr->last_slot = slot;
-    tr->slot = (slot + 1) % kSlots;
-    tr->rng_cur = nxt;
-    rng_guard.armed = false;
-    return BIH_OK;
+    return finish_slot(tr, slot, st, nxt, rng_guard);
 }
 
 int bih_whitted_work(const bih_tree *ctr, uint32_t rays[BIH_WHITTED_BOUNCES + 1],
@@ -2120,14 +2150,7 @@ int bih_render_whitted(const bih_scene *scene, const bih_tree *ctr, const bih_ca
     const size_t P = (size_t)fb->h * fb->w;
     {
         std::lock_guard<std::mutex> lk(tr->mu);
-        if (P > tr->fb_cap) {
-            if (tr->fb) (void)hipFree(tr->fb);
-            tr->fb = nullptr;
-            tr->fb_cap = 0;
-            hipError_t e = tree_malloc(tr, &tr->fb, P * 4);
-            if (e != hipSuccess) return map_hip((int)e);
-            tr->fb_cap = P;
-        }
+        if (const int rc = grow(tr, &tr->fb, &tr->fb_cap, P, P * 4)) return rc;
     }
     int rc = bih_render_whitted_device(tr, cam, fb->w, fb->h, fb->spp, fb->frame, fb->seed, nullptr, tr->fb,
                                        nullptr, nullptr);
@@ -2158,11 +2181,8 @@ static int trace_locked(bih_tree *tr, const void *d_rays, uint32_t n, uint32_t q
     int rc = ensure_trace(tr);
     if (rc) return rc;
     // after the last (re)build, as renders; no RNG state is read or waited for
-    if (tr->tree_pending && hipEventQuery(tr->ev_tree) == hipSuccess) tr->tree_pending = false;
-    if (tr->tree_pending) {
-        const hipError_t e = hipStreamWaitEvent(st, tr->ev_tree, 0);
-        if (e != hipSuccess) return map_hip((int)e);
-    }
+    rc = wait_tree(tr, st);
+    if (rc) return rc;
     // the cursor and the spill area are shared: after the trace before this one
     rc = wait_traces(tr, st);
     if (rc) return rc;
@@ -2210,25 +2230,13 @@ int bih_trace(const bih_tree *ctr, const bih_ray *rays, uint64_t n_rays, uint32_
     std::lock_guard<std::mutex> lk(tr->mu);
     const size_t in_bytes = (size_t)n_rays * sizeof(bih_ray);
     const size_t out_bytes = (size_t)n_rays * (query_closest(query) ? sizeof(bih_hit) : 1);
-    if (tr->tq_stage_cap < in_bytes + out_bytes) {
-        // (its only users are calls of this function, which wait for their work)
-        if (tr->tq_stage) (void)hipFree(tr->tq_stage);
-        tr->tq_stage = nullptr;
-        tr->tq_stage_cap = 0;
-        const hipError_t e = tree_malloc(tr, &tr->tq_stage, in_bytes + out_bytes);
-        if (e != hipSuccess) return map_hip((int)e);
-        tr->tq_stage_cap = in_bytes + out_bytes;
-    }
-    char *d_in = tr->tq_stage, *d_res = tr->tq_stage + in_bytes;   // (in_bytes: a multiple of 32)
-    hipError_t e = hipMemcpyAsync(d_in, rays, in_bytes, hipMemcpyHostToDevice, tr->stream);
+    // the rays go up (region 0), the results come back (region 1)
+    Stage<2> sg{{const_cast<bih_ray *>(rays), out}, {in_bytes, out_bytes}};
+    rc = sg.place(tr, &tr->tq_stage, &tr->tq_stage_cap);
+    if (rc) return rc;
+    const hipError_t e = hipMemcpyAsync(sg.dev(0), rays, in_bytes, hipMemcpyHostToDevice, tr->stream);
     if (e != hipSuccess) return map_hip((int)e);
-    rc = trace_locked(tr, d_in, (uint32_t)n_rays, query, d_res, tr->stream);
-    if (rc == BIH_OK) {
-        e = hipMemcpyAsync(out, d_res, out_bytes, hipMemcpyDeviceToHost, tr->stream);
-        if (e != hipSuccess) rc = map_hip((int)e);
-    }
-    e = hipStreamSynchronize(tr->stream);
-    return rc ? rc : map_hip((int)e);
+    return sg.finish(tr, trace_locked(tr, sg.dev(0), (uint32_t)n_rays, query, sg.dev(1), tr->stream), 1);
 }
 
 // Argument checks of both G-buffer entries, in the header's order; none
@@ -2253,13 +2261,14 @@ static int gbuffer_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, 
     return BIH_OK;
 }
 
-// What a direct-lighting call adds to its G-buffer launch: the lights (host
-// memory) and the caller's planes.  The launch's hits go to dr_mem.
+// What a direct-lighting call adds to its G-buffer launch: its light set
+// merged into the kernels' slot order (merge_light_set) and the planes to
+// write (device memory).  The launch's hits go to dr_mem.
 struct DirectJob {
-    const float *lights;    // n_lights x 4 floats: n_dir bih_light, then bih_point_light
-    uint32_t n_lights, n_dir;
+    float lights[4 * BIH_MAX_LIGHTS];   // n_lights x 4 floats: n_dir bih_light, then bih_point_light, then
+    uint32_t n_lights, n_dir;           // the area lights' {corner, weight}
+    bih::AreaLights area;               // the last area.n lights are area lights (0: no area kernels)
     bih_direct planes;
-    const bih::AreaLights *area = nullptr;   // the last area->n lights are area lights (else null)
 };
 
 // bih_render_gbuffer_device under the tree's lock, arguments checked, nrows > 0.
@@ -2284,23 +2293,9 @@ static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
         const size_t ntiles = (size_t)bih::gbuffer_tiles(w, rows.nrows, spp, &tiles_x);
         if (tr->gb_mask_cap < ntiles || tr->gb_scratch_cap < P) {
             rc = drain_renders(tr);
+            if (rc == BIH_OK) rc = grow(tr, &tr->gb_mask, &tr->gb_mask_cap, ntiles, ntiles * 8);
+            if (rc == BIH_OK) rc = grow(tr, &tr->gb_scratch, &tr->gb_scratch_cap, P, P * 4);
             if (rc) return rc;
-            if (tr->gb_mask_cap < ntiles) {
-                if (tr->gb_mask) (void)hipFree(tr->gb_mask);
-                tr->gb_mask = nullptr;
-                tr->gb_mask_cap = 0;
-                const hipError_t e = tree_malloc(tr, &tr->gb_mask, ntiles * 8);
-                if (e != hipSuccess) return map_hip((int)e);
-                tr->gb_mask_cap = ntiles;
-            }
-            if (tr->gb_scratch_cap < P) {
-                if (tr->gb_scratch) (void)hipFree(tr->gb_scratch);
-                tr->gb_scratch = nullptr;
-                tr->gb_scratch_cap = 0;
-                const hipError_t e = tree_malloc(tr, &tr->gb_scratch, P * 4);
-                if (e != hipSuccess) return map_hip((int)e);
-                tr->gb_scratch_cap = P;
-            }
         } else if (tr->gb_prev_slot >= 0 && tr->used[tr->gb_prev_slot]) {
             // the mask and the scratch image are rewritten in place: after the
             // last G-buffer launch (it reads the mask), whatever stream it ran on
@@ -2322,12 +2317,8 @@ static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
         const hipError_t e = wait_rng(tr, st);
         if (e != hipSuccess) return map_hip((int)e);
     }
-    if (tr->tree_pending && hipEventQuery(tr->ev_tree) == hipSuccess) tr->tree_pending = false;
-    if (tr->tree_pending) {
-        const hipError_t e = hipStreamWaitEvent(st, tr->ev_tree, 0);
-        if (e != hipSuccess) return map_hip((int)e);
-    }
-    rc = wait_traces(tr, st);
+    rc = wait_tree(tr, st);
+    if (rc == BIH_OK) rc = wait_traces(tr, st);
     if (rc) return rc;
     rc = prepare_rng(tr, w, spp, frame, seed, rows, st);
     if (rc) return rc;
@@ -2338,18 +2329,7 @@ static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
     hipError_t e = hipEventRecord(tr->ev_rng, st);
     if (e != hipSuccess) return map_hip((int)e);
     tr->rng_pending = true;
-    bih::RenderArgs a;
-    memcpy(a.cam, cam, sizeof a.cam);
-    a.w = w;
-    a.h = h;
-    a.spp = spp;
-    a.row0 = rows.row0;
-    a.nrows = rows.nrows;
-    a.band_h = rows.band_h;
-    a.band_step = rows.band_step;
-    uint32_t v[5], d0;
-    bih::xorwow_seed(seed, v, &d0);
-    a.d_base = d0 + (uint32_t)((uint64_t)2 * spp * frame) * 362437u;
+    bih::RenderArgs a = base_render_args(cam, w, h, spp, rows, seed, frame);
     a.rng_in = rng_buf(tr, cur);
     bih::GBufferPlanes p;
     p.hits = pl.hits;
@@ -2377,7 +2357,7 @@ static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
                                 reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
                                 tr->prm.trace_lds, tr->tq_cursor + 4,
                                 reinterpret_cast<unsigned long long *>(tr->tq_cursor + 2), tr->tq_spill,
-                                tr->tq_blocks, st, dj->area);
+                                tr->tq_blocks, st, dj->area.n ? &dj->area : nullptr);
     }
     // (a failed launch may have left work on st that uses the cursor: the event covers it)
     e = hipEventRecord(tr->ev_trace, st);
@@ -2389,20 +2369,9 @@ static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
         if (e == hipSuccess) e = hipEventRecord(tr->ev2[slot], st);
         if (e != hipSuccess) return map_hip((int)e);
     }
-    tr->last_timed = tr->timing;
-    tr->slot_timed[slot] = tr->timing;
-    e = hipEventRecord(tr->evd[slot], st);
-    if (e != hipSuccess) return map_hip((int)e);
-    tr->used[slot] = true;
-    tr->slot_gen[slot] = tr->gen;
-    note_stream(tr, slot, st);
-    tr->slot_cs[slot] = -1;            // reads no camera set
-    tr->last_slot = slot;
-    tr->slot = (slot + 1) % kSlots;
-    tr->gb_prev_slot = slot;
-    tr->rng_cur = nxt;
-    rng_guard.armed = false;
-    return BIH_OK;
+    rc = finish_slot(tr, slot, st, nxt, rng_guard);
+    if (rc == BIH_OK) tr->gb_prev_slot = slot;
+    return rc;
 }
 
 int bih_render_gbuffer_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
@@ -2425,224 +2394,31 @@ int bih_render_gbuffer(const bih_tree *ctr, const bih_camera *cam, uint32_t w, u
     bih_tree *tr = const_cast<bih_tree *>(ctr);
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
-    // device planes of the ones asked for, each at a multiple of 16 bytes
+    // device planes of the ones asked for
     const size_t P = (size_t)rows.nrows * w;
-    void *const host[6] = {host_planes->hits, host_planes->depth, host_planes->prim,
-                           host_planes->bary, host_planes->normal, host_planes->coverage};
-    const size_t size[6] = {P * spp * sizeof(bih_hit), P * 4, P * 4, P * 8, P * 12, P * 4};
-    size_t off[6], total = 0;
-    for (int k = 0; k < 6; ++k) {
-        off[k] = total;
-        if (host[k]) total += (size[k] + 15) & ~(size_t)15;
-    }
-    if (tr->gb_stage_cap < total) {
-        // (its only users are calls of this function, which wait for their work)
-        if (tr->gb_stage) (void)hipFree(tr->gb_stage);
-        tr->gb_stage = nullptr;
-        tr->gb_stage_cap = 0;
-        const hipError_t e = tree_malloc(tr, &tr->gb_stage, total);
-        if (e != hipSuccess) return map_hip((int)e);
-        tr->gb_stage_cap = total;
-    }
-    auto dev_plane = [&](int k) -> void * { return host[k] ? tr->gb_stage + off[k] : nullptr; };
+    Stage<6> sg{{host_planes->hits, host_planes->depth, host_planes->prim, host_planes->bary, host_planes->normal,
+                 host_planes->coverage},
+                {P * spp * sizeof(bih_hit), P * 4, P * 4, P * 8, P * 12, P * 4}};
+    rc = sg.place(tr, &tr->gb_stage, &tr->gb_stage_cap);
+    if (rc) return rc;
     bih_gbuffer d;
-    d.hits = static_cast<bih_hit *>(dev_plane(0));
-    d.depth = static_cast<float *>(dev_plane(1));
-    d.prim = static_cast<uint32_t *>(dev_plane(2));
-    d.bary = static_cast<float *>(dev_plane(3));
-    d.normal = static_cast<float *>(dev_plane(4));
-    d.coverage = static_cast<uint32_t *>(dev_plane(5));
-    rc = gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, d, nullptr);
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 6 && rc == BIH_OK; ++k)
-        if (host[k]) {
-            e = hipMemcpyAsync(host[k], tr->gb_stage + off[k], size[k], hipMemcpyDeviceToHost, tr->stream);
-            if (e != hipSuccess) rc = map_hip((int)e);
-        }
-    e = hipStreamSynchronize(tr->stream);
-    return rc ? rc : map_hip((int)e);
+    d.hits = static_cast<bih_hit *>(sg.dev(0));
+    d.depth = static_cast<float *>(sg.dev(1));
+    d.prim = static_cast<uint32_t *>(sg.dev(2));
+    d.bary = static_cast<float *>(sg.dev(3));
+    d.normal = static_cast<float *>(sg.dev(4));
+    d.coverage = static_cast<uint32_t *>(sg.dev(5));
+    return sg.finish(tr, gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, d, nullptr));
 }
 
-// Argument checks of both direct-lighting entries, in the header's order; none
-// touches the tree or a device.  *rows: the rows of the call.
-static int direct_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                        const bih_rows *rows_in, const bih_light *lights, uint32_t n_lights, const bih_direct *pl,
-                        bih_rows *rows) {
-    // the G-buffer's checks; its "all planes NULL" is about the three planes here
-    static float some_plane;
-    bih_gbuffer g = {};
-    if (pl && (pl->lit || pl->irradiance || pl->rgba)) g.depth = &some_plane;
-    const int rc = gbuffer_check(tr, cam, w, h, spp, rows_in, pl ? &g : nullptr, rows);
-    if (rc) return rc;
-    if (!lights || n_lights == 0 || n_lights > BIH_MAX_LIGHTS) return BIH_ERR_INVALID;
-    if ((uintptr_t)pl->lit & 7u) return BIH_ERR_INVALID;   // the lit words take 64-bit atomics
-    return BIH_OK;
-}
-
-// bih_render_direct_device under the tree's lock, arguments checked, nrows > 0.
-// lights: n_lights x 4 floats, the first n_dir directional, the rest point lights.
-static int direct_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t frame,
-                         uint64_t seed, const bih_rows &rows, const float *lights, uint32_t n_lights, uint32_t n_dir,
-                         const bih_direct &pl, void *stream, const bih::AreaLights *area = nullptr) {
-    const size_t S = (size_t)rows.nrows * w * spp;
-    const bool own_lit = !pl.lit && tr->dr_lit_cap < S;
-    if ((tr->dr_cap < S || own_lit) && tr->trace_used) {
-        // (the users of both buffers are direct-lighting launches: each ends before its ev_trace record)
-        const hipError_t e = hipEventSynchronize(tr->ev_trace);
-        if (e != hipSuccess) return map_hip((int)e);
-    }
-    if (own_lit) {
-        if (tr->dr_lit) (void)hipFree(tr->dr_lit);
-        tr->dr_lit = nullptr;
-        tr->dr_lit_cap = 0;
-        const hipError_t e = tree_malloc(tr, &tr->dr_lit, S * 8);
-        if (e != hipSuccess) return map_hip((int)e);
-        tr->dr_lit_cap = S;
-    }
-    if (tr->dr_cap < S) {
-        if (tr->dr_mem) (void)hipFree(tr->dr_mem);
-        tr->dr_mem = nullptr;
-        tr->dr_cap = 0;
-        const hipError_t e = tree_malloc(tr, &tr->dr_mem, S * kDirectSampleBytes);
-        if (e != hipSuccess) return map_hip((int)e);
-        tr->dr_cap = S;
-    }
-    static_assert(sizeof(bih_light) == 16 && BIH_MAX_LIGHTS == bih::kMaxLights, "bih_light / kMaxLights");
-    static_assert(sizeof(bih_point_light) == 16, "bih_point_light shares bih_light's slots");
-    bih_gbuffer g = {};
-    g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
-    const DirectJob dj{lights, n_lights, n_dir, pl, area};
-    return gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, g, stream, &dj);
-}
-
-int bih_render_direct_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                             uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light *lights,
-                             uint32_t n_lights, const bih_direct *d_planes, void *stream) {
-    bih_rows rows;
-    const int rc = direct_check(ctr, cam, w, h, spp, rows_in, lights, n_lights, d_planes, &rows);
-    if (rc || rows.nrows == 0) return rc;
-    bih_tree *tr = const_cast<bih_tree *>(ctr);
-    DeviceGuard g(tr->t.device);
-    std::lock_guard<std::mutex> lk(tr->mu);
-    return direct_locked(tr, cam, w, h, spp, frame, seed, rows, &lights[0].dir[0], n_lights, n_lights, *d_planes,
-                         stream);
-}
-
-// bih_render_direct / bih_render_lights under the tree's lock, arguments
-// checked, nrows > 0: direct_locked into device planes, copied to the host's.
-static int direct_host_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                              uint32_t frame, uint64_t seed, const bih_rows &rows, const float *lights,
-                              uint32_t n_lights, uint32_t n_dir, const bih_direct *host_planes,
-                              const bih::AreaLights *area = nullptr) {
-    int rc;
-    // device planes of the ones asked for, each at a multiple of 16 bytes
-    const size_t P = (size_t)rows.nrows * w;
-    void *const host[3] = {host_planes->lit, host_planes->irradiance, host_planes->rgba};
-    const size_t size[3] = {P * spp * 8, P * 4, P * 4};
-    size_t off[3], total = 0;
-    for (int k = 0; k < 3; ++k) {
-        off[k] = total;
-        if (host[k]) total += (size[k] + 15) & ~(size_t)15;
-    }
-    if (tr->dr_stage_cap < total) {
-        // (its only users are calls of this function, which wait for their work)
-        if (tr->dr_stage) (void)hipFree(tr->dr_stage);
-        tr->dr_stage = nullptr;
-        tr->dr_stage_cap = 0;
-        const hipError_t e = tree_malloc(tr, &tr->dr_stage, total);
-        if (e != hipSuccess) return map_hip((int)e);
-        tr->dr_stage_cap = total;
-    }
-    auto dev_plane = [&](int k) -> void * { return host[k] ? tr->dr_stage + off[k] : nullptr; };
-    bih_direct d;
-    d.lit = static_cast<uint64_t *>(dev_plane(0));
-    d.irradiance = static_cast<float *>(dev_plane(1));
-    d.rgba = static_cast<uint32_t *>(dev_plane(2));
-    rc = direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_lights, n_dir, d, nullptr, area);
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 3 && rc == BIH_OK; ++k)
-        if (host[k]) {
-            e = hipMemcpyAsync(host[k], tr->dr_stage + off[k], size[k], hipMemcpyDeviceToHost, tr->stream);
-            if (e != hipSuccess) rc = map_hip((int)e);
-        }
-    e = hipStreamSynchronize(tr->stream);
-    return rc ? rc : map_hip((int)e);
-}
-
-int bih_render_direct(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                      uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light *lights,
-                      uint32_t n_lights, const bih_direct *host_planes) {
-    bih_rows rows;
-    const int rc = direct_check(ctr, cam, w, h, spp, rows_in, lights, n_lights, host_planes, &rows);
-    if (rc || rows.nrows == 0) return rc;
-    bih_tree *tr = const_cast<bih_tree *>(ctr);
-    DeviceGuard g(tr->t.device);
-    std::lock_guard<std::mutex> lk(tr->mu);
-    return direct_host_locked(tr, cam, w, h, spp, frame, seed, rows, &lights[0].dir[0], n_lights, n_lights,
-                              host_planes);
-}
-
-// Argument checks of both bih_render_lights entries: direct_check's, its light
-// checks replaced (the header's order); none touches the tree or a device.
-static int lights_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                        const bih_rows *rows_in, const bih_light *dir_lights, uint32_t n_dir,
-                        const bih_point_light *point_lights, uint32_t n_point, const bih_direct *pl,
-                        bih_rows *rows) {
-    static float some_plane;
-    bih_gbuffer g = {};
-    if (pl && (pl->lit || pl->irradiance || pl->rgba)) g.depth = &some_plane;
-    const int rc = gbuffer_check(tr, cam, w, h, spp, rows_in, pl ? &g : nullptr, rows);
-    if (rc) return rc;
-    const uint64_t n = (uint64_t)n_dir + n_point;
-    if (n == 0 || n > BIH_MAX_LIGHTS) return BIH_ERR_INVALID;
-    if ((n_dir && !dir_lights) || (n_point && !point_lights)) return BIH_ERR_INVALID;
-    if ((uintptr_t)pl->lit & 7u) return BIH_ERR_INVALID;   // the lit words take 64-bit atomics
-    return BIH_OK;
-}
-
-// The call's lights in the kernels' slot order: directional, then point.
-static void merge_lights(const bih_light *dir_lights, uint32_t n_dir, const bih_point_light *point_lights,
-                         uint32_t n_point, float *out) {
-    if (n_dir) memcpy(out, dir_lights, (size_t)n_dir * sizeof(bih_light));
-    if (n_point) memcpy(out + 4 * (size_t)n_dir, point_lights, (size_t)n_point * sizeof(bih_point_light));
-}
-
-int bih_render_lights_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                             uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light *dir_lights,
-                             uint32_t n_dir, const bih_point_light *point_lights, uint32_t n_point,
-                             const bih_direct *d_planes, void *stream) {
-    bih_rows rows;
-    const int rc = lights_check(ctr, cam, w, h, spp, rows_in, dir_lights, n_dir, point_lights, n_point, d_planes,
-                                &rows);
-    if (rc || rows.nrows == 0) return rc;
-    float lights[4 * BIH_MAX_LIGHTS];
-    merge_lights(dir_lights, n_dir, point_lights, n_point, lights);
-    bih_tree *tr = const_cast<bih_tree *>(ctr);
-    DeviceGuard g(tr->t.device);
-    std::lock_guard<std::mutex> lk(tr->mu);
-    return direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_dir + n_point, n_dir, *d_planes, stream);
-}
-
-int bih_render_lights(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                      uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light *dir_lights,
-                      uint32_t n_dir, const bih_point_light *point_lights, uint32_t n_point,
-                      const bih_direct *host_planes) {
-    bih_rows rows;
-    const int rc = lights_check(ctr, cam, w, h, spp, rows_in, dir_lights, n_dir, point_lights, n_point,
-                                host_planes, &rows);
-    if (rc || rows.nrows == 0) return rc;
-    float lights[4 * BIH_MAX_LIGHTS];
-    merge_lights(dir_lights, n_dir, point_lights, n_point, lights);
-    bih_tree *tr = const_cast<bih_tree *>(ctr);
-    DeviceGuard g(tr->t.device);
-    std::lock_guard<std::mutex> lk(tr->mu);
-    return direct_host_locked(tr, cam, w, h, spp, frame, seed, rows, lights, n_dir + n_point, n_dir, host_planes);
-}
-
-// Argument checks of both bih_render_area_lights entries: lights_check's, its
-// light checks replaced (the header's order); none touches the tree or a device.
-static int area_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                      const bih_rows *rows_in, const bih_light_set *ls, const bih_direct *pl, bih_rows *rows) {
+// Argument checks of the six direct-lighting entries (bih_render_direct*,
+// bih_render_lights*, bih_render_area_lights*), each of which states its
+// lights as a bih_light_set: the G-buffer's checks, then the lights and lit's
+// alignment (BIH_ERR_INVALID all, so one order serves the three headers').
+// None touches the tree or a device.  *rows: the rows of the call.
+static int light_set_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                           const bih_rows *rows_in, const bih_light_set *ls, const bih_direct *pl, bih_rows *rows) {
+    // the G-buffer's "all planes NULL" is about the three planes here
     static float some_plane;
     bih_gbuffer g = {};
     if (pl && (pl->lit || pl->irradiance || pl->rgba)) g.depth = &some_plane;
@@ -2665,13 +2441,19 @@ static void area_normal(const float *u, const float *v, float *nl) {
 }
 
 // The call's lights in the kernels' slot order: directional, point, then the
-// area lights' {corner, weight}; *al: what else the area kernels need.
-static void merge_light_set(const bih_light_set *ls, uint32_t spp, uint32_t frame, uint64_t seed, float *out,
-                            bih::AreaLights *al) {
+// area lights' {corner, weight}; dj->area: what else the area kernels need.
+static void merge_light_set(const bih_light_set *ls, uint32_t spp, uint32_t frame, uint64_t seed, DirectJob *dj) {
+    static_assert(sizeof(bih_light) == 16 && BIH_MAX_LIGHTS == bih::kMaxLights, "bih_light / kMaxLights");
+    static_assert(sizeof(bih_point_light) == 16, "bih_point_light shares bih_light's slots");
     static_assert(sizeof(bih_area_light) == 48 && BIH_MAX_AREA_LIGHTS == bih::kMaxAreaLights,
                   "bih_area_light / kMaxAreaLights");
-    merge_lights(ls->dir, ls->n_dir, ls->point, ls->n_point, out);
-    float *slot = out + 4 * ((size_t)ls->n_dir + ls->n_point);
+    dj->n_dir = ls->n_dir;
+    dj->n_lights = ls->n_dir + ls->n_point + ls->n_area;
+    if (ls->n_dir) memcpy(dj->lights, ls->dir, (size_t)ls->n_dir * sizeof(bih_light));
+    float *slot = dj->lights + 4 * (size_t)ls->n_dir;
+    if (ls->n_point) memcpy(slot, ls->point, (size_t)ls->n_point * sizeof(bih_point_light));
+    slot += 4 * (size_t)ls->n_point;
+    bih::AreaLights *al = &dj->area;
     al->n = ls->n_area;
     al->hseed = bih::area_seed_hash(seed);
     al->fs0 = frame * spp;
@@ -2685,36 +2467,92 @@ static void merge_light_set(const bih_light_set *ls, uint32_t spp, uint32_t fram
     }
 }
 
-int bih_render_area_lights_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                                  uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light_set *ls,
-                                  const bih_direct *d_planes, void *stream) {
-    bih_rows rows;
-    const int rc = area_check(ctr, cam, w, h, spp, rows_in, ls, d_planes, &rows);
-    if (rc || rows.nrows == 0) return rc;
-    float lights[4 * BIH_MAX_LIGHTS];
-    bih::AreaLights al;
-    merge_light_set(ls, spp, frame, seed, lights, &al);
-    bih_tree *tr = const_cast<bih_tree *>(ctr);
-    DeviceGuard g(tr->t.device);
-    std::lock_guard<std::mutex> lk(tr->mu);
-    return direct_locked(tr, cam, w, h, spp, frame, seed, rows, lights, ls->n_dir + ls->n_point + ls->n_area,
-                         ls->n_dir, *d_planes, stream, al.n ? &al : nullptr);
+// A direct-lighting render into dj.planes under the tree's lock, arguments
+// checked, nrows > 0.
+static int direct_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t frame,
+                         uint64_t seed, const bih_rows &rows, const DirectJob &dj, void *stream) {
+    const size_t S = (size_t)rows.nrows * w * spp;
+    const bool own_lit = !dj.planes.lit && tr->dr_lit_cap < S;
+    if ((tr->dr_cap < S || own_lit) && tr->trace_used) {
+        // (the users of both buffers are direct-lighting launches: each ends before its ev_trace record)
+        const hipError_t e = hipEventSynchronize(tr->ev_trace);
+        if (e != hipSuccess) return map_hip((int)e);
+    }
+    int rc = own_lit ? grow(tr, &tr->dr_lit, &tr->dr_lit_cap, S, S * 8) : BIH_OK;
+    if (rc == BIH_OK) rc = grow(tr, &tr->dr_mem, &tr->dr_cap, S, S * kDirectSampleBytes);
+    if (rc) return rc;
+    bih_gbuffer g = {};
+    g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
+    return gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, g, stream, &dj);
 }
 
-int bih_render_area_lights(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                           uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light_set *ls,
-                           const bih_direct *host_planes) {
+// The body of the six entries: the checks, then under the tree's lock the
+// merged lights and the render -- into the caller's device planes on `stream`,
+// or (host) into device planes of dr_stage on the tree's stream, copied to the
+// caller's before the call returns.
+static int render_light_set(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                            uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light_set *ls,
+                            const bih_direct *planes, void *stream, bool host) {
     bih_rows rows;
-    const int rc = area_check(ctr, cam, w, h, spp, rows_in, ls, host_planes, &rows);
+    int rc = light_set_check(ctr, cam, w, h, spp, rows_in, ls, planes, &rows);
     if (rc || rows.nrows == 0) return rc;
-    float lights[4 * BIH_MAX_LIGHTS];
-    bih::AreaLights al;
-    merge_light_set(ls, spp, frame, seed, lights, &al);
     bih_tree *tr = const_cast<bih_tree *>(ctr);
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
-    return direct_host_locked(tr, cam, w, h, spp, frame, seed, rows, lights,
-                              ls->n_dir + ls->n_point + ls->n_area, ls->n_dir, host_planes, al.n ? &al : nullptr);
+    DirectJob dj;
+    merge_light_set(ls, spp, frame, seed, &dj);
+    dj.planes = *planes;
+    if (!host) return direct_locked(tr, cam, w, h, spp, frame, seed, rows, dj, stream);
+    const size_t P = (size_t)rows.nrows * w;
+    Stage<3> sg{{planes->lit, planes->irradiance, planes->rgba}, {P * spp * 8, P * 4, P * 4}};
+    rc = sg.place(tr, &tr->dr_stage, &tr->dr_stage_cap);
+    if (rc) return rc;
+    dj.planes.lit = static_cast<uint64_t *>(sg.dev(0));
+    dj.planes.irradiance = static_cast<float *>(sg.dev(1));
+    dj.planes.rgba = static_cast<uint32_t *>(sg.dev(2));
+    return sg.finish(tr, direct_locked(tr, cam, w, h, spp, frame, seed, rows, dj, nullptr));
+}
+
+int bih_render_direct_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                             uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light *lights,
+                             uint32_t n_lights, const bih_direct *d_planes, void *stream) {
+    const bih_light_set ls = {lights, n_lights, nullptr, 0, nullptr, 0};
+    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, &ls, d_planes, stream, false);
+}
+
+int bih_render_direct(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                      uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light *lights,
+                      uint32_t n_lights, const bih_direct *host_planes) {
+    const bih_light_set ls = {lights, n_lights, nullptr, 0, nullptr, 0};
+    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, &ls, host_planes, nullptr, true);
+}
+
+int bih_render_lights_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                             uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light *dir_lights,
+                             uint32_t n_dir, const bih_point_light *point_lights, uint32_t n_point,
+                             const bih_direct *d_planes, void *stream) {
+    const bih_light_set ls = {dir_lights, n_dir, point_lights, n_point, nullptr, 0};
+    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, &ls, d_planes, stream, false);
+}
+
+int bih_render_lights(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                      uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light *dir_lights,
+                      uint32_t n_dir, const bih_point_light *point_lights, uint32_t n_point,
+                      const bih_direct *host_planes) {
+    const bih_light_set ls = {dir_lights, n_dir, point_lights, n_point, nullptr, 0};
+    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, &ls, host_planes, nullptr, true);
+}
+
+int bih_render_area_lights_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                                  uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
+                                  const bih_direct *d_planes, void *stream) {
+    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, ls, d_planes, stream, false);
+}
+
+int bih_render_area_lights(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                           uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
+                           const bih_direct *host_planes) {
+    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, ls, host_planes, nullptr, true);
 }
 
 int bih_area_light_sample(const bih_area_light *light, uint32_t j, uint64_t seed, uint32_t pixel, uint32_t frame,
@@ -2960,14 +2798,7 @@ static int render_host(const bih_scene *scene, const bih_tree *ctr, const bih_ca
     const size_t P = (size_t)nrows * fb->w;
     {
         std::lock_guard<std::mutex> lk(tr->mu);
-        if (P > tr->fb_cap) {
-            if (tr->fb) (void)hipFree(tr->fb);
-            tr->fb = nullptr;
-            tr->fb_cap = 0;
-            hipError_t e = tree_malloc(tr, &tr->fb, P * 4);
-            if (e != hipSuccess) return map_hip((int)e);
-            tr->fb_cap = P;
-        }
+        if (const int rc = grow(tr, &tr->fb, &tr->fb_cap, P, P * 4)) return rc;
     }
     bih_rows rows{row0, nrows, nrows, 1};
     int rc = bih_render_device(tr, cam, fb->w, fb->h, fb->spp, fb->frame, fb->seed, &rows,
