@@ -2563,6 +2563,16 @@ int bih_area_light_sample(const bih_area_light *light, uint32_t j, uint64_t seed
     return BIH_OK;
 }
 
+#if BIH_PHASES
+// the root-path check's load at its two sites (path_site_count, bih_render.hip)
+static void print_pathcheck(const uint32_t *c) {
+    fprintf(stderr,
+            "bin-pathcheck cache-site tile-frames %u lanes %u max-lanes %u over16 %u"
+            " walk-site tile-frames %u lanes %u max-lanes %u over16 %u\n",
+            c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]);
+}
+#endif
+
 int bih_sync(const bih_tree *tr, void *stream) {
     if (!tr) return BIH_ERR_INVALID;
     DeviceGuard g(tr->t.device);
@@ -2635,7 +2645,7 @@ int bih_sync(const bih_tree *tr, void *stream) {
 #endif
 #if BIH_PHASES && !BIH_FAST_COUNTERS
     if (tr->work && tr->last_slot >= 0) {
-        uint32_t c[80];
+        uint32_t c[84];
         if (hipMemcpyAsync(c, tr->work + (size_t)tr->last_slot * bih::kWorkWords, sizeof c,
                            hipMemcpyDeviceToHost, st) == hipSuccess &&
             hipStreamSynchronize(st) == hipSuccess) {
@@ -2643,12 +2653,13 @@ int bih_sync(const bih_tree *tr, void *stream) {
             fprintf(stderr,
                     "bin-phases (wave cycles) queue %llu background %llu setup %llu walk %llu verify %llu"
                     " write %llu\n", ph[0], ph[1], ph[2], ph[3], ph[4], ph[5]);
+            print_pathcheck(c + 76);
         }
     }
 #endif
 #if BIH_FAST_COUNTERS
     if (tr->work && tr->last_slot >= 0) {
-        uint32_t c[80];
+        uint32_t c[84];
         if (hipMemcpyAsync(c, tr->work + (size_t)tr->last_slot * bih::kWorkWords, sizeof c,
                            hipMemcpyDeviceToHost, st) == hipSuccess &&
             hipStreamSynchronize(st) == hipSuccess) {
@@ -2670,6 +2681,7 @@ int bih_sync(const bih_tree *tr, void *stream) {
             fprintf(stderr,
                     "bin-phases (wave cycles) queue %llu background %llu setup %llu walk %llu verify %llu"
                     " write %llu\n", ph[0], ph[1], ph[2], ph[3], ph[4], ph[5]);
+            print_pathcheck(c + 76);
         }
     }
 #endif

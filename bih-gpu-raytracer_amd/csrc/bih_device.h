@@ -26,14 +26,15 @@ __device__ __forceinline__ float xorwow_uniform(uint32_t v[5], uint32_t &d) {
     return (float)x * 2.3283064e-10f + (2.3283064e-10f / 2.0f);   // _curand_uniform
 }
 
-// One XORWOW step without the float conversion: the 32-bit output
-// (curand(), the word xorwow_uniform converts); same state update.
-__device__ __forceinline__ uint32_t xorwow_next(uint32_t v[5], uint32_t &d) {
+// One XORWOW state update alone: the step's raw word v[4], to which curand()
+// adds the Weyl counter before xorwow_uniform converts it (draw k of a
+// sequence whose counter starts at d returns raw_k + d + (k + 1) * kWeyl,
+// modulo 2^32)
+__device__ __forceinline__ uint32_t xorwow_raw(uint32_t v[5]) {
     uint32_t t = v[0] ^ (v[0] >> 2);
     v[0] = v[1]; v[1] = v[2]; v[2] = v[3]; v[3] = v[4];
     v[4] = (v[4] ^ (v[4] << 4)) ^ (t ^ (t << 1));
-    d += kWeyl;
-    return v[4] + d;
+    return v[4];
 }
 __device__ __forceinline__ float xorwow_to_uniform(uint32_t x) {
     return (float)x * 2.3283064e-10f + (2.3283064e-10f / 2.0f);   // _curand_uniform

@@ -37,7 +37,12 @@ constexpr int kStackDepth = 32;   // Karras path length <= 30 for distinct 30-bi
 constexpr int kLdsStack = BIH_LDS_STACK;
 // work buffer: [0..8) chunk counters (one per image band / XCD); [16..56) walk
 // counters of counter builds; [64..64+32*1024) per-CU tile slots (u64, one per
-// 128-byte line: no false sharing of the slot atomics between CUs)
+// 128-byte line: no false sharing of the slot atomics between CUs).
+// k_render_bins keeps its queue elsewhere (bin_heads) and never touches the
+// tile slots, so its diagnostic builds use the first slot line's words:
+// [64..76) six u64 phase cycle sums (BIH_PHASES, "bin-phases"), [76..84) the
+// root-path check's site counters (path_site_count, "bin-pathcheck");
+// [84..96) are free
 constexpr uint32_t kSlotStrideWords = 32;
 constexpr uint32_t kWorkWords = 64 + kSlotStrideWords * 1024 + 64;   // + histograms (counter builds)
 constexpr uint32_t kHistWord = 64 + kSlotStrideWords * 1024;

@@ -1580,14 +1580,21 @@ __device__ __forceinline__ uint32_t pixels_of(unsigned long long m) {
 // fc_mt (the work a launch that measures tile costs records)
 template <bool PMASK, bool COUNT = false>
 __device__ __forceinline__ unsigned long long bin_walk(const RenderArgs &a, const cprim_t *prims,
-                                                      uint32_t bin, float uf, float vf, float dx,
+                                                      uint32_t bin, uint32_t e0, uint32_t e1, uint32_t glen,
+                                                      float uf, float vf, float dx,
                                                       float dy, float dz, unsigned long long live,
                                                       uint32_t lane, uint32_t &cand, uint32_t &cmeta,
                                                       uint32_t &cent, uint32_t &fc_ent,
                                                       uint32_t &fc_mt, float4 *lent, uint32_t *ltag) {
-    const cu32_t *off = (const cu32_t *)(const void *)a.bin_off;
+    // [e0, e1): the tile's list (bin_off[bin], bin_off[bin + 1]) and glen, the
+    // global list's length (*bin_gstat; the bins are usable here): the same
+    // for every frame of an item, which reads them once
     const float4 *ents = reinterpret_cast<const float4 *>(a.bin_list);
-    uint32_t e = off[bin], end = off[bin + 1];
+    uint32_t e = e0, end = e1;
+    // (opaque per walk: with e0 known before the frame loop the first chunk's
+    // entry addresses are hoisted out of it -- two more VGPRs live over the
+    // whole item, on top of the root-path check's register peak)
+    asm volatile("" : "+s"(e));
     const uint32_t e_first = e;
     unsigned long long rem = live;
     const unsigned long long me = lane_bit(lane);
@@ -1667,7 +1674,7 @@ __device__ __forceinline__ unsigned long long bin_walk(const RenderArgs &a, cons
         if (!rem) break;
         ents = reinterpret_cast<const float4 *>(a.bin_glist);
         e = 0;
-        end = *a.bin_gstat;   // the global list's length (the bins are usable here)
+        end = glen;
     }
     return live & ~rem;
 }
@@ -1732,26 +1739,83 @@ __device__ __forceinline__ bool path_verify(const uint2 *__restrict__ path, uint
 }
 
 // Ray::Ray (Ray.cu:3-10) + the scene-AABB slab test (CUDAKernels.cu:237-262):
-// the ray's inverse direction and [tMin, tMax]; true when the ray meets the box
-__device__ __forceinline__ bool scene_slab(const SceneU &sc, float dx, float dy, float dz, float &ix,
-                                           float &iy, float &iz, float &tMin, float &tMax) {
+// the ray's inverse direction and [tMin, tMax]; true when the ray meets the
+// box.  The reference forms ((neg ? hi : lo) - O) * inv per axis and ray.
+// Here the six differences lo - O, hi - O come in already (SlabU: the same
+// f32 subtractions of the same operands, formed once per wave), both of an
+// axis are multiplied by the inverse and its sign selects between the
+// products: (neg ? hi : lo) * i is neg ? hi * i : lo * i, the same multiply
+// of the same operands, and a product takes its uniform factor straight from
+// a scalar register where the select of two uniform bounds needs both moved
+// into vector registers first.
+struct SlabU {
+    float lo0, lo1, lo2, hi0, hi1, hi2;
+};
+__device__ __forceinline__ float wave_uniform(float v) {
+    return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
+}
+__device__ __forceinline__ SlabU slab_bounds(const SceneU &sc) {
+    SlabU b;
+    b.lo0 = wave_uniform(sc.slo0 - sc.ox); b.hi0 = wave_uniform(sc.shi0 - sc.ox);
+    b.lo1 = wave_uniform(sc.slo1 - sc.oy); b.hi1 = wave_uniform(sc.shi1 - sc.oy);
+    b.lo2 = wave_uniform(sc.slo2 - sc.oz); b.hi2 = wave_uniform(sc.shi2 - sc.oz);
+    return b;
+}
+__device__ __forceinline__ bool scene_slab(const SlabU &b, float dx, float dy, float dz, float &ix,
+                                               float &iy, float &iz, float &tMin, float &tMax) {
     ix = 1.0f / dx;
     iy = 1.0f / dy;
     iz = 1.0f / dz;
-    const uint32_t sg = (ix < 0.0f ? 1u : 0u) | (iy < 0.0f ? 2u : 0u) | (iz < 0.0f ? 4u : 0u);
-    tMin = (((sg & 1) ? sc.shi0 : sc.slo0) - sc.ox) * ix;
-    tMax = (((sg & 1) ? sc.slo0 : sc.shi0) - sc.ox) * ix;
-    const float tymin = (((sg & 2) ? sc.shi1 : sc.slo1) - sc.oy) * iy;
-    const float tymax = (((sg & 2) ? sc.slo1 : sc.shi1) - sc.oy) * iy;
+    const bool nx = ix < 0.0f, ny = iy < 0.0f, nz = iz < 0.0f;
+    const float xl = b.lo0 * ix, xh = b.hi0 * ix;
+    tMin = nx ? xh : xl;
+    tMax = nx ? xl : xh;
+    const float yl = b.lo1 * iy, yh = b.hi1 * iy;
+    const float tymin = ny ? yh : yl, tymax = ny ? yl : yh;
     bool in_box = !((tMin > tymax) || (tymin > tMax));
     if (tymin > tMin) tMin = tymin;
     if (tymax < tMax) tMax = tymax;
-    const float tzmin = (((sg & 4) ? sc.shi2 : sc.slo2) - sc.oz) * iz;
-    const float tzmax = (((sg & 4) ? sc.slo2 : sc.shi2) - sc.oz) * iz;
+    const float zl = b.lo2 * iz, zh = b.hi2 * iz;
+    const float tzmin = nz ? zh : zl, tzmax = nz ? zl : zh;
     in_box = in_box && !((tMin > tzmax) || (tzmin > tMax));
     if (tzmin > tMin) tMin = tzmin;
     if (tzmax < tMax) tMax = tzmax;
     return in_box;
+}
+
+// The frame's 2*SPP draws of one pixel state (rs ends at the next frame's
+// state), keeping the raw words (xorwow_raw) of draws 2s and 2s+1, the two
+// sample s takes.  Samples go in groups of four: the group's pair is selected
+// on the two low bits of s (three selects per word), and the group s >> 2
+// names keeps it -- no compare per draw.  The caller adds the Weyl counter
+// to the two words it keeps instead of to all 2*SPP.
+template <uint32_t SPP>
+__device__ __forceinline__ void frame_draws(uint32_t rs[5], uint32_t s, uint32_t &xu, uint32_t &xv) {
+    constexpr uint32_t G = SPP < 4u ? SPP : 4u;
+    const bool b0 = (s & 1u) != 0u, b1 = (s & 2u) != 0u;
+#pragma unroll 1
+    for (uint32_t g = 0; g < SPP / G; ++g) {
+        uint32_t u[G], v[G];
+#pragma unroll
+        for (uint32_t j = 0; j < G; ++j) {
+            u[j] = dev::xorwow_raw(rs);
+            v[j] = dev::xorwow_raw(rs);
+        }
+        uint32_t gu = u[0], gv = v[0];
+        if (G == 2u) {
+            gu = b0 ? u[G - 1] : u[0];
+            gv = b0 ? v[G - 1] : v[0];
+        } else if (G == 4u) {
+            const uint32_t ul = b0 ? u[1] : u[0], uh = b0 ? u[G - 1] : u[G / 2];
+            const uint32_t vl = b0 ? v[1] : v[0], vh = b0 ? v[G - 1] : v[G / 2];
+            gu = b1 ? uh : ul;
+            gv = b1 ? vh : vl;
+        }
+        if (SPP <= 4u || (s >> 2) == g) {
+            xu = gu;
+            xv = gv;
+        }
+    }
 }
 
 // A plan's 1-2 critical comparisons (meta & 3 of them) on its values v
@@ -1826,6 +1890,22 @@ __device__ __forceinline__ void tl_rec(uint32_t lane, uint32_t kind, uint64_t t0
         if (k < kTlPerWave)
             g_tl_rec[wv * kTlPerWave + k] = make_uint4(wv | (xcc_id() << 24) | (kind << 28), (uint32_t)t0,
                                                        (uint32_t)(t1 - t0), len);
+    }
+}
+#endif
+#if BIH_PHASES
+// The root-path check's load at its two sites (0: the hit-cache retest, 1:
+// after the walk), work[76 + 4 * site ..]: {tile-frames with a lane that needs
+// it, those lanes, the most lanes of one tile-frame, tile-frames with more
+// than 16 of them}; bih_sync prints them ("bin-pathcheck")
+__device__ __forceinline__ void path_site_count(const RenderArgs &a, uint32_t site, unsigned long long need,
+                                                uint32_t lane) {
+    const uint32_t n = (uint32_t)__popcll(need);
+    if (n && lane == 0) {
+        atomicAdd(a.work + 76 + 4 * site, 1u);
+        atomicAdd(a.work + 77 + 4 * site, n);
+        atomicMax(a.work + 78 + 4 * site, n);
+        if (n > 16u) atomicAdd(a.work + 79 + 4 * site, 1u);
     }
 }
 #endif
@@ -1950,11 +2030,17 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
     if (tid == 0)
         for (uint32_t k = blockIdx.x; k < 9u; k += gridDim.x) a.bin_heads_next[k * 32] = 0u;
     const SceneU sc = load_scene(a);
+    const SlabU slab = slab_bounds(sc);
     const cprim_t *prims = (const cprim_t *)(const void *)a.tri_prim;
     const uint32_t tiles_x = (a.w + TW - 1) / TW;
     const float fw = (float)a.w, fh = (float)a.h;
     const uint32_t pix = lane >> LOG2SPP;
     const uint32_t bgpix = pixel_from_hits(0u, SPP);
+    // the bins' status word (k_bin_status wrote it before this launch, nothing
+    // writes it during one): read once per wave, as a scalar.  bins_ok: the
+    // lists were built; else the exact walk decides
+    const uint32_t gstat = ((const cu32_t *)(const void *)a.bin_gstat)[0];
+    const bool bins_ok = gstat != kBinsUnusable;
     BinQueue q;
     q.hdr = reinterpret_cast<const uint4 *>(a.bin_qhdr);
     q.set = a.bin_heads;
@@ -2100,8 +2186,15 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
         // (tiles with short lists: the walk finds a lane's triangle about as
         // fast as the cache test would -- a record gather and a full
         // intersector call per lane -- so they walk every frame)
-        const bool use_cache = ((const uint32_t *)a.bin_off)[bin + 1] - ((const uint32_t *)a.bin_off)[bin] >=
-                               kCacheMinLen;
+        // the tile's list [le0, le1) of bin_list: read once per item (bin_walk
+        // read both offsets again at the start of every frame's walk)
+        const uint32_t le0 = ((const cu32_t *)(const void *)a.bin_off)[bin],
+                       le1 = ((const cu32_t *)(const void *)a.bin_off)[bin + 1];
+        const bool use_cache = le1 - le0 >= kCacheMinLen;
+        // the Weyl counter's offset at this lane's first draw of a frame
+        // (frame_draws): draw 2s returns its raw word + dfr + wo, draw 2s+1
+        // that + kWeyl
+        const uint32_t wo = (2u * s + 1u) * kWeyl;
         // the lane's hit of the tile's last item (an earlier launch of this
         // camera set's current queue, RenderArgs::hcache): valid while the
         // tile's stamp is the queue's sequence number; the triangle's leaf
@@ -2133,16 +2226,15 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
                 // flow); rs ends at the next frame's state
                 // (the two words this sample takes are converted to floats,
                 // not all 2*SPP: curand_uniform of the same words)
+                // (and only those two get the Weyl counter added -- the add
+                // is modulo 2^32 and commutes with the select)
                 uint32_t xu = 0u, xv = 0u;
-                uint32_t d = dfr, rs[5];
+                uint32_t rs[5];
 #pragma unroll
                 for (int i = 0; i < 5; ++i) rs[i] = s_rs[i][tid];
-#pragma unroll 8
-                for (uint32_t k = 0; k < 2u * SPP; ++k) {
-                    const uint32_t x = dev::xorwow_next(rs, d);
-                    if (k == 2u * s) xu = x;
-                    if (k == 2u * s + 1u) xv = x;
-                }
+                frame_draws<SPP>(rs, s, xu, xv);
+                xu += dfr + wo;
+                xv += dfr + wo + kWeyl;
                 const float ru = dev::xorwow_to_uniform(xu), rv = dev::xorwow_to_uniform(xv);
                 if (fj + 1u < nf) {
 #pragma unroll
@@ -2164,12 +2256,10 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
             }
             // Ray::Ray (Ray.cu:3-10) + scene-AABB slab test (CUDAKernels.cu:237-262)
             float ix, iy, iz, tMin, tMax;
-            const bool in_box = valid && scene_slab(sc, dx, dy, dz, ix, iy, iz, tMin, tMax);
+            const bool in_box = valid && scene_slab(slab, dx, dy, dz, ix, iy, iz, tMin, tMax);
             const unsigned long long live = sc.U > 0 ? __ballot(in_box) : 0ull;
             unsigned long long hits = 0ull, undecided = 0ull;
             BIH_PH(2);
-            // bins_ok: the lists were built (k_bin_status); else the exact walk decides
-            const bool bins_ok = *a.bin_gstat != kBinsUnusable;
             if (live && sc.U > 1 && bins_ok && !(a.dbg & 8u)) {
                 uint32_t cand = 0, cmeta = 0, cent = 0, fc_ent = 0, fc_mt = 0;
                 // Hit cache (frames after an item's first): a lane first tests
@@ -2184,19 +2274,25 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
                 unsigned long long chit = 0ull;
                 if (use_cache && !(a.dbg & 20u)) {
                     const uint32_t cti = s_hc[0][tid];
-                    bool okc = false;
+                    bool okc = false, needc = false;
                     if (in_box && cti != kNoCache) {
                         const float4 *rp = reinterpret_cast<const float4 *>(a.tri_prim) + 4ull * cti;
                         const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2];
                         const float tn = reinterpret_cast<const float *>(rp)[12];
-                        okc = prim_hit_lane(r0, r1, r2, tn, dx, dy, dz) &&
-                              plan_verify(a, s_hc[1][tid], s_hc[2][tid], cti, ix, iy, iz, tMin, tMax);
+                        const bool hc = prim_hit_lane(r0, r1, r2, tn, dx, dy, dz);
+                        needc = hc && !(s_hc[1][tid] >> 31) && (s_hc[2][tid] & 3u) == 3u;
+                        okc = hc && plan_verify(a, s_hc[1][tid], s_hc[2][tid], cti, ix, iy, iz, tMin, tMax);
                     }
+#if BIH_PHASES
+                    path_site_count(a, 0u, __ballot(needc), lane);
+#else
+                    (void)needc;
+#endif
                     chit = __ballot(okc);
                 }
                 const unsigned long long wlive = live & ~chit;
                 const unsigned long long found = wlive ? bin_walk<LOG2SPP == 2, COST || BIH_BINS_TIMELINE>(
-                    a, prims, bin, uf, vf, dx, dy, dz, wlive, lane, cand, cmeta, cent, fc_ent, fc_mt, lent,
+                    a, prims, bin, le0, le1, gstat, uf, vf, dx, dy, dz, wlive, lane, cand, cmeta, cent, fc_ent, fc_mt, lent,
                     &ltag) : 0ull;
                 if (COST) work += fc_ent + 4u * fc_mt;
 #if BIH_BINS_TIMELINE
@@ -2206,6 +2302,10 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
                 tl_pl += (uint32_t)__popcll(__ballot(((found >> lane) & 1ull) && !(cand >> 31) && (cmeta & 3u) != 3u));
 #endif
                 BIH_PH(3);
+#if BIH_PHASES
+                path_site_count(a, 1u, __ballot(((found >> lane) & 1ull) && !(a.dbg & 16u) && !(cand >> 31) &&
+                                                (cmeta & 3u) == 3u), lane);
+#endif
                 const bool ok = ((found >> lane) & 1ull) &&
                                 ((a.dbg & 16u) || plan_verify(a, cand, cmeta, cent, ix, iy, iz, tMin, tMax));
                 hits = __ballot(ok) | chit;
@@ -2279,7 +2379,7 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
         }
 #if BIH_BINS_TIMELINE
         tl_rec(lane, 0u, tl_t0, __builtin_amdgcn_s_memrealtime(),
-               (((const uint32_t *)a.bin_off)[bin + 1] - ((const uint32_t *)a.bin_off)[bin]) | ((nf - f0) << 24));
+               (le1 - le0) | ((nf - f0) << 24));
         tl_rec(lane, 4u, tl_ent, tl_ent + tl_mt, tl_pv | (tl_pl << 16));   // {ent, mt, pv | pl << 16}
 #endif
     }
