@@ -21,7 +21,7 @@ import numpy as np
 from . import scenes  # noqa: F401
 from ._lib import (PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_STATIC_SOUP,
                    PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS, PARAM_GBUFFER_MASK,
-                   AREA_LIGHT_DTYPE, MAX_AREA_LIGHTS, AreaLight, LightSet,
+                   AREA_LIGHT_DTYPE, MAX_AREA_LIGHTS, AreaLight, LightSet, BOUNCE_SLOT, Bounce, Indirect,
                    NO_HIT, LIGHT_DTYPE, POINT_LIGHT_DTYPE, MAX_LIGHTS, SHADOW_T_LO, QUERY_CLOSEST, QUERY_OCCLUDED,
                    QUERY_T_HI, QUERY_CLOSEST_WITHIN, QUERY_OCCLUDED_WITHIN, PointLight, Direct, GBuffer, Hit, Light, Ray, TRAVERSE_ANYHIT,
                    TRAVERSE_REFERENCE, BihError, Camera, Framebuffer, Rows, Scene, TreeInfo, check, load)
@@ -63,6 +63,13 @@ GBUFFER_PLANES = {"depth": (np.float32, 1), "prim": (np.uint32, 1), "bary": (np.
 # the planes of a direct-lighting render (bih_direct): name -> (dtype, values
 # per pixel; 0: one per sample); lights are LIGHT_DTYPE arrays (bih_light)
 DIRECT_PLANES = {"lit": (np.uint64, 0), "irradiance": (np.float32, 1), "rgba": (np.uint32, 1)}
+
+
+# the planes of an indirect-lighting render (bih_indirect), as DIRECT_PLANES;
+# "bounce" holds HIT_DTYPE records
+INDIRECT_PLANES = {"lit": (np.uint64, 0), "bounce": (HIT_DTYPE, 0), "lit2": (np.uint64, 0),
+                   "irradiance": (np.float32, 1), "rgba": (np.uint32, 1)}
+INDIRECT = tuple(INDIRECT_PLANES)
 
 
 def _rows_ref(rows: Rows | None):
@@ -120,6 +127,16 @@ def area_light_sample(light, j: int, seed: int, pixel: int, frame: int, spp: int
     check(load().bih_area_light_sample(C.c_void_p(lt.ctypes.data), j, seed, pixel, frame, spp, s, q),
           "bih_area_light_sample")
     return np.array(q[:], np.float32)
+
+
+def bounce_sample(seed: int, pixel: int, frame: int, spp: int, s: int, n) -> np.ndarray:
+    """bih_bounce_sample (host only): the bounce direction B (3,) float32 that
+    sample s of global pixel `pixel` = y*w + x uses in frame `frame` at spp
+    samples for the normal n."""
+    nn = (C.c_float * 3)(*[float(x) for x in np.asarray(n, np.float32).reshape(3)])
+    d = (C.c_float * 3)()
+    check(load().bih_bounce_sample(seed, pixel, frame, spp, s, nn, d), "bih_bounce_sample")
+    return np.array(d[:], np.float32)
 
 
 def pack_rays(orig, dirs, t_lo=0.0, t_hi=None) -> np.ndarray:
@@ -470,6 +487,51 @@ class Renderer:
               "bih_render_area_lights_device")
         del keep
 
+    @staticmethod
+    def _bounce(bounce) -> Bounce:
+        """A Bounce of a Bounce or of (albedo, sky)."""
+        return bounce if isinstance(bounce, Bounce) else Bounce(float(bounce[0]), float(bounce[1]))
+
+    def render_indirect(self, dir_lights, point_lights, area_lights, bounce, frame: int | None = None,
+                        rows: Rows | None = None, planes=INDIRECT) -> dict:
+        """render_area_lights plus one bounce of indirect light and a sky term
+        (bih_render_indirect; synchronous).  bounce: a Bounce or (albedo, sky).
+        All three light arrays may be None or empty: the sky-only
+        (ambient-occlusion) render.  Returns a dict of the planes asked for
+        (INDIRECT_PLANES): "lit" and "lit2" (nrows*w*spp,) uint64 of the primary
+        and the bounce hit, "bounce" (nrows*w*spp,) HIT_DTYPE, the bounce ray's
+        closest hit, "irradiance" (nrows, w) float32, "rgba" (nrows, w) uint32."""
+        f = self.frame if frame is None else frame
+        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
+        nrows = rows.nrows if rows is not None else self.h
+        out, ip = {}, Indirect()
+        for name in planes:
+            dt, k = INDIRECT_PLANES[name]
+            out[name] = np.zeros((nrows, self.w) if k else nrows * self.w * self.spp, dt)
+            setattr(ip, name, out[name].ctypes.data)
+        bn = self._bounce(bounce)
+        check(load().bih_render_indirect(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
+                                         self.seed, _rows_ref(rows), C.byref(ls), C.byref(bn), C.byref(ip)),
+              "bih_render_indirect")
+        del keep
+        self.frame = f + 1
+        return out
+
+    def render_indirect_device(self, ptrs: dict, dir_lights, point_lights, area_lights, bounce, frame: int,
+                               rows: Rows | None = None, stream: int | None = None):
+        """Asynchronous render_indirect into device memory
+        (bih_render_indirect_device): ptrs maps plane names (INDIRECT_PLANES) to
+        device pointers; planes left out are not written.  The light arrays and
+        bounce are host memory, copied by the call."""
+        ip = _device_planes(Indirect(), INDIRECT_PLANES, ptrs)
+        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
+        bn = self._bounce(bounce)
+        check(load().bih_render_indirect_device(self.arrays.handle, C.byref(self.camera), self.w, self.h,
+                                                self.spp, frame, self.seed, _rows_ref(rows),
+                                                C.byref(ls), C.byref(bn), C.byref(ip), C.c_void_p(stream or 0)),
+              "bih_render_indirect_device")
+        del keep
+
     def whitted_work(self) -> dict:
         """Per bounce d = 0..8 of the last Whitted render (run with
         PARAM_WHITTED_COUNTERS on): rays traced, BIH nodes entered, triangles
@@ -569,4 +631,5 @@ __all__ = ["GPUArrayManager", "Renderer", "Model", "load_obj", "host_register", 
            "Light", "Direct", "LIGHT_DTYPE", "DIRECT_PLANES", "MAX_LIGHTS", "SHADOW_T_LO", "pack_lights",
            "QUERY_T_HI", "QUERY_CLOSEST_WITHIN", "QUERY_OCCLUDED_WITHIN", "PointLight", "POINT_LIGHT_DTYPE",
            "pack_point_lights", "AreaLight", "LightSet", "AREA_LIGHT_DTYPE", "MAX_AREA_LIGHTS",
-           "pack_area_lights", "area_light_sample"]
+           "pack_area_lights", "area_light_sample", "Bounce", "Indirect", "INDIRECT", "INDIRECT_PLANES",
+           "BOUNCE_SLOT", "bounce_sample"]

@@ -38,6 +38,7 @@ MAX_LIGHTS = 64           # bih_render_direct*: one bit each of a sample's lit w
 LIGHT_DTYPE = np.dtype([("dir", np.float32, 3), ("weight", np.float32)])   # numpy view of a bih_light array
 POINT_LIGHT_DTYPE = np.dtype([("pos", np.float32, 3), ("weight", np.float32)])   # ... of a bih_point_light array
 SHADOW_T_LO = 1e-4        # BIH_SHADOW_T_LO
+BOUNCE_SLOT = 0x80000000  # BIH_BOUNCE_SLOT: the hash slot of the bounce direction
 MAX_AREA_LIGHTS = 16      # bih_render_area_lights*: area lights of one call
 AREA_LIGHT_DTYPE = np.dtype([("corner", np.float32, 3), ("weight", np.float32),       # numpy view of a
                              ("edge_u", np.float32, 3), ("reserved0", np.float32),    # bih_area_light array
@@ -134,6 +135,18 @@ class Direct(C.Structure):
     _fields_ = [("lit", C.c_void_p), ("irradiance", C.c_void_p), ("rgba", C.c_void_p)]
 
 
+class Bounce(C.Structure):
+    """bih_bounce (8 bytes): the bounced light's diffuse reflectance and the
+    irradiance an escaped bounce ray collects."""
+    _fields_ = [("albedo", C.c_float), ("sky", C.c_float)]
+
+
+class Indirect(C.Structure):
+    """bih_indirect: five plane pointers, any of them NULL (not written)."""
+    _fields_ = [("lit", C.c_void_p), ("bounce", C.c_void_p), ("lit2", C.c_void_p), ("irradiance", C.c_void_p),
+                ("rgba", C.c_void_p)]
+
+
 class BinsStats(C.Structure):
     _fields_ = [("usable", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
                 ("list_entries", C.c_uint64), ("global_entries", C.c_uint32)]
@@ -228,6 +241,11 @@ def load():
     L.bih_render_area_lights.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
                                          C.POINTER(LightSet), C.POINTER(Direct)]
     L.bih_area_light_sample.argtypes = [vp, u32, u64, u32, u32, u32, u32, C.POINTER(C.c_float)]
+    L.bih_render_indirect_device.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                             C.POINTER(LightSet), C.POINTER(Bounce), C.POINTER(Indirect), vp]
+    L.bih_render_indirect.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                      C.POINTER(LightSet), C.POINTER(Bounce), C.POINTER(Indirect)]
+    L.bih_bounce_sample.argtypes = [u64, u32, u32, u32, u32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
@@ -236,7 +254,8 @@ def load():
                  "bih_host_register", "bih_host_unregister", "bih_render_history", "bih_trace_device", "bih_trace",
                  "bih_render_gbuffer_device", "bih_render_gbuffer", "bih_render_direct_device", "bih_render_direct",
                  "bih_render_lights_device", "bih_render_lights", "bih_render_area_lights_device",
-                 "bih_render_area_lights", "bih_area_light_sample"):
+                 "bih_render_area_lights", "bih_area_light_sample", "bih_render_indirect_device",
+                 "bih_render_indirect", "bih_bounce_sample"):
         getattr(L, name).restype = i32
     _lib = L
     return L

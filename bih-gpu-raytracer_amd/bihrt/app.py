@@ -18,6 +18,7 @@ usage:  python -m bihrt --mesh sponza --resources path/to/resources --frames 10 
             [--direct frames/d%04d.ppm [--sun X,Y,Z] [--sky K]]   (sky- and sun-lit grey preview per written frame)
                      [--lamp X,Y,Z[,W]]...            (point lights next to them; --sky 0: lamps only)
                      [--panel CX,CY,CZ,UX,UY,UZ,VX,VY,VZ[,W]]...   (area lights: soft shadows)
+                     [--bounce ALBEDO[,SKY]]          (one bounce of indirect light and a sky term; alone: sky only)
         python -m bihrt --obj file.obj ...     (explicit path)
         python -m bihrt --scene cornell|torus|soup[:N] ...   (built-in scenes)
 """
@@ -75,7 +76,7 @@ class App:
 
     def run(self, frames: int, out_pattern: str | None = None, rebuild: bool = True,
             every: int = 1, gbuffer_pattern: str | None = None, direct_pattern: str | None = None,
-            lights=None, lamps=None, panels=None):
+            lights=None, lamps=None, panels=None, bounce=None):
         """App::Run for a fixed number of frames: Renderer::Render each frame
         (BIH rebuild + render), optional PPM output; returns the frames.
         gbuffer_pattern: one .npz of the frame's G-buffer planes
@@ -84,9 +85,11 @@ class App:
         rgba plane) per written frame; lights = None: scenes.sky_dome(8).
         lamps: point lights {pos, weight} next to them (Renderer.render_lights).
         panels: area lights, (k, 10) rows {corner, edge_u, edge_v, weight}, next
-        to both (Renderer.render_area_lights)."""
+        to both (Renderer.render_area_lights).  bounce: (albedo, sky) adds one
+        bounce of indirect light and the sky term (Renderer.render_indirect);
+        lights = None is then no directional light."""
         assert self.renderer is not None, "load_models first"
-        if direct_pattern and lights is None:
+        if direct_pattern and lights is None and bounce is None:
             lights = scenes.sky_dome(8)
         imgs = []
         last = time.perf_counter()
@@ -115,7 +118,9 @@ class App:
                 d = os.path.dirname(path)
                 if d:
                     os.makedirs(d, exist_ok=True)
-                if panels is not None and len(panels):
+                if bounce is not None:
+                    shade = self.renderer.render_indirect(lights, lamps, panels, bounce, f, planes=("rgba",))["rgba"]
+                elif panels is not None and len(panels):
                     shade = self.renderer.render_area_lights(lights, lamps, panels, f, planes=("rgba",))["rgba"]
                 elif lamps is not None and len(lamps):
                     shade = self.renderer.render_lights(lights, lamps, f, planes=("rgba",))["rgba"]
@@ -150,6 +155,10 @@ def main(argv=None) -> int:
     ap.add_argument("--panel", action="append", default=None, metavar="CX,CY,CZ,UX,UY,UZ,VX,VY,VZ[,W]",
                     help="--direct: an area light corner + a*U + b*V of radiance W (default 1) that emits to the "
                          "side cross(U, V) points to; repeatable, up to 16")
+    ap.add_argument("--bounce", default=None, metavar="ALBEDO[,SKY]",
+                    help="--direct: add one bounce of indirect light of reflectance ALBEDO and a sky of irradiance "
+                         "SKY (default 1) for bounce rays that escape; --sky then defaults to 0, and without any "
+                         "light the image is the sky term alone (ambient occlusion)")
     ap.add_argument("--every", type=int, default=1, help="write every k-th frame")
     ap.add_argument("--no-rebuild", action="store_true",
                     help="build once (the reference rebuilds every frame)")
@@ -174,8 +183,19 @@ def main(argv=None) -> int:
         ap.error("--sun and --sky belong to --direct")
     if not a.direct and a.lamp:
         ap.error("--lamp belongs to --direct")
+    if not a.direct and a.bounce is not None:
+        ap.error("--bounce belongs to --direct")
+    bounce = None
     if a.direct:
-        a.sky = 8 if a.sky is None else a.sky
+        if a.bounce is not None:
+            try:
+                v = [float(x) for x in a.bounce.split(",")]
+            except ValueError:
+                v = []
+            if len(v) not in (1, 2):
+                ap.error("--bounce takes ALBEDO[,SKY]")
+            bounce = (v[0], v[1] if len(v) == 2 else 1.0)
+        a.sky = (8 if bounce is None else 0) if a.sky is None else a.sky
         sun = [float(x) for x in a.sun.split(",")] if a.sun else None
         if sun is not None and len(sun) != 3:
             ap.error("--sun takes X,Y,Z")
@@ -206,7 +226,7 @@ def main(argv=None) -> int:
         n_lamps = 0 if lamps is None else lamps.shape[0]
         n_panels = 0 if panels is None else panels.shape[0]
         n_dir = a.sky + (sun is not None)
-        if a.sky < 0 or n_dir + n_lamps + n_panels > 64 or n_dir + n_lamps + n_panels == 0:
+        if a.sky < 0 or n_dir + n_lamps + n_panels > 64 or (n_dir + n_lamps + n_panels == 0 and bounce is None):
             ap.error("--direct needs 1..64 lights (--sky K, --sun, --lamp, --panel)" if n_lamps or n_panels else
                      "--direct needs 1..64 lights (--sky K, --sun)")
         if a.sky:
@@ -218,5 +238,5 @@ def main(argv=None) -> int:
     app = App(a.width, a.height, a.spp, device=a.device)
     app.load_models(scene)
     app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every, gbuffer_pattern=a.gbuffer,
-            direct_pattern=a.direct, lights=lights, lamps=lamps, panels=panels)
+            direct_pattern=a.direct, lights=lights, lamps=lamps, panels=panels, bounce=bounce)
     return 0

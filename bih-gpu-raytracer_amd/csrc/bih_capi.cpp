@@ -24,6 +24,7 @@
 
 #include "../../include/bih.h"
 #include "bih_area.h"
+#include "bih_bounce.h"
 #include "bih_internal.h"
 
 // Up to kSlots renders through one tree may be in flight together (issued
@@ -42,8 +43,10 @@ constexpr int kRngBufs = kSlots + 1;
 constexpr bool kShareOneFrame = BIH_SHARE_ONE_FRAME != 0;
 constexpr size_t kEntryBytes = 16 * bih::kBinEntryF4;   // frustum-bin list entry
 constexpr size_t kTraceCursorBytes = 256;               // the trace cursor's allocation (u32 at 0: rays / tiles taken;
-                                                        // direct lighting: u64 at 8 items taken, u32 at 16 listed samples)
+                                                        // direct lighting: u64 at 8 items taken, u32 at 16 listed samples;
+                                                        // indirect lighting: u32 at 24 hit samples)
 constexpr size_t kDirectSampleBytes = 16 + 8 + 4;       // dr_mem per sample: record, facing mask, list entry
+constexpr size_t kIndirectSampleBytes = 16 + 4;         // in_mem per sample: bounce record, hit-list entry
 
 // Per-camera structures (bih_render.hip / bih_bins.hip): primary-ray records,
 // frustum bins and the tile queue of one camera.  A tree keeps kCamSets of
@@ -291,6 +294,16 @@ struct bih_tree {
     size_t dr_lit_cap = 0;           // samples
     char *dr_stage = nullptr;        // bih_render_direct's device planes
     size_t dr_stage_cap = 0;         // bytes
+    // Indirect-lighting renders (bih_render_indirect*) are a direct-lighting
+    // render with a second level: next to dr_mem per sample the bounce's
+    // record and the list of hit samples; the lit2 words of calls whose caller
+    // passes none; the host entry's device planes.  Same users, same waits.
+    char *in_mem = nullptr;
+    size_t in_cap = 0;               // samples (kIndirectSampleBytes each)
+    unsigned long long *in_lit2 = nullptr;
+    size_t in_lit2_cap = 0;          // samples
+    char *in_stage = nullptr;
+    size_t in_stage_cap = 0;         // bytes
 };
 
 namespace {
@@ -788,6 +801,9 @@ void bih_free(bih_tree *tr) {
     if (tr->dr_mem) (void)hipFree(tr->dr_mem);
     if (tr->dr_lit) (void)hipFree(tr->dr_lit);
     if (tr->dr_stage) (void)hipFree(tr->dr_stage);
+    if (tr->in_mem) (void)hipFree(tr->in_mem);
+    if (tr->in_lit2) (void)hipFree(tr->in_lit2);
+    if (tr->in_stage) (void)hipFree(tr->in_stage);
     if (tr->ev_trace) (void)hipEventDestroy(tr->ev_trace);
     for (int k = 0; k < kSlots; ++k) {
         if (tr->ev0[k]) (void)hipEventDestroy(tr->ev0[k]);
@@ -849,7 +865,8 @@ int bih_tree_get_info(const bih_tree *tr, bih_tree_info *info) {
                          (tr->wh_mem ? bih::whitted_bytes(tr->wh_rays) : 0) + tr->wh_mask_cap * 8 + tr->stamp_cap * 8 +
                          (tr->tq_cursor ? kTraceCursorBytes : 0) + tr->tq_spill_words * 4 + tr->tq_stage_cap +
                          tr->gb_mask_cap * 8 + tr->gb_scratch_cap * 4 + tr->gb_stage_cap +
-                         tr->dr_cap * kDirectSampleBytes + tr->dr_lit_cap * 8 + tr->dr_stage_cap;
+                         tr->dr_cap * kDirectSampleBytes + tr->dr_lit_cap * 8 + tr->dr_stage_cap +
+                         tr->in_cap * kIndirectSampleBytes + tr->in_lit2_cap * 8 + tr->in_stage_cap;
     info->build_ms = tr->build_ms;
     info->device_allocs = tr->allocs + tr->t.allocs + tr->back[0].allocs + tr->back[1].allocs;
     return BIH_OK;
@@ -2269,6 +2286,10 @@ struct DirectJob {
     uint32_t n_lights, n_dir;           // the area lights' {corner, weight}
     bih::AreaLights area;               // the last area.n lights are area lights (0: no area kernels)
     bih_direct planes;
+    // bih_render_indirect*: the second level (planes then holds lit, irradiance, rgba of `ind`)
+    bool indirect = false;
+    bih_bounce bounce;
+    bih_indirect ind;
 };
 
 // bih_render_gbuffer_device under the tree's lock, arguments checked, nrows > 0.
@@ -2353,11 +2374,28 @@ static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
         dp.lit = dj->planes.lit ? reinterpret_cast<unsigned long long *>(dj->planes.lit) : tr->dr_lit;
         dp.irradiance = dj->planes.irradiance;
         dp.rgba = dj->planes.rgba;
-        rc = bih::launch_direct(tr->t, a, dp, dj->lights, dj->n_lights, dj->n_dir, rec,
-                                reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
-                                tr->prm.trace_lds, tr->tq_cursor + 4,
-                                reinterpret_cast<unsigned long long *>(tr->tq_cursor + 2), tr->tq_spill,
-                                tr->tq_blocks, st, dj->area.n ? &dj->area : nullptr);
+        if (dj->indirect) {
+            // in_mem: bounce records, hit list
+            char *rec2 = tr->in_mem, *blist = rec2 + 16 * tr->in_cap;
+            bih::IndirectPlanes ip;
+            ip.lit = dp.lit;
+            ip.bounce = dj->ind.bounce;
+            ip.lit2 = dj->ind.lit2 ? reinterpret_cast<unsigned long long *>(dj->ind.lit2) : tr->in_lit2;
+            ip.irradiance = dp.irradiance;
+            ip.rgba = dp.rgba;
+            rc = bih::launch_indirect(tr->t, a, ip, dj->lights, dj->n_lights, dj->n_dir, dj->area, dj->bounce.albedo,
+                                      dj->bounce.sky, rec, rec2, reinterpret_cast<uint32_t *>(list),
+                                      reinterpret_cast<unsigned long long *>(face),
+                                      reinterpret_cast<uint32_t *>(blist), tr->prm.trace_lds, tr->tq_cursor + 4,
+                                      reinterpret_cast<unsigned long long *>(tr->tq_cursor + 2), tr->tq_cursor + 6,
+                                      tr->tq_spill, tr->tq_blocks, st);
+        } else {
+            rc = bih::launch_direct(tr->t, a, dp, dj->lights, dj->n_lights, dj->n_dir, rec,
+                                    reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
+                                    tr->prm.trace_lds, tr->tq_cursor + 4,
+                                    reinterpret_cast<unsigned long long *>(tr->tq_cursor + 2), tr->tq_spill,
+                                    tr->tq_blocks, st, dj->area.n ? &dj->area : nullptr);
+        }
     }
     // (a failed launch may have left work on st that uses the cursor: the event covers it)
     e = hipEventRecord(tr->ev_trace, st);
@@ -2416,17 +2454,21 @@ int bih_render_gbuffer(const bih_tree *ctr, const bih_camera *cam, uint32_t w, u
 // lights as a bih_light_set: the G-buffer's checks, then the lights and lit's
 // alignment (BIH_ERR_INVALID all, so one order serves the three headers').
 // None touches the tree or a device.  *rows: the rows of the call.
+// ind: the planes of bih_render_indirect* (pl then holds its lit, irradiance
+// and rgba): "all planes NULL" is about the five, ls may be NULL or empty.
 static int light_set_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                           const bih_rows *rows_in, const bih_light_set *ls, const bih_direct *pl, bih_rows *rows) {
+                           const bih_rows *rows_in, const bih_light_set *ls, const bih_direct *pl, bih_rows *rows,
+                           const bih_indirect *ind = nullptr) {
     // the G-buffer's "all planes NULL" is about the three planes here
     static float some_plane;
     bih_gbuffer g = {};
     if (pl && (pl->lit || pl->irradiance || pl->rgba)) g.depth = &some_plane;
+    if (ind && (ind->bounce || ind->lit2)) g.depth = &some_plane;
     const int rc = gbuffer_check(tr, cam, w, h, spp, rows_in, pl ? &g : nullptr, rows);
     if (rc) return rc;
     if (!ls) return BIH_ERR_INVALID;
     const uint64_t n = (uint64_t)ls->n_dir + ls->n_point + ls->n_area;
-    if (n == 0 || n > BIH_MAX_LIGHTS) return BIH_ERR_INVALID;
+    if ((n == 0 && !ind) || n > BIH_MAX_LIGHTS) return BIH_ERR_INVALID;
     if (ls->n_area > BIH_MAX_AREA_LIGHTS) return BIH_ERR_INVALID;
     if ((ls->n_dir && !ls->dir) || (ls->n_point && !ls->point) || (ls->n_area && !ls->area)) return BIH_ERR_INVALID;
     if ((uintptr_t)pl->lit & 7u) return BIH_ERR_INVALID;   // the lit words take 64-bit atomics
@@ -2473,13 +2515,17 @@ static int direct_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32
                          uint64_t seed, const bih_rows &rows, const DirectJob &dj, void *stream) {
     const size_t S = (size_t)rows.nrows * w * spp;
     const bool own_lit = !dj.planes.lit && tr->dr_lit_cap < S;
-    if ((tr->dr_cap < S || own_lit) && tr->trace_used) {
+    const bool own_lit2 = dj.indirect && !dj.ind.lit2 && tr->in_lit2_cap < S;
+    const bool own_in = dj.indirect && tr->in_cap < S;
+    if ((tr->dr_cap < S || own_lit || own_lit2 || own_in) && tr->trace_used) {
         // (the users of both buffers are direct-lighting launches: each ends before its ev_trace record)
         const hipError_t e = hipEventSynchronize(tr->ev_trace);
         if (e != hipSuccess) return map_hip((int)e);
     }
     int rc = own_lit ? grow(tr, &tr->dr_lit, &tr->dr_lit_cap, S, S * 8) : BIH_OK;
     if (rc == BIH_OK) rc = grow(tr, &tr->dr_mem, &tr->dr_cap, S, S * kDirectSampleBytes);
+    if (rc == BIH_OK && own_lit2) rc = grow(tr, &tr->in_lit2, &tr->in_lit2_cap, S, S * 8);
+    if (rc == BIH_OK && own_in) rc = grow(tr, &tr->in_mem, &tr->in_cap, S, S * kIndirectSampleBytes);
     if (rc) return rc;
     bih_gbuffer g = {};
     g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
@@ -2553,6 +2599,63 @@ int bih_render_area_lights(const bih_tree *tr, const bih_camera *cam, uint32_t w
                            uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                            const bih_direct *host_planes) {
     return render_light_set(tr, cam, w, h, spp, frame, seed, rows, ls, host_planes, nullptr, true);
+}
+
+// The body of the two indirect-lighting entries, as render_light_set.
+static int render_indirect(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                           uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light_set *ls_in,
+                           const bih_bounce *bounce, const bih_indirect *planes, void *stream, bool host) {
+    static const bih_light_set no_lights = {nullptr, 0, nullptr, 0, nullptr, 0};
+    const bih_light_set *ls = ls_in ? ls_in : &no_lights;
+    bih_rows rows;
+    bih_direct three = {};
+    if (planes) three = bih_direct{planes->lit, planes->irradiance, planes->rgba};
+    int rc = light_set_check(ctr, cam, w, h, spp, rows_in, ls, planes ? &three : nullptr, &rows, planes);
+    if (rc) return rc;
+    if (!bounce) return BIH_ERR_INVALID;
+    if (((uintptr_t)planes->lit2 & 7u) || ((uintptr_t)planes->bounce & 15u)) return BIH_ERR_INVALID;
+    if (rows.nrows == 0) return BIH_OK;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    DirectJob dj;
+    merge_light_set(ls, spp, frame, seed, &dj);
+    dj.planes = three;
+    dj.indirect = true;
+    dj.bounce = *bounce;
+    dj.ind = *planes;
+    if (!host) return direct_locked(tr, cam, w, h, spp, frame, seed, rows, dj, stream);
+    const size_t P = (size_t)rows.nrows * w;
+    Stage<5> sg{{planes->lit, planes->bounce, planes->lit2, planes->irradiance, planes->rgba},
+                {P * spp * 8, P * spp * sizeof(bih_hit), P * spp * 8, P * 4, P * 4}};
+    rc = sg.place(tr, &tr->in_stage, &tr->in_stage_cap);
+    if (rc) return rc;
+    dj.planes.lit = static_cast<uint64_t *>(sg.dev(0));
+    dj.ind.bounce = static_cast<bih_hit *>(sg.dev(1));
+    dj.ind.lit2 = static_cast<uint64_t *>(sg.dev(2));
+    dj.planes.irradiance = static_cast<float *>(sg.dev(3));
+    dj.planes.rgba = static_cast<uint32_t *>(sg.dev(4));
+    return sg.finish(tr, direct_locked(tr, cam, w, h, spp, frame, seed, rows, dj, nullptr));
+}
+
+int bih_render_indirect_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                               uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
+                               const bih_bounce *bounce, const bih_indirect *d_planes, void *stream) {
+    return render_indirect(tr, cam, w, h, spp, frame, seed, rows, ls, bounce, d_planes, stream, false);
+}
+
+int bih_render_indirect(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                        uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
+                        const bih_bounce *bounce, const bih_indirect *host_planes) {
+    return render_indirect(tr, cam, w, h, spp, frame, seed, rows, ls, bounce, host_planes, nullptr, true);
+}
+
+int bih_bounce_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s, const float n[3],
+                      float d[3]) {
+    static_assert(BIH_BOUNCE_SLOT == bih::kBounceSlot, "BIH_BOUNCE_SLOT / kBounceSlot");
+    if (!n || !d || spp == 0 || s >= spp) return BIH_ERR_INVALID;
+    bih::bounce_dir(bih::area_seed_hash(seed), pixel, frame * spp + s, n, d);
+    return BIH_OK;
 }
 
 int bih_area_light_sample(const bih_area_light *light, uint32_t j, uint64_t seed, uint32_t pixel, uint32_t frame,

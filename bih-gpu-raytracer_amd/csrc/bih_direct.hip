@@ -45,11 +45,15 @@
 // whose position Q differs per sample: Q is bih_area.h's hash of (seed, global
 // pixel, frame*spp + s, light), recomputed from the item's sample index in all
 // three kernels (area_dir), so a lane's walk state stays SRay's {o, d, i, k}.
+//
+// One-bounce indirect lighting (bih_render_indirect*) runs the stages twice,
+// with the bounce walk k_bounce between the levels: see IArgs below.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stddef.h>
 
 #include "bih_area.h"
+#include "bih_bounce.h"
 #include "bih_closest.h"
 #include "bih_internal.h"
 #include "bih_primary.h"
@@ -140,6 +144,41 @@ __device__ __forceinline__ void area_dir(const AArgs &ax, uint32_t j, const DLig
     l[2] = pt[2] - p[2];
 }
 
+// The 64-bit mask of the lights that face a point pt with normal nrm, the
+// point of sample s of global pixel gp (the area lights' Q).  KIND (compile
+// time): kDir, kPoint or kArea; ax: the area lights (kArea only).
+template <int KIND>
+__device__ __forceinline__ unsigned long long facing_mask(const DArgs &a, const AArgs *ax, const float *nrm,
+                                                          const float *pt, uint32_t gp, uint32_t s) {
+    unsigned long long face = 0ull;
+    const uint32_t n_dir = KIND != kDir ? a.n_dir : a.n_lights;
+    for (uint32_t k = 0; k < n_dir; ++k) {   // (k is uniform: the lights come as scalars)
+        const float c = (nrm[0] * a.lights[k].x + nrm[1] * a.lights[k].y) + nrm[2] * a.lights[k].z;
+        if (c > 0.0f) face |= 1ull << k;
+    }
+    if (KIND != kDir) {
+        const uint32_t n_lamp = KIND == kArea ? a.n_lights - ax->n_area : a.n_lights;
+        for (uint32_t k = n_dir; k < n_lamp; ++k) {
+            float l[3];
+            lamp_dir(a.lights[k], pt, l);
+            const float c = (nrm[0] * l[0] + nrm[1] * l[1]) + nrm[2] * l[2];
+            if (c > 0.0f) face |= 1ull << k;
+        }
+    }
+    if (KIND == kArea) {
+        const uint32_t k0 = a.n_lights - ax->n_area;
+        for (uint32_t j = 0; j < ax->n_area; ++j) {
+            float l[3];
+            area_dir(*ax, j, a.lights[k0 + j], gp, s, pt, l);
+            const float *nl = ax->panel[j].nl;
+            const float c = (nrm[0] * l[0] + nrm[1] * l[1]) + nrm[2] * l[2];
+            const float g = -((nl[0] * l[0] + nl[1] * l[1]) + nl[2] * l[2]);
+            if (c > 0.0f && g > 0.0f) face |= 1ull << (k0 + j);   // it faces the panel's emitting side
+        }
+    }
+    return face;
+}
+
 // KIND (compile time): kDir, kPoint or kArea; ax: the area lights (kArea only).
 template <int KIND>
 __device__ __forceinline__ void direct_setup_body(const DArgs &a, const AArgs *ax) {
@@ -162,31 +201,7 @@ __device__ __forceinline__ void direct_setup_body(const DArgs &a, const AArgs *a
             const float t = __uint_as_float(h.x);
             for (int k = 0; k < 3; ++k) pt[k] = a.cam[k] + t * d[k];
             dev::tri_normal(a.tris + 9ull * bi, nrm);
-            const uint32_t n_dir = KIND != kDir ? a.n_dir : a.n_lights;
-            for (uint32_t k = 0; k < n_dir; ++k) {   // (k is uniform: the lights come as scalars)
-                const float c = (nrm[0] * a.lights[k].x + nrm[1] * a.lights[k].y) + nrm[2] * a.lights[k].z;
-                if (c > 0.0f) face |= 1ull << k;
-            }
-            if (KIND != kDir) {
-                const uint32_t n_lamp = KIND == kArea ? a.n_lights - ax->n_area : a.n_lights;
-                for (uint32_t k = n_dir; k < n_lamp; ++k) {
-                    float l[3];
-                    lamp_dir(a.lights[k], pt, l);
-                    const float c = (nrm[0] * l[0] + nrm[1] * l[1]) + nrm[2] * l[2];
-                    if (c > 0.0f) face |= 1ull << k;
-                }
-            }
-            if (KIND == kArea) {
-                const uint32_t k0 = a.n_lights - ax->n_area, gp = y * a.w + x;
-                for (uint32_t j = 0; j < ax->n_area; ++j) {
-                    float l[3];
-                    area_dir(*ax, j, a.lights[k0 + j], gp, s, pt, l);
-                    const float *nl = ax->panel[j].nl;
-                    const float c = (nrm[0] * l[0] + nrm[1] * l[1]) + nrm[2] * l[2];
-                    const float g = -((nl[0] * l[0] + nl[1] * l[1]) + nl[2] * l[2]);
-                    if (c > 0.0f && g > 0.0f) face |= 1ull << (k0 + j);   // it faces the panel's emitting side
-                }
-            }
+            face = facing_mask<KIND>(a, ax, nrm, pt, y * a.w + x, s);
         }
         a.lit[i] = 0ull;
     }
@@ -333,9 +348,49 @@ __global__ void __launch_bounds__(kDT) k_shadow_area(const AArgs a) {
     shadow_body<LDS, kArea>(a.d, &a, s_node, s_min, s_max);
 }
 
+// A sample's sum over its lit lights l, k ascending, in the header's order:
+// bi its triangle, *recp its record ({P, bi} when l != 0), (gp, s) its global
+// pixel and sample (the area lights' Q).
+template <int KIND>
+__device__ __forceinline__ float sample_sum(const DArgs &a, const AArgs *ax, const DLight *s_light, const uint4 *recp,
+                                            uint32_t bi, unsigned long long l, uint32_t gp, uint32_t s) {
+    constexpr bool POINT = KIND != kDir;
+    float e = 0.0f;
+    if (l) {
+        float nrm[3];
+        dev::tri_normal(a.tris + 9ull * bi, nrm);
+        while (l) {   // k ascending over the lit bits
+            const uint32_t k = (uint32_t)__builtin_ctzll(l);
+            const DLight q = s_light[k];
+            l &= l - 1ull;
+            if (POINT && k >= a.n_dir) {
+                const uint4 rec = *recp;   // (a lit sample is a listed one: rec.xyz = P)
+                const float pt[3] = {__uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z)};
+                float L[3];
+                const bool area = KIND == kArea && k >= a.n_lights - ax->n_area;
+                if (area) area_dir(*ax, k - (a.n_lights - ax->n_area), q, gp, s, pt, L);
+                else lamp_dir(q, pt, L);
+                const float c = (nrm[0] * L[0] + nrm[1] * L[1]) + nrm[2] * L[2];
+                const float r2 = (L[0] * L[0] + L[1] * L[1]) + L[2] * L[2];
+                const float len = sqrtf(r2);
+                if (area) {   // the emitter's own cosine times its area: g = -(nl . L)
+                    const float *nl = ax->panel[k - (a.n_lights - ax->n_area)].nl;
+                    const float g = -((nl[0] * L[0] + nl[1] * L[1]) + nl[2] * L[2]);
+                    e = e + ((q.w * (c / len)) * (g / len)) / r2;
+                } else {
+                    e = e + (q.w * (c / len)) / r2;
+                }
+            } else {
+                const float c = (nrm[0] * q.x + nrm[1] * q.y) + nrm[2] * q.z;
+                e = e + q.w * c;
+            }
+        }
+    }
+    return e;
+}
+
 template <int KIND>
 __device__ __forceinline__ void direct_resolve_body(const DArgs &a, const AArgs *ax, DLight *s_light) {
-    constexpr bool POINT = KIND != kDir;
     if (threadIdx.x < a.n_lights) s_light[threadIdx.x] = a.lights[threadIdx.x];
     __syncthreads();
     const uint64_t P = (uint64_t)a.nrows * a.w;
@@ -352,38 +407,7 @@ __device__ __forceinline__ void direct_resolve_body(const DArgs &a, const AArgs 
         const uint64_t i = lp * a.spp + s;
         const uint32_t bi = a.rec[i].w;
         any = any || bi != kNoHit;
-        unsigned long long l = a.lit[i];
-        float e = 0.0f;
-        if (l) {
-            float nrm[3];
-            dev::tri_normal(a.tris + 9ull * bi, nrm);
-            while (l) {   // k ascending over the lit bits
-                const uint32_t k = (uint32_t)__builtin_ctzll(l);
-                const DLight q = s_light[k];
-                l &= l - 1ull;
-                if (POINT && k >= a.n_dir) {
-                    const uint4 rec = a.rec[i];   // (a lit sample is a listed one: rec.xyz = P)
-                    const float pt[3] = {__uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z)};
-                    float L[3];
-                    const bool area = KIND == kArea && k >= a.n_lights - ax->n_area;
-                    if (area) area_dir(*ax, k - (a.n_lights - ax->n_area), q, gp, s, pt, L);
-                    else lamp_dir(q, pt, L);
-                    const float c = (nrm[0] * L[0] + nrm[1] * L[1]) + nrm[2] * L[2];
-                    const float r2 = (L[0] * L[0] + L[1] * L[1]) + L[2] * L[2];
-                    const float len = sqrtf(r2);
-                    if (area) {   // the emitter's own cosine times its area: g = -(nl . L)
-                        const float *nl = ax->panel[k - (a.n_lights - ax->n_area)].nl;
-                        const float g = -((nl[0] * L[0] + nl[1] * L[1]) + nl[2] * L[2]);
-                        e = e + ((q.w * (c / len)) * (g / len)) / r2;
-                    } else {
-                        e = e + (q.w * (c / len)) / r2;
-                    }
-                } else {
-                    const float c = (nrm[0] * q.x + nrm[1] * q.y) + nrm[2] * q.z;
-                    e = e + q.w * c;
-                }
-            }
-        }
+        const float e = sample_sum<KIND>(a, ax, s_light, a.rec + i, bi, a.lit[i], gp, s);
         E = s == 0 ? e : E + e;
     }
     E = E / (float)a.spp;
@@ -409,21 +433,223 @@ __global__ void __launch_bounds__(kDSetupT) k_area_resolve(const AArgs a) {
     direct_resolve_body<kArea>(a.d, &a, s_light);
 }
 
-}  // namespace
+// ---- One-bounce indirect lighting (bih_render_indirect*) ----
+// Two levels of the stages above.  The primary level is bih_render_area_lights'
+// (k_indirect_setup is its setup, which also turns EVERY hit sample's record
+// into {P, sorted position} and lists the hit samples); k_bounce walks one
+// hashed, cosine-distributed ray per hit sample (bih_bounce.h) to its closest
+// hit and leaves {P2, sorted position} in rec2; k_indirect_setup2 is the setup
+// on those records; the secondary shadow pass is the primary's kernel, launched
+// on rec2 / lit2 (a secondary record keeps its sample's index, so sample_pixel
+// still gives the primary's (gp, s) for an area light's Q);
+// k_indirect_resolve sums both levels.  The setup and resolve kernels are the
+// kArea bodies for every light set (n_area, the lamps or all lights may be 0).
+struct IArgs {
+    AArgs a;                    // a.d: the primary level's rec, list, face, lit, count, cursor
+    uint4 *rec2;                // [P*spp]: the bounce hit's {P2, sorted position}; kNoHit: escaped, or a missed sample
+    unsigned long long *lit2;   // [P*spp]
+    uint4 *bounce;              // [P*spp] bih_hit, prim in file order, or null
+    uint32_t *blist;            // [P*spp]: hit samples
+    uint32_t *bcount;           // hit samples (zero at launch)
+    const uint32_t *tri_idx;    // sorted position -> file order
+    float albedo, sky;
+};
 
-int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes &p, const float *lights,
-                  uint32_t n_lights, uint32_t n_dir, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
-                  uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream,
-                  const AreaLights *area) {
-    const hipStream_t st = (hipStream_t)stream;
-    if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0 || n_lights == 0) return 0;
-    if (n_lights > kMaxLights || n_dir > n_lights) return (int)hipErrorInvalidValue;
+// The wave's lanes with `on` take consecutive slots from *count: one atomic
+// per wave (all lanes of the wave call it).
+__device__ __forceinline__ uint32_t wave_append(bool on, uint32_t *count) {
+    const unsigned long long m = __ballot(on);
+    const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    uint32_t first = 0;
+    if (m && (threadIdx.x & (dev::kLanes - 1u)) == 0) first = atomicAdd(count, (uint32_t)__popcll(m));
+    return __builtin_amdgcn_readfirstlane(first) + rk;
+}
+
+__global__ void __launch_bounds__(kDSetupT) k_indirect_setup(const IArgs ia) {
+    const DArgs &a = ia.a.d;
+    const uint64_t P = (uint64_t)a.nrows * a.w;
+    const uint64_t n = P * a.spp;
+    const uint64_t i = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
+    unsigned long long face = 0ull;
+    uint32_t bi = kNoHit;
+    if (i < n) {
+        const uint4 h = a.rec[i];
+        bi = h.w;
+        if (bi != kNoHit) {
+            const uint64_t lp = i / a.spp;
+            const uint32_t s = (uint32_t)(i - lp * a.spp);
+            const uint32_t lr = (uint32_t)(lp / a.w), x = (uint32_t)(lp - (uint64_t)lr * a.w);
+            const uint32_t y = dev::global_row(lr, a.row0, a.band_h, a.band_step);
+            float d[3], nrm[3], pt[3];
+            dev::primary_dir(a.cam, a.rng_in, P, lp, a.d_base, s, x, y, a.w, a.h, d);
+            const float t = __uint_as_float(h.x);
+            for (int k = 0; k < 3; ++k) pt[k] = a.cam[k] + t * d[k];
+            dev::tri_normal(a.tris + 9ull * bi, nrm);
+            face = facing_mask<kArea>(a, &ia.a, nrm, pt, y * a.w + x, s);
+            a.rec[i] = make_uint4(__float_as_uint(pt[0]), __float_as_uint(pt[1]), __float_as_uint(pt[2]), bi);
+        } else {   // a missed sample has no bounce: the miss record, lit2 = 0 (k_indirect_setup2)
+            ia.rec2[i] = make_uint4(0u, 0u, 0u, kNoHit);
+            if (ia.bounce) ia.bounce[i] = make_uint4(__float_as_uint(FLT_MAX), 0u, 0u, kNoHit);
+        }
+        a.lit[i] = 0ull;
+    }
+    const uint32_t jb = wave_append(bi != kNoHit, ia.bcount);
+    if (bi != kNoHit) ia.blist[jb] = (uint32_t)i;
+    const uint32_t j = wave_append(face != 0ull, a.count);
+    if (face != 0ull) {
+        a.list[j] = (uint32_t)i;
+        a.face[j] = face;
+    }
+}
+
+// A bounce ray: where it starts, whose it is, and its walk.
+struct BRay {
+    float o[3];
+    uint32_t i;                 // sample
+    ClosestRay w;
+};
+
+// The bounce's result: {P2, sorted position} for the secondary level, and the
+// caller's bih_hit (tray_write's: u, v from the accepted triangle's test once
+// more, prim in file order).
+__device__ __forceinline__ void bray_write(const IArgs &ia, const ClosestScene &s, const BRay &r) {
+    float t = FLT_MAX, u = 0.0f, v = 0.0f;
+    uint32_t prim = kNoHit;
+    uint4 q2 = make_uint4(0u, 0u, 0u, kNoHit);
+    if (r.w.bi != kNoHit) {
+        (void)dev::mt_tuv(s.tris + 9ull * r.w.bi, r.o, r.w.d, t, u, v);
+        prim = ia.tri_idx[r.w.bi];
+        q2 = make_uint4(__float_as_uint(r.o[0] + t * r.w.d[0]), __float_as_uint(r.o[1] + t * r.w.d[1]),
+                        __float_as_uint(r.o[2] + t * r.w.d[2]), r.w.bi);
+    }
+    ia.rec2[r.i] = q2;
+    if (ia.bounce) ia.bounce[r.i] = make_uint4(__float_as_uint(t), __float_as_uint(u), __float_as_uint(v), prim);
+}
+
+// The bounce walk, k_trace's shape: persistent one-wave blocks; work item = a
+// hit sample of blist, taken from the global cursor; a lane whose walk has
+// ended takes the next item while its wave-mates keep walking.  No ray goes
+// through memory: the origin is the sample's P, the direction bih_bounce.h's
+// hash about its triangle's normal.  The walk is bih_closest.h's closest walk.
+template <int LDS>
+__global__ void __launch_bounds__(kDT) k_bounce(const IArgs ia) {
+    __shared__ uint32_t s_node[LDS * kDT];
+    __shared__ float s_min[LDS * kDT];
+    __shared__ float s_max[LDS * kDT];
+    const DArgs &a = ia.a.d;
+    const uint32_t lane = threadIdx.x;
+    const dev::LaneStack<LDS> stk(s_node, s_min, s_max, a.spill);
+    const ClosestScene sc = dev::load_closest_scene(a.hdr, a.nodes, a.tris, a.dup);
+    const uint64_t n = *ia.bcount;
+    BRay r;
+    bool has = false;          // this lane walks a ray
+    bool more = true;          // (wave-uniform) the cursor may still be short of n
+    for (;;) {
+        const unsigned long long idle = __ballot(!has);
+        if (more && (__popcll(idle) >= kDRefill || idle == ~0ull)) {
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            unsigned long long first = 0;
+            if (lane == 0) first = atomicAdd(a.cursor, (unsigned long long)cnt);
+            first = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(first >> 32)) << 32) |
+                    __builtin_amdgcn_readfirstlane((uint32_t)first);
+            if (first + cnt >= n) more = false;
+            if (!has) {
+                const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (first + rk < n) {
+                    r.i = ia.blist[first + rk];
+                    const uint4 q = a.rec[r.i];   // {P, sorted position}: k_indirect_setup
+                    r.o[0] = __uint_as_float(q.x); r.o[1] = __uint_as_float(q.y); r.o[2] = __uint_as_float(q.z);
+                    float nrm[3];
+                    dev::tri_normal(a.tris + 9ull * q.w, nrm);
+                    uint32_t s;
+                    const uint32_t gp = sample_pixel(a, r.i, &s);
+                    bounce_dir(ia.a.hseed, gp, ia.a.fs0 + s, nrm, r.w.d);
+                    has = dev::closest_start<dev::kWalkClosest>(sc, r.w, r.o, kShadowTLo);
+                    if (!has) bray_write(ia, sc, r);   // missed the box / one-leaf tree: final
+                }
+            }
+        }
+        if (!__ballot(has)) {
+            if (!more) break;
+            continue;
+        }
+        if (has) {
+            bool fin = false;
+            for (int k = 0; k < kDSteps && !fin; ++k)
+                fin = dev::closest_step<dev::kWalkClosest>(sc, r.w, r.o, kShadowTLo, stk);
+            if (fin) {
+                bray_write(ia, sc, r);
+                has = false;
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kDSetupT) k_indirect_setup2(const IArgs ia) {
+    const DArgs &a = ia.a.d;
+    const uint64_t n = (uint64_t)a.nrows * a.w * a.spp;
+    const uint64_t i = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
+    unsigned long long face = 0ull;
+    if (i < n) {
+        const uint4 h = ia.rec2[i];
+        if (h.w != kNoHit && a.n_lights) {
+            const float pt[3] = {__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(h.z)};
+            float nrm[3];
+            dev::tri_normal(a.tris + 9ull * h.w, nrm);
+            uint32_t s;
+            const uint32_t gp = sample_pixel(a, (uint32_t)i, &s);
+            face = facing_mask<kArea>(a, &ia.a, nrm, pt, gp, s);
+        }
+        ia.lit2[i] = 0ull;
+    }
+    const uint32_t j = wave_append(face != 0ull, a.count);
+    if (face != 0ull) {
+        a.list[j] = (uint32_t)i;
+        a.face[j] = face;
+    }
+}
+
+__global__ void __launch_bounds__(kDSetupT) k_indirect_resolve(const IArgs ia) {
+    __shared__ DLight s_light[kMaxLights];
+    const DArgs &a = ia.a.d;
+    if (threadIdx.x < a.n_lights) s_light[threadIdx.x] = a.lights[threadIdx.x];
+    __syncthreads();
+    const uint64_t P = (uint64_t)a.nrows * a.w;
+    const uint64_t lp = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
+    if (lp >= P) return;
+    const uint32_t lr = (uint32_t)(lp / a.w), px = (uint32_t)(lp - (uint64_t)lr * a.w);
+    const uint32_t gp = dev::global_row(lr, a.row0, a.band_h, a.band_step) * a.w + px;
+    float E = 0.0f;
+    bool any = false;
+    for (uint32_t s = 0; s < a.spp; ++s) {
+        const uint64_t i = lp * a.spp + s;
+        const uint32_t bi = a.rec[i].w;
+        float e = 0.0f;
+        if (bi != kNoHit) {
+            any = true;
+            const float e_dir = sample_sum<kArea>(a, &ia.a, s_light, a.rec + i, bi, a.lit[i], gp, s);
+            const uint32_t bi2 = ia.rec2[i].w;
+            float e_ind = ia.sky;   // an escaped bounce
+            if (bi2 != kNoHit)
+                e_ind = ia.albedo * sample_sum<kArea>(a, &ia.a, s_light, ia.rec2 + i, bi2, ia.lit2[i], gp, s);
+            e = e_dir + e_ind;
+        }
+        E = s == 0 ? e : E + e;
+    }
+    E = E / (float)a.spp;
+    if (a.irradiance) a.irradiance[lp] = E;
+    if (a.rgba) {
+        const uint32_t g = (uint32_t)(int)fmaxf(0.0f, fminf(255.0f, 255.0f * E));
+        a.rgba[lp] = any ? (g | (g << 8) | (g << 16)) : kMissShade;
+    }
+}
+
+// The argument block of a call: the frame, the tree, the lights in slot order
+// and, with area lights, their panels (else only aa.d is filled and read).
+static void fill_args(AArgs &aa, const DeviceTree &t, const RenderArgs &ra, const float *lights, uint32_t n_lights,
+                      uint32_t n_dir, const AreaLights *area) {
     const uint32_t n_area = area ? area->n : 0u;
-    if (n_area > kMaxAreaLights || n_area > n_lights - n_dir) return (int)hipErrorInvalidValue;
-    static_assert(offsetof(DArgs, n_dir) + 4 == offsetof(DArgs, hdr) && offsetof(DArgs, n_dir) % 8 == 4,
-                  "n_dir sits in what was padding before the pointers: the argument block has not grown");
-    const bool point = n_dir < n_lights;   // else: bih_render_direct's kernels
-    AArgs aa;                              // (n_area == 0: only its DArgs is filled and passed on)
     DArgs &a = aa.d;
     for (int k = 0; k < 12; ++k) a.cam[k] = ra.cam[k];
     a.w = ra.w;
@@ -441,15 +667,6 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
     a.tris = t.tris_s;
     a.dup = t.dup_cnt;
     a.rng_in = ra.rng_in;
-    a.rec = reinterpret_cast<uint4 *>(rec);
-    a.list = list;
-    a.face = face;
-    a.lit = p.lit;
-    a.irradiance = p.irradiance;
-    a.rgba = p.rgba;
-    a.count = count;
-    a.cursor = cursor;
-    a.spill = spill;
     for (uint32_t k = 0; k < kMaxLights; ++k) {
         const bool on = k < n_lights;
         a.lights[k] = DLight{on ? lights[4 * k] : 0.0f, on ? lights[4 * k + 1] : 0.0f, on ? lights[4 * k + 2] : 0.0f,
@@ -466,6 +683,53 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
                 aa.panel[j].nl[c] = j < n_area ? area->uvn[j][6 + c] : 0.0f;
             }
     }
+}
+
+// The shadow pass over the samples listed in aa.d: the kernel of the call's
+// kinds of light (n_area, then point: n_dir < n_lights, else bih_render_direct's).
+static hipError_t launch_shadow(const AArgs &aa, uint32_t n_area, uint64_t n, uint32_t lds_slots, uint32_t max_blocks,
+                                hipStream_t st) {
+    const DArgs &a = aa.d;
+    const bool point = a.n_dir < a.n_lights;
+    // (the listed samples are counted on the device: the grid covers all of them)
+    const uint64_t need = (n * a.n_lights + kDT - 1) / kDT;
+    const dim3 grid((uint32_t)(need < max_blocks ? need : max_blocks)), block(kDT);
+    const bool small = lds_slots == (uint32_t)kTraceLdsTest;
+    if (n_area && small) hipLaunchKernelGGL((k_shadow_area<kTraceLdsTest>), grid, block, 0, st, aa);
+    else if (n_area) hipLaunchKernelGGL((k_shadow_area<kTraceLds>), grid, block, 0, st, aa);
+    else if (point && small) hipLaunchKernelGGL((k_shadow_lights<kTraceLdsTest>), grid, block, 0, st, a);
+    else if (point) hipLaunchKernelGGL((k_shadow_lights<kTraceLds>), grid, block, 0, st, a);
+    else if (small) hipLaunchKernelGGL((k_shadow<kTraceLdsTest>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_shadow<kTraceLds>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes &p, const float *lights,
+                  uint32_t n_lights, uint32_t n_dir, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
+                  uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream,
+                  const AreaLights *area) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0 || n_lights == 0) return 0;
+    if (n_lights > kMaxLights || n_dir > n_lights) return (int)hipErrorInvalidValue;
+    const uint32_t n_area = area ? area->n : 0u;
+    if (n_area > kMaxAreaLights || n_area > n_lights - n_dir) return (int)hipErrorInvalidValue;
+    static_assert(offsetof(DArgs, n_dir) + 4 == offsetof(DArgs, hdr) && offsetof(DArgs, n_dir) % 8 == 4,
+                  "n_dir sits in what was padding before the pointers: the argument block has not grown");
+    const bool point = n_dir < n_lights;   // else: bih_render_direct's kernels
+    AArgs aa;                              // (n_area == 0: only its DArgs is filled and passed on)
+    DArgs &a = aa.d;
+    fill_args(aa, t, ra, lights, n_lights, n_dir, area);
+    a.rec = reinterpret_cast<uint4 *>(rec);
+    a.list = list;
+    a.face = face;
+    a.lit = p.lit;
+    a.irradiance = p.irradiance;
+    a.rgba = p.rgba;
+    a.count = count;
+    a.cursor = cursor;
+    a.spill = spill;
     hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), st);
     if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return (int)e;
@@ -476,23 +740,91 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
     else hipLaunchKernelGGL(k_direct_setup, sgrid, dim3(kDSetupT), 0, st, a);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    // (the listed samples are counted on the device: the grid covers all of them)
-    const uint64_t need = (n * n_lights + kDT - 1) / kDT;
-    const dim3 grid((uint32_t)(need < max_blocks ? need : max_blocks)), block(kDT);
-    const bool small = lds_slots == (uint32_t)kTraceLdsTest;
-    if (n_area && small) hipLaunchKernelGGL((k_shadow_area<kTraceLdsTest>), grid, block, 0, st, aa);
-    else if (n_area) hipLaunchKernelGGL((k_shadow_area<kTraceLds>), grid, block, 0, st, aa);
-    else if (point && small) hipLaunchKernelGGL((k_shadow_lights<kTraceLdsTest>), grid, block, 0, st, a);
-    else if (point) hipLaunchKernelGGL((k_shadow_lights<kTraceLds>), grid, block, 0, st, a);
-    else if (small) hipLaunchKernelGGL((k_shadow<kTraceLdsTest>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_shadow<kTraceLds>), grid, block, 0, st, a);
-    e = hipGetLastError();
+    e = launch_shadow(aa, n_area, n, lds_slots, max_blocks, st);
     if (e != hipSuccess) return (int)e;
     if (p.irradiance || p.rgba) {
         const dim3 rgrid((uint32_t)((P + kDSetupT - 1) / kDSetupT));
         if (n_area) hipLaunchKernelGGL(k_area_resolve, rgrid, dim3(kDSetupT), 0, st, aa);
-        else if (point) hipLaunchKernelGGL(k_lights_resolve, rgrid, dim3(kDSetupT), 0, st, a);
-        else hipLaunchKernelGGL(k_direct_resolve, rgrid, dim3(kDSetupT), 0, st, a);
+        else if (point) hipLaunchKernelGGL(k_lights_resolve, rgrid, dim3(kDSetupT), 0, st, aa.d);
+        else hipLaunchKernelGGL(k_direct_resolve, rgrid, dim3(kDSetupT), 0, st, aa.d);
+        e = hipGetLastError();
+    }
+    return (int)e;
+}
+
+// The call's passes, each behind the one before on the stream: the primary
+// setup, the primary shadow pass, the bounce walk, the secondary setup, the
+// secondary shadow pass (the primary's kernels on the secondary records; list,
+// face, count and cursor are the primary's, free again), the resolve.
+int launch_indirect(const DeviceTree &t, const RenderArgs &ra, const IndirectPlanes &p, const float *lights,
+                    uint32_t n_lights, uint32_t n_dir, const AreaLights &area, float albedo, float sky, void *rec,
+                    void *rec2, uint32_t *list, unsigned long long *face, uint32_t *blist, uint32_t lds_slots,
+                    uint32_t *count, unsigned long long *cursor, uint32_t *bcount, uint32_t *spill,
+                    uint32_t max_blocks, void *stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0) return 0;
+    if (n_lights > kMaxLights || n_dir > n_lights) return (int)hipErrorInvalidValue;
+    if (area.n > kMaxAreaLights || area.n > n_lights - n_dir) return (int)hipErrorInvalidValue;
+    static_assert(sizeof(IArgs) <= 4096, "kernel arguments");
+    IArgs ia;
+    fill_args(ia.a, t, ra, lights, n_lights, n_dir, &area);
+    ia.a.n_area = area.n;      // (fill_args leaves the three alone without an area light)
+    ia.a.hseed = area.hseed;
+    ia.a.fs0 = area.fs0;
+    DArgs &a = ia.a.d;
+    a.rec = reinterpret_cast<uint4 *>(rec);
+    a.list = list;
+    a.face = face;
+    a.lit = p.lit;
+    a.irradiance = p.irradiance;
+    a.rgba = p.rgba;
+    a.count = count;
+    a.cursor = cursor;
+    a.spill = spill;
+    ia.rec2 = reinterpret_cast<uint4 *>(rec2);
+    ia.lit2 = p.lit2;
+    ia.bounce = reinterpret_cast<uint4 *>(p.bounce);
+    ia.blist = blist;
+    ia.bcount = bcount;
+    ia.tri_idx = t.vals;
+    ia.albedo = albedo;
+    ia.sky = sky;
+    const uint64_t P = (uint64_t)ra.nrows * ra.w, n = P * ra.spp;
+    const dim3 sgrid((uint32_t)((n + kDSetupT - 1) / kDSetupT));
+    const auto reset = [&](bool with_bcount) {
+        hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), st);
+        if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), st);
+        if (e == hipSuccess && with_bcount) e = hipMemsetAsync(bcount, 0, sizeof(uint32_t), st);
+        return e;
+    };
+    hipError_t e = reset(true);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_indirect_setup, sgrid, dim3(kDSetupT), 0, st, ia);
+    e = hipGetLastError();
+    if (e == hipSuccess && n_lights) e = launch_shadow(ia.a, area.n, n, lds_slots, max_blocks, st);
+    if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), st);
+    if (e != hipSuccess) return (int)e;
+    {
+        const uint64_t need = (n + kDT - 1) / kDT;
+        const dim3 grid((uint32_t)(need < max_blocks ? need : max_blocks)), block(kDT);
+        if (lds_slots == (uint32_t)kTraceLdsTest) hipLaunchKernelGGL((k_bounce<kTraceLdsTest>), grid, block, 0, st, ia);
+        else hipLaunchKernelGGL((k_bounce<kTraceLds>), grid, block, 0, st, ia);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = reset(false);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_indirect_setup2, sgrid, dim3(kDSetupT), 0, st, ia);
+    e = hipGetLastError();
+    if (e == hipSuccess && n_lights) {
+        AArgs a2 = ia.a;       // the secondary level: its records and lit words
+        a2.d.rec = ia.rec2;
+        a2.d.lit = ia.lit2;
+        e = launch_shadow(a2, area.n, n, lds_slots, max_blocks, st);
+    }
+    if (e != hipSuccess) return (int)e;
+    if (p.irradiance || p.rgba) {
+        const dim3 rgrid((uint32_t)((P + kDSetupT - 1) / kDSetupT));
+        hipLaunchKernelGGL(k_indirect_resolve, rgrid, dim3(kDSetupT), 0, st, ia);
         e = hipGetLastError();
     }
     return (int)e;

@@ -394,6 +394,25 @@ int launch_direct(const DeviceTree &t, const RenderArgs &a, const DirectPlanes &
                   uint32_t n_lights, uint32_t n_dir, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
                   uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream,
                   const AreaLights *area = nullptr);
+// One-bounce indirect lighting (bih_direct.hip), behind a launch_gbuffer as
+// launch_direct: the primary level as there (n_lights may be 0: sky only),
+// then per hit sample one bounce ray (bih_bounce.h; area.hseed and area.fs0
+// are read whatever area.n), its hit lit by the same lights, and the sums of
+// both levels.  rec2 (16 bytes per sample) and blist (4) are the call's own
+// next to launch_direct's rec, list and face; lit and lit2 are never null;
+// bcount is a zeroed-by-the-call word as count.
+struct IndirectPlanes {
+    unsigned long long *lit = nullptr;
+    void *bounce = nullptr;             // bih_hit[P*spp], prim in file order, or null
+    unsigned long long *lit2 = nullptr;
+    float *irradiance = nullptr;
+    uint32_t *rgba = nullptr;
+};
+int launch_indirect(const DeviceTree &t, const RenderArgs &a, const IndirectPlanes &p, const float *lights,
+                    uint32_t n_lights, uint32_t n_dir, const AreaLights &area, float albedo, float sky, void *rec,
+                    void *rec2, uint32_t *list, unsigned long long *face, uint32_t *blist, uint32_t lds_slots,
+                    uint32_t *count, unsigned long long *cursor, uint32_t *bcount, uint32_t *spill,
+                    uint32_t max_blocks, void *stream);
 int launch_rng_init(uint32_t *rng, uint32_t w, uint32_t row0, uint32_t nrows, uint32_t band_h,
                     uint32_t band_step, uint64_t seed, uint64_t skip, int device, void *stream);
 // dst = src's per-pixel state advanced by `steps` draws (planes of `pixels`; dst may be src)

@@ -39,7 +39,8 @@ extern "C" {
                                4: bih_host_register / bih_host_unregister, bih_render_history;
                                (4, added since: bih_trace*, bih_render_gbuffer*, BIH_PARAM_GBUFFER_MASK,
                                 bih_render_direct*, BIH_QUERY_T_HI and bih_ray.t_hi, bih_render_lights*,
-                                bih_render_area_lights*, bih_area_light_sample) */
+                                bih_render_area_lights*, bih_area_light_sample, bih_render_indirect*,
+                                bih_bounce_sample) */
 
 /* error codes */
 #define BIH_OK               0
@@ -617,6 +618,104 @@ int bih_render_area_lights(const bih_tree *tree, const bih_camera *camera, uint3
  * s >= spp -> BIH_ERR_INVALID. */
 int bih_area_light_sample(const bih_area_light *light, uint32_t j, uint64_t seed, uint32_t pixel,
                           uint32_t frame, uint32_t spp, uint32_t s, float q[3]);
+
+/* One-bounce indirect lighting with a sky (ambient) term on top of
+ * bih_render_area_lights, in one call: per hit sample
+ * one hashed, cosine-distributed bounce ray, its closest hit lit by the same
+ * lights under the same rules; a bounce ray that escapes the scene collects the
+ * sky.  No new walk rule.  With no lights at all it is the ambient-occlusion
+ * render.
+ *
+ * Any plane may be NULL (not written); all five NULL -> BIH_ERR_INVALID.
+ * P = rows->nrows * w local pixels, sample index p*spp + s.
+ *
+ * Semantics.  Every f32 operation is one separately rounded IEEE operation.
+ * The primary sample:
+ *  - Sample (x, y, s) of frame f, global pixel gp = y*w + x, has
+ *    bih_render_area_lights' hit {t, u, v, prim}, hit point P, normal n, `lit`
+ *    word and direct sum e_dir, exactly as that call defines them.
+ *  - `lit` is byte-identical to bih_render_area_lights' `lit` for the same light
+ *    set, whatever `bounce` holds.
+ *  - A missed sample has lit = 0, bounce = the miss record, lit2 = 0 and e_s = 0.
+ * Bounce direction:
+ *  - mix is the area lights' mix.
+ *      h = mix((uint32_t)seed); h = mix(h ^ (uint32_t)(seed>>32)); h = mix(h ^ gp);
+ *      h = mix(h ^ (frame*spp + s)); h = mix(h ^ BIH_BOUNCE_SLOT);
+ *      ha = mix(h + 0x9E3779B9); hb = mix(h + 0x3C6EF372);
+ *      a = (float)(ha>>8) * 0x1p-24f; b = (float)(hb>>8) * 0x1p-24f   (both exact)
+ *  - A point w of the unit sphere, without library trigonometry (host and
+ *    device sinf differ, so none is used):
+ *      z = 1.0f - 2.0f*a; r = sqrtf(fmaxf(0.0f, 1.0f - z*z));
+ *      b4 = 4.0f*b; q = (int)b4 (0..3); f = b4 - (float)q (exact);
+ *      S(x) = ((((C9*x2 + C7)*x2 + C5)*x2 + C3)*x2 + C1) * x  with x2 = x*x,
+ *      C1 = 0x1.921fb6p+0f, C3 = -0x1.4abbcep-1f, C5 = 0x1.466bc6p-4f,
+ *      C7 = -0x1.32d2ccp-8f, C9 = 0x1.507834p-13f
+ *    (the f32 values nearest to +-(pi/2)^k / k!: S is the Taylor sine of
+ *    (pi/2)x, within 3.8e-6 of sin on [0, 1]);
+ *      sn = S(f); cs = S(1.0f - f)   (1 - f is exact);
+ *      (cx, sx) = (cs, sn) for q = 0, (-sn, cs) for 1, (-cs, -sn) for 2,
+ *      (sn, -cs) for 3;  w = (r*cx, r*sx, z).
+ *  - B[c] = n[c] + w[c].  With n of unit length B is cosine-distributed about
+ *    n.  bih_bounce_sample returns exactly this B.  A (near-)zero B is legal, as
+ *    for any ray query.
+ * Bounce record:
+ *  - bounce[i] is exactly the bih_hit of bih_trace(.., BIH_QUERY_CLOSEST) for
+ *    {o = P, t_lo = BIH_SHADOW_T_LO, d = B}; prim is in file order, the miss
+ *    record marks an escape.  Triangles are one-sided, so the originating
+ *    triangle (B.n >= 0) cannot stop its own ray, and an accepted triangle
+ *    faces the ray.
+ * Escaped bounce: e_ind = sky.
+ * Bounce hit {t2, prim2}:
+ *  - P2[c] = P[c] + t2*B[c]; n2 = the `normal` formula on triangle prim2.
+ *  - lit2 and e2 are the lit word and per-sample sum bih_render_area_lights'
+ *    rules give with P2, n2 in place of P, n: the same facing tests,
+ *    BIH_QUERY_OCCLUDED for directional lights, BIH_QUERY_OCCLUDED_WITHIN with
+ *    t_hi = 1 for lamps and panels from o = P2, the same contributions in
+ *    ascending k.  An area light's point Q is the same Q the sample's primary
+ *    hit uses (same gp, frame*spp + s, j).
+ *  - e_ind = albedo * e2 (one multiply).
+ * Sums: e_s = e_dir + e_ind (one add).  E, rgba and the miss shade are
+ * bih_render_direct's.
+ * Sky only: lights may be NULL or empty (all three counts 0).  Then lit = lit2
+ * = 0, no shadow kernel runs, and E = sky x (escaped bounce rays of the pixel)
+ * / spp: the ambient-occlusion render.
+ * Errors, in bih_render_area_lights' order with these changes: "all planes
+ * NULL" is about the five planes; lights == NULL and an empty set are legal;
+ * counts above the limits and a NULL array with a non-zero count stay
+ * BIH_ERR_INVALID; then lit not 8-byte aligned, bounce (the bih_bounce) ==
+ * NULL, lit2 not 8-byte aligned or the bounce plane not 16-byte aligned ->
+ * BIH_ERR_INVALID; nrows == 0 -> BIH_OK, nothing launched.
+ * RNG accounting, ordering (the ev_trace chain, rebuilds) and memory are
+ * bih_render_direct's.  Scratch: next to its 28 bytes per sample 20 more (the
+ * bounce's record and a hit-list entry), and 8 more (the lit2 word) once a call
+ * passes no `lit2`.  After the first call of a shape, light count and choice
+ * of planes further calls allocate nothing. */
+#define BIH_BOUNCE_SLOT 0x80000000u   /* the hash slot of the bounce direction: no area light index takes it */
+typedef struct bih_bounce {
+    float albedo;   /* the diffuse reflectance applied to the bounced light */
+    float sky;      /* the irradiance an unoccluded sky gives: an escaped bounce ray contributes it */
+} bih_bounce;
+typedef struct bih_indirect {
+    uint64_t *lit;         /* u64[P*spp] the primary hit's lit word; 8-byte aligned */
+    bih_hit  *bounce;      /* bih_hit[P*spp] the bounce ray's closest hit; 16-byte aligned */
+    uint64_t *lit2;        /* u64[P*spp] the bounce hit's lit word; 8-byte aligned */
+    float    *irradiance;  /* f32[P] */
+    uint32_t *rgba;        /* u32[P] 0x00BBGGRR */
+} bih_indirect;
+int bih_render_indirect_device(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                               uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                               const bih_light_set *lights, const bih_bounce *bounce,
+                               const bih_indirect *d_planes, void *stream);  /* async; bih_sync waits */
+int bih_render_indirect(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                        uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                        const bih_light_set *lights, const bih_bounce *bounce,
+                        const bih_indirect *host_planes);                    /* synchronous, host memory */
+/* Host only, no device: the bounce direction B that sample s of global pixel
+ * `pixel` = y*w + x uses in frame `frame` of a render with `spp` samples per
+ * pixel, for the normal n.  n or d NULL, spp == 0 or s >= spp ->
+ * BIH_ERR_INVALID. */
+int bih_bounce_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s,
+                      const float n[3], float d[3]);
 
 /* The drop-in host loop (bih_render into a caller's framebuffer) ends in a
  * device-to-host copy of w*h*4 bytes.  Into pageable memory the runtime
