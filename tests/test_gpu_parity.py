@@ -41,7 +41,8 @@ def test_build_matches_oracle_edge(name, gpu, bihrt_mod, oracle_mod):
                                     (1_000_000, 1), (10_000_000, 1)])
 def test_build_matches_oracle_soup(n, seed, gpu, bihrt_mod, oracle_mod):
     """Every canonical array bit-equal, up to SURVEY 8f-1's 10M triangles
-    (where the segment tree of k_seg_up takes 3 launches)."""
+    (9766 k_seg_build blocks, past the last-block hand-off, so issue_build
+    launches k_seg_up twice: 10 blocks for levels 11..20, then 1 for the rest)."""
     tris = bihrt_mod.scenes.soup(n, seed=seed)
     g = bihrt_mod.GPUArrayManager(tris)
     ot = oracle_mod.OracleTree(tris)

@@ -88,8 +88,12 @@ def scene(name):
 
 def expected(name, o, d, tlo):
     """The oracle's hit records (HIT_DTYPE) of rays (o, d, tlo) in scene `name`."""
+    return expected_of(*scene(name), o, d, tlo)
+
+
+def expected_of(tris, ot, o, d, tlo):
+    """The same for the soup `tris` and its OracleTree `ot`."""
     import bihrt
-    tris, ot = scene(name)
     n = o.shape[0]
     tlo = np.broadcast_to(np.asarray(tlo, F32), (n,))
     t = np.empty(n, F32)
