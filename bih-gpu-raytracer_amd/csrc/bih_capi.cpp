@@ -8,9 +8,11 @@
 //
 // Shared by the entries: grow (every buffer of a tree that follows the calls'
 // shapes), Stage (the host entries' device copies), wait_tree (a launch after
-// the last rebuild), base_render_args / finish_slot (the Whitted and G-buffer
-// launches), and light_set_check / render_light_set (the one path of the six
-// direct-lighting entries).
+// the last rebuild), Frame (what every render entry is asked for), resolve_rows
+// (the row rule), begin_slot / slot_args / finish_slot (a render slot taken
+// outside the camera sets: Whitted and G-buffer launches), mask_prepass (their
+// any-hit pass through the frustum bins), and light_set_check /
+// render_light_set (the one path of the six direct-lighting entries).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,9 +44,7 @@ constexpr int kRngBufs = kSlots + 1;
 // one-frame renders also take the shared grid while another render is in flight
 constexpr bool kShareOneFrame = BIH_SHARE_ONE_FRAME != 0;
 constexpr size_t kEntryBytes = 16 * bih::kBinEntryF4;   // frustum-bin list entry
-constexpr size_t kTraceCursorBytes = 256;               // the trace cursor's allocation (u32 at 0: rays / tiles taken;
-                                                        // direct lighting: u64 at 8 items taken, u32 at 16 listed samples;
-                                                        // indirect lighting: u32 at 24 hit samples)
+using bih::kTraceCursorBytes;                           // the work area's cursor block (bih::WorkArea)
 constexpr size_t kDirectSampleBytes = 16 + 8 + 4;       // dr_mem per sample: record, facing mask, list entry
 constexpr size_t kIndirectSampleBytes = 16 + 4;         // in_mem per sample: bounce record, hit-list entry
 
@@ -57,6 +57,12 @@ constexpr size_t kIndirectSampleBytes = 16 + 4;         // in_mem per sample: bo
 #define BIH_CAM_SETS 3
 #endif
 constexpr int kCamSets = BIH_CAM_SETS;
+// A boolean switch of the environment (A/B; each caller reads its own once):
+// off when the variable is exactly "0".
+static bool env_off(const char *name) {
+    const char *e = getenv(name);
+    return e && strcmp(e, "0") == 0;
+}
 // sets in use (BIH_CAM_SETS=1..kCamSets in the environment: A/B)
 static int cam_sets() {
     static const int n = [] {
@@ -158,6 +164,31 @@ static uint32_t dbg_bits() {
 }
 #endif
 
+// What a render entry is asked for: the camera, the image, the frame of the
+// seed's sequence and the rows of the call.  An entry states it as it was
+// called, rows empty; its checks resolve the rows (resolve_rows).
+struct Frame {
+    const bih_camera *cam;
+    uint32_t w, h, spp, frame;
+    uint64_t seed;
+    bih_rows rows;
+    size_t pixels() const { return (size_t)rows.nrows * w; }
+    uint64_t samples() const { return (uint64_t)pixels() * spp; }
+    // packet tiles of the call's rows (spp a power of two <= 64)
+    bih::Tiles shape() const { return bih::tiles_of(w, rows.nrows, spp); }
+    uint64_t tiles() const { return shape().count(); }
+    uint32_t tiles_x() const { return shape().x; }
+};
+
+// What the XORWOW ring's per-pixel state depends on besides the frame (no
+// padding: compared as bytes).
+struct RngKey {
+    uint32_t w, spp;
+    bih_rows rows;
+    uint64_t seed;
+};
+static_assert(sizeof(RngKey) == 32, "RngKey is compared with memcmp");
+
 struct bih_tree {
     bih::DeviceTree t;
     // Rebuilds write the oldest of three tree buffers and rotate (back[0] =
@@ -213,8 +244,7 @@ struct bih_tree {
     uint32_t *fb = nullptr;
     size_t fb_cap = 0;               // pixels
     bool rng_valid = false;
-    uint32_t key_w = 0, key_spp = 0, key_row0 = 0, key_nrows = 0, key_bh = 0, key_bs = 0;
-    uint64_t key_seed = 0;
+    RngKey key = {};                 // what the ring's state was seeded for (rng_valid)
     uint32_t next_frame = 0;
     // stamped XORWOW state (RenderArgs::stamps): frustum-bin launches on one
     // stream read and write per-tile state in ring buffers st_a and st_a + 1,
@@ -430,14 +460,6 @@ int wait_set_readers(bih_tree *tr, int c, hipStream_t st) {
     return BIH_OK;
 }
 
-// Cost-ordered tile queue of the packet kernel (bih::launch_chunk_order):
-// the chunks of this render start in descending order of the cycles their
-// longest packet
-// took in the last render of the same slot and geometry (frame f - kSlots in
-// a frame sequence), so the slow part of the image starts first and the frame
-// does not end on one long packet.  The order never changes a pixel.
-// Called after `st` waits for the slot's previous render.  BIH_CHUNK_ORDER=0
-// turns it off (tuning / A-B).
 // The any-hit walk's shortcut passes (k_render_packet_asm, bih_render.hip):
 // 2 = hit shortcut + miss proof (default), BIH_FAST=1 the hit shortcut only,
 // BIH_FAST=0 neither (A-B).  They never change a pixel.
@@ -451,12 +473,17 @@ int fast_enabled() {
     return level;
 }
 
-int prepare_chunk_order(bih_tree *tr, uint32_t w, uint32_t spp, const bih_rows &rows, int slot,
-                        hipStream_t st, bih::RenderArgs &a) {
-    static const bool enabled = [] {
-        const char *e = getenv("BIH_CHUNK_ORDER");
-        return !(e && strcmp(e, "0") == 0);
-    }();
+// Cost-ordered tile queue of the packet kernel (bih::launch_chunk_order):
+// the chunks of this render start in descending order of the cycles their
+// longest packet took in the last render of the same slot and geometry (frame
+// f - kSlots in a frame sequence), so the slow part of the image starts first
+// and the frame does not end on one long packet.  The order never changes a pixel.
+// Called after `st` waits for the slot's previous render.  BIH_CHUNK_ORDER=0
+// turns it off (tuning / A-B).
+int prepare_chunk_order(bih_tree *tr, const Frame &f, int slot, hipStream_t st, bih::RenderArgs &a) {
+    static const bool enabled = !env_off("BIH_CHUNK_ORDER");
+    const uint32_t w = f.w, spp = f.spp;
+    const bih_rows &rows = f.rows;
     a.chunk_order = nullptr;
     a.chunk_cost = nullptr;
     uint32_t cx = 0;
@@ -544,10 +571,7 @@ int finish_build(bih_tree *tr) {
         // ~15 short kernels leaves most of the GPU idle); each render still
         // waits for its own frame's tree.  BIH_BUILD_PIPE=0: one stream (A/B).
         async = tr->owns_soup || tr->prm.static_soup;
-        static const bool pipe = [] {
-            const char *v = getenv("BIH_BUILD_PIPE");
-            return !(v && v[0] == '0');
-        }();
+        static const bool pipe = !env_off("BIH_BUILD_PIPE");
         if (async && pipe && (tr->bpar++ & 1u)) {
             if (!tr->bstream && hipStreamCreateWithFlags(&tr->bstream, hipStreamNonBlocking) != hipSuccess) {
                 (void)hipGetLastError();
@@ -957,10 +981,7 @@ static int ensure_rng(bih_tree *tr, size_t P, hipStream_t st) {
 constexpr uint32_t kStampRun = 3;
 
 static bool share_alternating() {
-    static const bool on = [] {
-        const char *e = getenv("BIH_SHARE_ALTERNATING");
-        return !(e && strcmp(e, "0") == 0);
-    }();
+    static const bool on = !env_off("BIH_SHARE_ALTERNATING");
     return on;
 }
 
@@ -998,10 +1019,7 @@ static void note_stream(bih_tree *tr, int slot, hipStream_t st) {
 }
 
 static bool stamps_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("BIH_STAMPED");
-        return !(e && strcmp(e, "0") == 0);
-    }();
+    static const bool on = !env_off("BIH_STAMPED");
     return on;
 }
 
@@ -1071,10 +1089,9 @@ struct RngGuard {
     }
 };
 
-static bool rng_same_px(const bih_tree *tr, uint32_t w, uint32_t spp, uint64_t seed, const bih_rows &rows) {
-    return tr->rng_valid && tr->key_w == w && tr->key_spp == spp && tr->key_seed == seed &&
-           tr->key_row0 == rows.row0 && tr->key_nrows == rows.nrows && tr->key_bh == rows.band_h &&
-           tr->key_bs == rows.band_step;
+static bool rng_same_px(const bih_tree *tr, const Frame &f) {
+    const RngKey k = {f.w, f.spp, f.rows, f.seed};
+    return tr->rng_valid && memcmp(&k, &tr->key, sizeof k) == 0;
 }
 
 // Leaves stamped mode: every pixel's state at next_frame into a ring buffer
@@ -1086,18 +1103,18 @@ static int unstamp(bih_tree *tr, hipStream_t st) {
     const int c = (tr->st_a + 2) % kRngBufs;
     tr->rng_cur = c;
     const int e = bih::launch_rng_sync(tr->stamps, rng_buf(tr, tr->st_a), rng_buf(tr, (tr->st_a + 1) % kRngBufs),
-                                       rng_buf(tr, c), tr->key_w, tr->key_nrows, tr->key_spp, tr->next_frame,
+                                       rng_buf(tr, c), tr->key.w, tr->key.rows.nrows, tr->key.spp, tr->next_frame,
                                        0xFFFFu, tr->t.device, st);
     if (e) tr->rng_valid = false;
     return map_hip(e);
 }
 
-static int prepare_rng(bih_tree *tr, uint32_t w, uint32_t spp, uint32_t frame, uint64_t seed,
-                       const bih_rows &rows, hipStream_t st) {
-    const size_t P = (size_t)rows.nrows * w;
+static int prepare_rng(bih_tree *tr, const Frame &f, hipStream_t st) {
+    const uint32_t spp = f.spp, frame = f.frame;
+    const size_t P = f.pixels();
     int rc = ensure_rng(tr, P, st);
     if (rc) return rc;
-    bool same_px = rng_same_px(tr, w, spp, seed, rows);
+    bool same_px = rng_same_px(tr, f);
     if (tr->stamped) {
         // the stamped state back into the ring, or dropped (re-seeded below)
         if (same_px && frame >= tr->next_frame) {
@@ -1120,18 +1137,11 @@ static int prepare_rng(bih_tree *tr, uint32_t w, uint32_t spp, uint32_t frame, u
         if (e) return map_hip(e);
     } else if (!same) {
         uint64_t skip = (uint64_t)2 * spp * frame;
-        int e = bih::launch_rng_init(rng_buf(tr, tr->rng_cur), w, rows.row0,
-                                     rows.nrows, rows.band_h, rows.band_step,
-                                     seed, skip, tr->t.device, st);
+        int e = bih::launch_rng_init(rng_buf(tr, tr->rng_cur), f.w, f.rows.row0, f.rows.nrows, f.rows.band_h,
+                                     f.rows.band_step, f.seed, skip, tr->t.device, st);
         if (e) return map_hip(e);
         tr->rng_valid = true;
-        tr->key_w = w;
-        tr->key_spp = spp;
-        tr->key_seed = seed;
-        tr->key_row0 = rows.row0;
-        tr->key_nrows = rows.nrows;
-        tr->key_bh = rows.band_h;
-        tr->key_bs = rows.band_step;
+        tr->key = RngKey{f.w, spp, f.rows, f.seed};
     }
     tr->next_frame = frame + 1;
     return BIH_OK;
@@ -1140,50 +1150,27 @@ static int prepare_rng(bih_tree *tr, uint32_t w, uint32_t spp, uint32_t frame, u
 // k_render_bins' queue in LPT order of measured tile costs (prepare_bin_queue)
 // unless BIH_COST_QUEUE=0 (A/B); it never changes a pixel.
 static bool cost_queue_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("BIH_COST_QUEUE");
-        return !(e && strcmp(e, "0") == 0);
-    }();
+    static const bool on = !env_off("BIH_COST_QUEUE");
     return on;
 }
 
 // k_render_bins' hit cache across launches unless BIH_HIT_CACHE_XL=0 (A/B);
 // it never changes a pixel.
 static bool hit_cache_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("BIH_HIT_CACHE_XL");
-        return !(e && strcmp(e, "0") == 0);
-    }();
+    static const bool on = !env_off("BIH_HIT_CACHE_XL");
     return on;
 }
 
 // Frustum bins are on unless BIH_BINS=0 (A-B); they never change a pixel.
 static bool bins_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("BIH_BINS");
-        return !(e && strcmp(e, "0") == 0);
-    }();
+    static const bool on = !env_off("BIH_BINS");
     return on;
 }
 
-// Packet tile of spp samples per pixel (TileShape in bih_render.hip).
-static void tile_shape(uint32_t spp, uint32_t *tw, uint32_t *th) {
-    const int L = __builtin_ctz(spp);
-    const uint32_t lp = 6 - L;
-    *tw = 1u << ((lp + 1) / 2);
-    *th = 1u << (lp / 2);
-}
-
-// (Re)builds the frustum bins for `cam` and a w x h image on `st`, after the
-// primary-ray records; every render that read the old ones has finished
-// (the caller waited for them).  Synchronises `st` once to size the lists.
 // Runs the camera's primary-ray records (launch_prim) when `need_prim` and
 // the bins take no part.
-static int prim_only(bih_tree *tr, CamSet &c, const bih_camera *cam, const float dmax[3], bool need_prim, hipStream_t st) {
-    if (!need_prim) return BIH_OK;
-    const uint32_t n_int = tr->t.u > 0 ? tr->t.u - 1 : 0;
-    return map_hip(bih::launch_prim(tr->t.tris_s, tr->t.n, tr->t.nodes, tr->t.first_idx, tr->t.dup_cnt,
-                                    tr->t.leaf_parent, tr->t.parent, n_int, cam->origin, dmax, c.prim, st));
+static int prim_only(bih_tree *tr, CamSet &c, const bih_camera *cam, bool need_prim, hipStream_t st) {
+    return need_prim ? map_hip(bih::launch_prim(tr->t, cam->origin, c.prim, st)) : BIH_OK;
 }
 
 // (Re)builds the frustum bins for `cam` and a w x h image on `st`; with
@@ -1191,8 +1178,9 @@ static int prim_only(bih_tree *tr, CamSet &c, const bih_camera *cam, const float
 // launch_prim when no bins are built).  Every render that read the old ones
 // has finished (the caller waited for them).  Synchronises `st` once to size
 // the lists the first time.
-static int build_bins(bih_tree *tr, CamSet &c, const bih_camera *cam, const float dmax[3], uint32_t w,
-                      uint32_t h, uint32_t spp, bool need_prim, hipStream_t st) {
+static int build_bins(bih_tree *tr, CamSet &c, const Frame &f, const float dmax[3], bool need_prim, hipStream_t st) {
+    const bih_camera *cam = f.cam;
+    const uint32_t w = f.w, h = f.h, spp = f.spp;
     c.bins_valid = true;
     c.bins_usable = false;
     c.bin_gn = 0;        // (an earlier camera's counts are not this one's: a camera
@@ -1203,15 +1191,14 @@ static int build_bins(bih_tree *tr, CamSet &c, const bih_camera *cam, const floa
     c.bins_key[1] = h;
     c.bins_key[2] = spp;
     const uint32_t n = tr->t.n, U = tr->t.u;
-    uint32_t tw = 0, th = 0;
-    tile_shape(spp, &tw, &th);
+    const bih::Tiles full = bih::tiles_of(w, h, spp);   // of the whole image, not the call's rows
     bih::BinCamera bc;
     if (n == 0 || U < 2 || w > 0xffffu || h > 0xffffu ||
-        !bih::bin_camera(reinterpret_cast<const float *>(cam), dmax, w, h, tw, th, &bc))
-        return prim_only(tr, c, cam, dmax, need_prim, st);   // no bins: the kernel runs the shortcut passes instead
+        !bih::bin_camera(reinterpret_cast<const float *>(cam), dmax, w, h, full.tw, full.th, &bc))
+        return prim_only(tr, c, cam, need_prim, st);   // no bins: the kernel runs the shortcut passes instead
     bih::BinBuffers b;
-    b.bins_x = (w + tw - 1) / tw;
-    b.bins_y = (h + th - 1) / th;
+    b.bins_x = full.x;
+    b.bins_y = full.y;
     const size_t nb = (size_t)b.bins_x * b.bins_y;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const uint32_t nblk = (n + 255) / 256;   // k_cam_tris blocks (bih::kThreads)
@@ -1388,14 +1375,13 @@ static int ensure_queue_mem(bih_tree *tr, CamSet &c, uint32_t ntiles, hipStream_
 // The render kernel's tile queue for this launch's rows (launch_bin_queue):
 // rebuilt when the bins or the rows change, after every render that may
 // still read the old one.
-static int prepare_bin_queue(bih_tree *tr, CamSet &c, int ci, uint32_t w, uint32_t h, uint32_t spp, const bih_rows &rows,
-                             int slot, hipStream_t st, bih::RenderArgs &a, uint32_t nframes) {
-    uint32_t tw = 0, th = 0;
-    tile_shape(spp, &tw, &th);
-    const uint32_t tiles_x = (w + tw - 1) / tw;
-    const uint32_t ntiles = tiles_x * ((rows.nrows + th - 1) / th);
+static int prepare_bin_queue(bih_tree *tr, CamSet &c, int ci, const Frame &f, int slot, hipStream_t st,
+                             bih::RenderArgs &a, uint32_t nframes) {
+    const bih_rows &rows = f.rows;
+    const bih::Tiles t = f.shape();
+    const uint32_t ntiles = (uint32_t)t.count();
     const size_t nrec = (size_t)ntiles * nframes;   // fallback records: one per packet at most
-    const uint32_t key[8] = {w, h, spp, rows.row0, rows.nrows, rows.band_h, rows.band_step, c.gen};
+    const uint32_t key[8] = {f.w, f.h, f.spp, rows.row0, rows.nrows, rows.band_h, rows.band_step, c.gen};
     int rc = ensure_qcount(tr);
     if (rc) return rc;
     // Queue order: the first launch over these rows (and bins) orders the
@@ -1417,8 +1403,8 @@ static int prepare_bin_queue(bih_tree *tr, CamSet &c, int ci, uint32_t w, uint32
             c.hseq = ++tr->hseq_ctr;
             if (c.hseq == 0) c.hseq = ++tr->hseq_ctr;
         }
-        int le = bih::launch_bin_queue(c.bins.off, c.bins.gcount + 1, c.bins.bins_x, tiles_x, ntiles, rows.row0,
-                                       rows.band_h, rows.band_step, th, c.q_mem, &c.q_list, &c.q_hdr,
+        int le = bih::launch_bin_queue(c.bins.off, c.bins.gcount + 1, c.bins.bins_x, t.x, ntiles, rows.row0,
+                                       rows.band_h, rows.band_step, t.th, c.q_mem, &c.q_list, &c.q_hdr,
                                        st, measured ? c.bins.cost : nullptr);
         if (le) return map_hip(le);
         memcpy(c.q_key, key, sizeof key);
@@ -1463,23 +1449,120 @@ static int prepare_bin_queue(bih_tree *tr, CamSet &c, int ci, uint32_t w, uint32
 }
 
 // Frames per k_render_bins item (*fpi) and item splits (*nsplit) of an
-// nframes launch over a w x nrows image: every frame of the launch in one
+// nframes launch over f's rows: every frame of the launch in one
 // item when the launch has many tiles (the list is walked nframes times while
 // it is cached), fewer when it has few (a rank's bands of the frame), so the
 // items keep outnumbering the resident waves.  BIH_PARAM_ITEM_TILES is the
 // tile count below which an item's frames are split; it changes the order of
 // the work, never a pixel.
-static void item_split(const bih_tree *tr, uint32_t w, uint32_t nrows, uint32_t spp, uint32_t nframes,
-                       uint32_t *fpi, uint32_t *nsplit) {
-    uint32_t tw = 0, th = 0;
-    tile_shape(spp, &tw, &th);
-    const uint64_t ntiles = (uint64_t)((w + tw - 1) / tw) * ((nrows + th - 1) / th);
+static void item_split(const bih_tree *tr, const Frame &f, uint32_t nframes, uint32_t *fpi, uint32_t *nsplit) {
+    const uint64_t ntiles = f.tiles();
     uint64_t ns = ntiles ? (tr->prm.item_tiles + ntiles / 2) / ntiles : nframes;
     ns = std::max<uint64_t>(1, std::min<uint64_t>(ns, nframes));
     *fpi = (uint32_t)((nframes + ns - 1) / ns);
     *nsplit = (nframes + *fpi - 1) / *fpi;
 }
 
+// The rows of a call: *rows_in, or (NULL) the whole frame of height h.  The
+// row rule: band_h and band_step are non-zero and the last local row maps
+// inside the frame (no rows: nothing to map).
+static int resolve_rows(const bih_rows *rows_in, uint32_t h, bih_rows *rows) {
+    *rows = rows_in ? *rows_in : bih_rows{0, h, h, 1};
+    if (rows->nrows == 0) return BIH_OK;
+    if (rows->band_h == 0 || rows->band_step == 0) return BIH_ERR_INVALID;
+    const uint64_t lr = rows->nrows - 1;
+    const uint64_t ylast = rows->row0 + (lr / rows->band_h) * (uint64_t)rows->band_h * rows->band_step +
+                           (lr % rows->band_h);
+    return ylast < h ? BIH_OK : BIH_ERR_INVALID;
+}
+
+// The RenderArgs fields every launch fills alike: the camera, the image, the
+// rows and the frame's first draw.
+static bih::RenderArgs base_render_args(const Frame &f) {
+    bih::RenderArgs a;
+    memcpy(a.cam, f.cam, sizeof a.cam);
+    a.w = f.w;
+    a.h = f.h;
+    a.spp = f.spp;
+    a.row0 = f.rows.row0;
+    a.nrows = f.rows.nrows;
+    a.band_h = f.rows.band_h;
+    a.band_step = f.rows.band_step;
+    uint32_t v[5], d0;
+    bih::xorwow_seed(f.seed, v, &d0);
+    a.d_base = d0 + (uint32_t)((uint64_t)2 * f.spp * f.frame) * 362437u;
+    return a;
+}
+
+// The slot's accounting once its launch is issued on `st`: the end of the
+// render's device work (ev2, timed renders), its evd, the slot rotation, the
+// camera set it read (-1: none) and the ring's buffer for the next frame.
+static int finish_slot(bih_tree *tr, int slot, hipStream_t st, int cs, int rng_next, RngGuard &rng_guard) {
+    hipError_t e = tr->timing ? hipEventRecord(tr->ev2[slot], st) : hipSuccess;
+    if (e != hipSuccess) return map_hip((int)e);
+    tr->last_timed = tr->timing;
+    tr->slot_timed[slot] = tr->timing;
+    e = hipEventRecord(tr->evd[slot], st);
+    if (e != hipSuccess) return map_hip((int)e);
+    tr->used[slot] = true;
+    tr->slot_gen[slot] = tr->gen;
+    note_stream(tr, slot, st);
+    tr->slot_cs[slot] = cs;
+    tr->last_slot = slot;
+    tr->slot = (slot + 1) % kSlots;
+    tr->rng_cur = rng_next;
+    rng_guard.armed = false;
+    return BIH_OK;
+}
+
+// A render slot taken outside the camera sets (Whitted and G-buffer launches:
+// neither reads one).  begin_slot orders `st` after every render in flight
+// (the launch's buffers are shared by all of them), the last writer of the
+// XORWOW ring, the last (re)build and -- `traces` -- the trace before it (the
+// work area), brings the ring to the frame and issues the advance to the next;
+// slot_args, once the caller's own buffers stand, publishes the ring to the
+// next render (ev_rng) and gives the launch's arguments; finish_slot closes.
+struct SlotRun {
+    bih_tree *tr;
+    int slot = 0, cur = 0, nxt = 0;
+    RngGuard guard{tr, false};   // armed once prepare_rng has moved next_frame
+};
+static int begin_slot(SlotRun &s, const Frame &f, hipStream_t st, bool traces) {
+    bih_tree *tr = s.tr;
+    int rc = wait_renders(tr, st);
+    if (rc) return rc;
+    const hipError_t e = wait_rng(tr, st);
+    if (e != hipSuccess) return map_hip((int)e);
+    rc = wait_tree(tr, st);
+    if (rc == BIH_OK && traces) rc = wait_traces(tr, st);
+    if (rc == BIH_OK) rc = prepare_rng(tr, f, st);
+    if (rc) return rc;
+    s.guard.armed = true;
+    s.slot = tr->slot;
+    s.cur = tr->rng_cur;
+    s.nxt = (s.cur + 1) % kRngBufs;
+    return map_hip(bih::launch_rng_advance(rng_buf(tr, s.cur), rng_buf(tr, s.nxt), f.pixels(), 2 * f.spp, tr->t.device, st));
+}
+static int slot_args(SlotRun &s, const Frame &f, hipStream_t st, bih::RenderArgs *a) {
+    const hipError_t e = hipEventRecord(s.tr->ev_rng, st);
+    if (e != hipSuccess) return map_hip((int)e);
+    s.tr->rng_pending = true;
+    *a = base_render_args(f);
+    a->rng_in = rng_buf(s.tr, s.cur);
+    return BIH_OK;
+}
+
+// The checks of the primary entries, in their order (f: the call as the entry
+// was given it; f->rows: the rows of the call, nrows == 0: nothing to do).
+static int primary_check(const bih_tree *tr, Frame *f, const bih_rows *rows_in, uint32_t traverse,
+                         const uint32_t *d_out) {
+    if (!tr || !f->cam || !d_out || f->w == 0 || f->h == 0 || f->spp == 0 || traverse > 1) return BIH_ERR_INVALID;
+    const int rc = resolve_rows(rows_in, f->h, &f->rows);
+    if (rc || f->rows.nrows == 0) return rc;
+    return (uint64_t)f->h * f->w > 0xFFFFFFFFull ? BIH_ERR_TOO_LARGE : BIH_OK;
+}
+
+// The primary render of frame f's rows (checked, nrows > 0) into d_out.
 // nframes > 1 (bih_render_device_frames): frames frame .. frame+nframes-1 in
 // one frustum-bin launch, frame j at d_out + j * out_stride.  Returns
 // kRenderPerFrame, before any RNG work, when this render does not go
@@ -1489,21 +1572,12 @@ constexpr int kRenderPerFrame = 1;
 // 64-bit mask of the samples that hit (RenderArgs::hit_mask), and leave the
 // XORWOW ring at this frame's state for the Whitted render that follows
 // (kRenderPerFrame, before any work, when the bins do not cover the render).
-static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                              uint32_t frame, uint64_t seed, const bih_rows *rows_in, uint32_t traverse,
-                              uint32_t *d_out, uint32_t *d_ray_stats, void *stream, uint32_t nframes,
-                              uint64_t out_stride, unsigned long long *hit_mask = nullptr,
-                              bool have_lock = false) {
-    if (!tr || !cam || !d_out || w == 0 || h == 0 || spp == 0 || traverse > 1) return BIH_ERR_INVALID;
-    bih_rows rows = rows_in ? *rows_in : bih_rows{0, h, h, 1};
-    if (rows.nrows == 0) return BIH_OK;
-    if (rows.band_h == 0 || rows.band_step == 0) return BIH_ERR_INVALID;
-    // the last local row must map inside the frame
-    uint64_t lr = rows.nrows - 1;
-    uint64_t ylast = rows.row0 + (lr / rows.band_h) * (uint64_t)rows.band_h * rows.band_step +
-                     (lr % rows.band_h);
-    if (ylast >= h) return BIH_ERR_INVALID;
-    if ((uint64_t)h * w > 0xFFFFFFFFull) return BIH_ERR_TOO_LARGE;
+static int render_device_impl(bih_tree *tr, const Frame &f, uint32_t traverse, uint32_t *d_out,
+                              uint32_t *d_ray_stats, void *stream, uint32_t nframes, uint64_t out_stride,
+                              unsigned long long *hit_mask = nullptr, bool have_lock = false) {
+    const bih_camera *cam = f.cam;
+    const uint32_t w = f.w, h = f.h, spp = f.spp, frame = f.frame;
+    const bih_rows &rows = f.rows;
     DeviceGuard g(tr->t.device);
     // (a Whitted call holds the lock across its mask render and its launch)
     std::unique_lock<std::mutex> lk(tr->mu, std::defer_lock);
@@ -1578,23 +1652,12 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
         const bool want_bins = bins_enabled() && traverse == BIH_TRAVERSE_ANYHIT && !d_ray_stats && n_int > 0;
         bool need_prim = false;
         if (!c.prim_valid || memcmp(ob, c.prim_origin, sizeof ob) != 0) {
-            // |D| per component over the primary rays: D = (llc + u h + v vert) - O
-            // (Camera.cu:18-20) is affine in (u, v) in [0, 1]^2, so its largest
-            // magnitude is at a corner.  The kernel evaluates it in f32: four
-            // rounded ops whose results are bounded by |llc|+|h|+|vert|+|O|,
-            // so each adds at most 2^-24 of that; the slack takes 2^-21
-            // (twice the sum) plus a relative 1e-3 (tests/test_miss_box.py
-            // checks it against the kernel's evaluation with offset origins)
-            float dmax[3];
-            (void)bih_camera_ray_bound(cam, dmax);
             if (want_bins) {
                 need_prim = true;
             } else {
                 rc = wait_tree_once();
                 if (rc) return rc;
-                int le = bih::launch_prim(tr->t.tris_s, tr->t.n, tr->t.nodes, tr->t.first_idx,
-                                          tr->t.dup_cnt, tr->t.leaf_parent, tr->t.parent, n_int,
-                                          cam->origin, dmax, c.prim, st);
+                const int le = bih::launch_prim(tr->t, cam->origin, c.prim, st);
                 if (le) return map_hip(le);
             }
             memcpy(c.prim_origin, ob, sizeof ob);
@@ -1610,11 +1673,18 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
             // already waited above)
             rc = wait_set_readers(tr, ci, st);
             if (rc) return rc;
+            // |D| per component over the primary rays: D = (llc + u h + v vert) - O
+            // (Camera.cu:18-20) is affine in (u, v) in [0, 1]^2, so its largest
+            // magnitude is at a corner.  The kernel evaluates it in f32: four
+            // rounded ops whose results are bounded by |llc|+|h|+|vert|+|O|,
+            // so each adds at most 2^-24 of that; the slack takes 2^-21
+            // (twice the sum) plus a relative 1e-3 (tests/test_miss_box.py
+            // checks it against the kernel's evaluation with offset origins)
             float dmax[3];
             (void)bih_camera_ray_bound(cam, dmax);
             rc = wait_tree_once();
             if (rc) return rc;
-            rc = build_bins(tr, c, cam, dmax, w, h, spp, need_prim, st);
+            rc = build_bins(tr, c, f, dmax, need_prim, st);
             if (rc) {
                 if (need_prim) c.prim_valid = false;
                 return rc;
@@ -1630,17 +1700,15 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
     // stream built, when this render reuses them)
     e = wait_rng(tr, st);
     if (e != hipSuccess) return map_hip((int)e);
-    bih::RenderArgs a;
     bool use_bins = false;
     if (c.bins_usable && c.bins_valid && c.bins_key[0] == w && c.bins_key[1] == h &&
         c.bins_key[2] == spp && traverse == BIH_TRAVERSE_ANYHIT && !d_ray_stats && c.prim) {
-        uint32_t tw = 0, th = 0;
-        tile_shape(spp, &tw, &th);
         // a packet's rows are one bin row when tiles and bands align
+        const uint32_t th = f.shape().th;
         use_bins = rows.row0 % th == 0 && rows.band_h % th == 0;
     }
     if ((nframes > 1 || hit_mask) && !use_bins) return kRenderPerFrame;
-    const size_t P = (size_t)rows.nrows * w;
+    const size_t P = f.pixels();
     // stamped state (RenderArgs::stamps): a frustum-bin launch that follows
     // kStampRun renders on its own stream reads and writes per-tile state and
     // runs no k_rng_advance.  Stamped launches order after each other (ev_rng
@@ -1651,7 +1719,7 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
     const bool stamp_ok = use_bins && !hit_mask && stamps_enabled() &&
                           (uint64_t)frame + nframes <= bih::kStampFrameMax && same_stream &&
                           (tr->stamped || tr->stream_run >= kStampRun);
-    const bool stamped = stamp_ok && tr->stamped && rng_same_px(tr, w, spp, seed, rows) && frame >= tr->next_frame &&
+    const bool stamped = stamp_ok && tr->stamped && rng_same_px(tr, f) && frame >= tr->next_frame &&
                          (uint64_t)(frame - tr->next_frame) * 2 * spp <= 4096;
     if (stamped) {
         // bound the steps a tile's state lags behind (background tiles are
@@ -1673,7 +1741,7 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
         // the frame's per-pixel XORWOW state (InitRandGPU / the state earlier
         // frames left), and the state cudaRender leaves behind for the frame
         // after this launch's last (CUDAKernels.cu:419)
-        rc = prepare_rng(tr, w, spp, frame, seed, rows, st);
+        rc = prepare_rng(tr, f, st);
         if (rc) return rc;
     }
     // next_frame now points past this launch while rng_cur still holds its
@@ -1683,9 +1751,7 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
     if (!stamped && stamp_ok) {
         // into stamped mode: every tile at this frame in rng_cur; after every
         // render in flight (they may read the ring buffers)
-        uint32_t tw = 0, th = 0;
-        tile_shape(spp, &tw, &th);
-        const size_t ntiles = (size_t)((w + tw - 1) / tw) * ((rows.nrows + th - 1) / th);
+        const size_t ntiles = f.tiles();
         rc = ensure_stamps(tr, ntiles, st);
         if (rc) return rc;
         for (int k = 0; k < kSlots; ++k)
@@ -1701,6 +1767,7 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
     }
     const bool use_stamps = stamp_ok;   // (stamped mode from here on)
     const int cur = tr->rng_cur, nxt = (cur + 1) % kRngBufs;
+    bih::RenderArgs a = base_render_args(f);
     a.nframes = nframes;
     a.out_stride = out_stride;
     if (use_bins && nframes > 1) {
@@ -1708,7 +1775,7 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
         // per tile 0.047 ms per frame, two of 8 0.051; a rank's eighth of the
         // bands, 8 frames per call: items of 8 frames 0.0107 ms per frame, of
         // 2 0.0078; 16 per call, items of 4: 0.0069)
-        item_split(tr, w, rows.nrows, spp, nframes, &a.fpi, &a.nsplit);
+        item_split(tr, f, nframes, &a.fpi, &a.nsplit);
         // (a caller's BIH_PARAM_ITEM_TILES keeps item_split's rule)
         a.live_items = tr->prm.item_tiles_set ? 0u : live_items_target();
     } else {
@@ -1750,13 +1817,13 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
         a.bin_path = c.bins.path;
         a.bins_x = c.bins.bins_x;
         a.bin_gstat = c.bins.gcount + 1;
-        rc = prepare_bin_queue(tr, c, ci, w, h, spp, rows, slot, st, a, nframes);
+        rc = prepare_bin_queue(tr, c, ci, f, slot, st, a, nframes);
         if (rc) return rc;
         if (hit_mask) a.bin_cost = nullptr;   // (the mask pass's kernel does not measure)
     } else {
         // the cost order pays off for the long BIH walks; with the bins the
         // packets are short and the order's own launch costs more (A/B)
-        rc = prepare_chunk_order(tr, w, spp, rows, slot, st, a);
+        rc = prepare_chunk_order(tr, f, slot, st, a);
         if (rc) return rc;
     }
     // the BIH walk kernels read the culled node records: built on first use
@@ -1764,8 +1831,7 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
     if (!use_bins && bih::render_uses_prim(spp) && c.prim && n_int > 0 && !c.cull_valid) {
         rc = wait_set_readers(tr, ci, st);
         if (rc) return rc;
-        const int le = bih::launch_prim_cull(tr->t.n, tr->t.nodes, tr->t.first_idx, tr->t.dup_cnt, n_int,
-                                             cam->origin, c.prim, st);
+        const int le = bih::launch_prim_cull(tr->t, cam->origin, c.prim, st);
         if (le) return map_hip(le);
         c.cull_valid = true;
     }
@@ -1778,9 +1844,7 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
         if (rc) return rc;
         float dmax[3];
         (void)bih_camera_ray_bound(cam, dmax);
-        const int le = bih::launch_fast_boxes(tr->t.tris_s, tr->t.n, tr->t.nodes, tr->t.first_idx,
-                                              tr->t.dup_cnt, tr->t.leaf_parent, tr->t.parent, n_int,
-                                              cam->origin, dmax, c.prim, st);
+        const int le = bih::launch_fast_boxes(tr->t, cam->origin, dmax, c.prim, st);
         if (le) return map_hip(le);
         c.fast_valid = true;
     }
@@ -1793,17 +1857,6 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
         if (e != hipSuccess) return map_hip((int)e);
         tr->rng_pending = true;
     }
-    memcpy(a.cam, cam, sizeof a.cam);
-    a.w = w;
-    a.h = h;
-    a.spp = spp;
-    a.row0 = rows.row0;
-    a.nrows = rows.nrows;
-    a.band_h = rows.band_h;
-    a.band_step = rows.band_step;
-    uint32_t v[5], d0;
-    bih::xorwow_seed(seed, v, &d0);
-    a.d_base = d0 + (uint32_t)((uint64_t)2 * spp * frame) * 362437u;
     a.hdr = tr->t.hdr;
     a.hdr_n_tris = tr->t.n;
     a.n_nodes = n_int;
@@ -1849,36 +1902,28 @@ static int render_device_impl(bih_tree *tr, const bih_camera *cam, uint32_t w, u
         c.cost_known = true;
     }
     if (use_stamps) {
+        // (the next launch reads the stamps this one writes)
         e = hipEventRecord(tr->ev_rng, st);
         if (e != hipSuccess) return map_hip((int)e);
         tr->rng_pending = true;
     }
-    if (tr->timing) {
-        e = hipEventRecord(tr->ev2[slot], st);
-        if (e != hipSuccess) return map_hip((int)e);
-    }
-    tr->last_timed = tr->timing;
-    tr->slot_timed[slot] = tr->timing;
-    e = hipEventRecord(tr->evd[slot], st);
-    if (e != hipSuccess) return map_hip((int)e);
-    tr->used[slot] = true;
-    tr->slot_gen[slot] = tr->gen;
-    note_stream(tr, slot, st);
-    tr->slot_cs[slot] = ci;
+    // the slot read camera set ci, which becomes the current one; the ring
+    // moves to frame+1's state unless the launch left it where it was (a mask
+    // pass: its Whitted or G-buffer render advances it; stamped: no advance ran)
+    rc = finish_slot(tr, slot, st, ci, (hit_mask || use_stamps) ? cur : nxt, rng_guard);
+    if (rc) return rc;
     if (use_bins) ++c.uses;
     tr->cs_cur = ci;
-    tr->last_slot = slot;
-    tr->slot = (slot + 1) % kSlots;
-    if (!hit_mask && !use_stamps) tr->rng_cur = nxt;  // frame+1's state
-    rng_guard.armed = false;
     return BIH_OK;
 }
 
 int bih_render_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                       uint32_t frame, uint64_t seed, const bih_rows *rows_in, uint32_t traverse,
                       uint32_t *d_out, uint32_t *d_ray_stats, void *stream) {
-    return render_device_impl(const_cast<bih_tree *>(ctr), cam, w, h, spp, frame, seed, rows_in, traverse,
-                              d_out, d_ray_stats, stream, 1, 0);
+    Frame f = {cam, w, h, spp, frame, seed, {}};
+    const int rc = primary_check(ctr, &f, rows_in, traverse, d_out);
+    if (rc || f.rows.nrows == 0) return rc;
+    return render_device_impl(const_cast<bih_tree *>(ctr), f, traverse, d_out, d_ray_stats, stream, 1, 0);
 }
 
 int bih_render_device_frames(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
@@ -1891,14 +1936,15 @@ int bih_render_device_frames(const bih_tree *ctr, const bih_camera *cam, uint32_
     if (nframes > 1 && out_stride < nrows * w) return BIH_ERR_INVALID;
     // one launch: items (<= tiles per band x nframes) and records stay far below 2^31
     const bool one_launch = nframes > 1 && (uint64_t)((w + 7) / 4) * ((nrows + 3) / 4 + 1) * nframes < (1ull << 28);
+    Frame f = {cam, w, h, spp, frame0, seed, {}};
+    int rc = primary_check(tr, &f, rows_in, BIH_TRAVERSE_ANYHIT, d_out);
+    if (rc || f.rows.nrows == 0) return rc;
     if (one_launch) {
-        const int rc = render_device_impl(tr, cam, w, h, spp, frame0, seed, rows_in, BIH_TRAVERSE_ANYHIT, d_out,
-                                          nullptr, stream, nframes, out_stride);
+        rc = render_device_impl(tr, f, BIH_TRAVERSE_ANYHIT, d_out, nullptr, stream, nframes, out_stride);
         if (rc != kRenderPerFrame) return rc;
     }
-    for (uint32_t j = 0; j < nframes; ++j) {
-        const int rc = render_device_impl(tr, cam, w, h, spp, frame0 + j, seed, rows_in, BIH_TRAVERSE_ANYHIT,
-                                          d_out + (uint64_t)j * out_stride, nullptr, stream, 1, 0);
+    for (uint32_t j = 0; j < nframes; ++j, ++f.frame) {
+        rc = render_device_impl(tr, f, BIH_TRAVERSE_ANYHIT, d_out + (uint64_t)j * out_stride, nullptr, stream, 1, 0);
         if (rc) return rc;
     }
     return BIH_OK;
@@ -1906,21 +1952,20 @@ int bih_render_device_frames(const bih_tree *ctr, const bih_camera *cam, uint32_
 
 int bih_reserve(bih_tree *tr, uint32_t w, uint32_t h, uint32_t spp, const bih_rows *rows_in, uint32_t max_frames) {
     if (!tr || w == 0 || h == 0 || spp == 0 || max_frames == 0 || max_frames > 64) return BIH_ERR_INVALID;
-    const bih_rows rows = rows_in ? *rows_in : bih_rows{0, h, h, 1};
-    if (rows.nrows == 0) return BIH_OK;
-    if (rows.band_h == 0 || rows.band_step == 0 || (uint64_t)h * w > 0xFFFFFFFFull) return BIH_ERR_INVALID;
+    // (sizes buffers only: the rows need not lie inside the frame, and a frame
+    // no render would take is an invalid argument here)
+    const Frame f = {nullptr, w, h, spp, 0, 0, rows_in ? *rows_in : bih_rows{0, h, h, 1}};
+    if (f.rows.nrows == 0) return BIH_OK;
+    if (f.rows.band_h == 0 || f.rows.band_step == 0 || (uint64_t)h * w > 0xFFFFFFFFull) return BIH_ERR_INVALID;
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
-    const size_t P = (size_t)rows.nrows * w;
-    int rc = ensure_rng(tr, P, tr->stream);
+    int rc = ensure_rng(tr, f.pixels(), tr->stream);
     if (!rc) rc = ensure_work(tr);
     if (!rc) rc = ensure_qcount(tr);
     if (rc) return rc;
     // the frustum-bin path: tile queues of every camera set, fallback records
     // (one per packet and frame at most), the stamps
-    uint32_t tw = 0, th = 0;
-    tile_shape(spp, &tw, &th);
-    const uint32_t ntiles = ((w + tw - 1) / tw) * ((rows.nrows + th - 1) / th);
+    const uint32_t ntiles = (uint32_t)f.tiles();
     for (int k = 0; k < cam_sets() && !rc; ++k) rc = ensure_queue_mem(tr, tr->cs[k], ntiles, tr->stream);
     if (!rc) rc = ensure_per_slot(tr, &tr->fb_mem, &tr->fbq_cap, (size_t)ntiles * max_frames, 8);
     if (!rc && stamps_enabled()) rc = ensure_stamps(tr, ntiles, tr->stream);
@@ -1987,42 +2032,31 @@ int bih_tree_set_param(bih_tree *tr, int param, uint64_t value) {
     return BIH_OK;
 }
 
-// The RenderArgs fields a Whitted and a G-buffer launch fill alike: the
-// camera, the image, the rows and the frame's first draw.
-static bih::RenderArgs base_render_args(const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                                        const bih_rows &rows, uint64_t seed, uint32_t frame) {
-    bih::RenderArgs a;
-    memcpy(a.cam, cam, sizeof a.cam);
-    a.w = w;
-    a.h = h;
-    a.spp = spp;
-    a.row0 = rows.row0;
-    a.nrows = rows.nrows;
-    a.band_h = rows.band_h;
-    a.band_step = rows.band_step;
-    uint32_t v[5], d0;
-    bih::xorwow_seed(seed, v, &d0);
-    a.d_base = d0 + (uint32_t)((uint64_t)2 * spp * frame) * 362437u;
-    return a;
-}
-
-// The slot's accounting once a Whitted or G-buffer launch (neither reads a
-// camera set) is issued on `st`: its evd, the slot rotation, and the ring's
-// buffer `nxt` for the next frame.
-static int finish_slot(bih_tree *tr, int slot, hipStream_t st, int nxt, RngGuard &rng_guard) {
-    tr->last_timed = tr->timing;
-    tr->slot_timed[slot] = tr->timing;
-    const hipError_t e = hipEventRecord(tr->evd[slot], st);
-    if (e != hipSuccess) return map_hip((int)e);
-    tr->used[slot] = true;
-    tr->slot_gen[slot] = tr->gen;
-    note_stream(tr, slot, st);
-    tr->slot_cs[slot] = -1;
-    tr->last_slot = slot;
-    tr->slot = (slot + 1) % kSlots;
-    tr->rng_cur = nxt;
-    rng_guard.armed = false;
-    return BIH_OK;
+// The primary samples' any-hit result from the frustum bins, for a Whitted or
+// G-buffer launch of the same frame: the any-hit render (the primary render's
+// kernels) leaves per tile the mask of its samples that hit, and only those
+// enter the closest-hit walk (a proven miss has no closest hit: same visit set,
+// same test).  *buf (*cap tiles) is the launch kind's mask buffer, prev_slot the
+// slot of its last launch, which read the buffer.  The render's pixels go to
+// *pixels: the caller's image, or (pixels_cap) a scratch image of the tree,
+// grown here.  *mask: the buffer, or NULL when the bins do not cover the render.
+static int mask_prepass(bih_tree *tr, const Frame &f, unsigned long long **buf, size_t *cap, int prev_slot,
+                        uint32_t **pixels, size_t *pixels_cap, void *stream, hipStream_t st,
+                        unsigned long long **mask) {
+    const size_t ntiles = f.tiles(), P = f.pixels();
+    if (*cap < ntiles || (pixels_cap && *pixels_cap < P)) {
+        int rc = drain_renders(tr);
+        if (rc == BIH_OK) rc = grow(tr, buf, cap, ntiles, ntiles * 8);
+        if (rc == BIH_OK && pixels_cap) rc = grow(tr, pixels, pixels_cap, P, P * 4);
+        if (rc) return rc;
+    } else if (prev_slot >= 0 && tr->used[prev_slot]) {
+        // rewritten in place: after the last launch that read them, whatever stream it ran on
+        const hipError_t e = hipStreamWaitEvent(st, tr->evd[prev_slot], 0);
+        if (e != hipSuccess) return map_hip((int)e);
+    }
+    const int rc = render_device_impl(tr, f, BIH_TRAVERSE_ANYHIT, *pixels, nullptr, stream, 1, 0, *buf, true);
+    if (rc == BIH_OK) *mask = *buf;
+    return rc == kRenderPerFrame ? BIH_OK : rc;
 }
 
 int bih_render_whitted_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h,
@@ -2030,13 +2064,9 @@ int bih_render_whitted_device(const bih_tree *ctr, const bih_camera *cam, uint32
                               uint32_t *d_out, uint32_t *d_hits, void *stream) {
     bih_tree *tr = const_cast<bih_tree *>(ctr);
     if (!tr || !cam || !d_out || w == 0 || h == 0 || spp == 0) return BIH_ERR_INVALID;
-    bih_rows rows = rows_in ? *rows_in : bih_rows{0, h, h, 1};
-    if (rows.nrows == 0) return BIH_OK;
-    if (rows.band_h == 0 || rows.band_step == 0) return BIH_ERR_INVALID;
-    uint64_t lr = rows.nrows - 1;
-    uint64_t ylast = rows.row0 + (lr / rows.band_h) * (uint64_t)rows.band_h * rows.band_step +
-                     (lr % rows.band_h);
-    if (ylast >= h) return BIH_ERR_INVALID;
+    Frame f = {cam, w, h, spp, frame, seed, {}};
+    int rc = resolve_rows(rows_in, h, &f.rows);
+    if (rc || f.rows.nrows == 0) return rc;
     // u32 ray ids, and k_wh_trace's u32 fetch counter overshoots the ray
     // count by at most one 64-ray fetch per wave of its grid (<= 2^20 lanes)
     if ((uint64_t)h * w * spp > 0xFFFFFFFFull - (1ull << 20)) return BIH_ERR_TOO_LARGE;
@@ -2045,95 +2075,52 @@ int bih_render_whitted_device(const bih_tree *ctr, const bih_camera *cam, uint32
     // through this tree slips in between
     std::lock_guard<std::mutex> lk(tr->mu);
     hipStream_t st = stream ? (hipStream_t)stream : tr->stream;
-    // Bounce 0 through the frustum bins: the any-hit render of the same
-    // frame (the primary render's kernels) leaves per tile the mask of its
-    // samples that hit; only those enter the closest-hit walk of bounce 0 (a
-    // proven miss has no closest hit: same visit set, same test).  Its pixels
-    // go to d_out, which the Whitted shade overwrites.  BIH_WH_BINS=0: every
-    // primary sample is walked (A/B).
+    // Bounce 0 through the frustum bins (mask_prepass); the mask render's
+    // pixels go to d_out, which the Whitted shade overwrites.  BIH_WH_BINS=0:
+    // every primary sample is walked (A/B).
     unsigned long long *mask = nullptr;
-    uint32_t mask_tiles_x = 0;
-    static const bool wh_bins = [] {
-        const char *e = getenv("BIH_WH_BINS");
-        return !(e && e[0] == '0');
-    }();
+    static const bool wh_bins = !env_off("BIH_WH_BINS");
     // With work counters on, every primary sample is walked, so that the
     // counts equal the oracle's on every frame.
-    if (wh_bins && bins_enabled() && !tr->prm.wh_counters && spp <= 64 && (spp & (spp - 1)) == 0 &&
-        tr->t.u > 1) {
-        uint32_t tw = 0, th = 0;
-        tile_shape(spp, &tw, &th);
-        mask_tiles_x = (w + tw - 1) / tw;
-        const size_t ntiles = (size_t)mask_tiles_x * ((rows.nrows + th - 1) / th);
-        if (tr->wh_mask_cap < ntiles) {
-            int rc = drain_renders(tr);
-            if (rc) return rc;
-            rc = grow(tr, &tr->wh_mask, &tr->wh_mask_cap, ntiles, ntiles * 8);
-            if (rc) return rc;
-        } else if (tr->wh_prev_slot >= 0 && tr->used[tr->wh_prev_slot]) {
-            // the mask is rewritten in place: after the last Whitted launch
-            // (its k_wh_gen reads the previous mask), whatever stream it ran on
-            hipError_t e = hipStreamWaitEvent(st, tr->evd[tr->wh_prev_slot], 0);
-            if (e != hipSuccess) return map_hip((int)e);
-        }
-        const int mrc = render_device_impl(tr, cam, w, h, spp, frame, seed, &rows, BIH_TRAVERSE_ANYHIT, d_out,
-                                           nullptr, stream, 1, 0, tr->wh_mask, true);
-        if (mrc == BIH_OK) mask = tr->wh_mask;
-        else if (mrc != kRenderPerFrame) return mrc;
+    const bool masked = wh_bins && bins_enabled() && !tr->prm.wh_counters && spp <= 64 && (spp & (spp - 1)) == 0 &&
+                        tr->t.u > 1;
+    if (masked) {
+        rc = mask_prepass(tr, f, &tr->wh_mask, &tr->wh_mask_cap, tr->wh_prev_slot, &d_out, nullptr, stream, st, &mask);
+        if (rc) return rc;
     }
-    // the queues are shared by every Whitted render of this tree: order after
-    // every render in flight (and after the last writer of the RNG ring)
-    int rc = wait_renders(tr, st);
-    if (rc) return rc;
-    {
-        hipError_t e = wait_rng(tr, st);
-        if (e != hipSuccess) return map_hip((int)e);
-    }
-    rc = wait_tree(tr, st);
-    if (rc) return rc;
+    // the queues are shared by every Whitted render of this tree (begin_slot's waits)
+    SlotRun s{tr};
+    rc = begin_slot(s, f, st, false);
     // bih_whitted_work describes the last Whitted launch issued: none until
     // this one is (a failure below, or a reallocated wh_mem, leaves nothing
     // to read)
     tr->wh_last_slot = -1;
-    rc = prepare_rng(tr, w, spp, frame, seed, rows, st);
     if (rc) return rc;
-    RngGuard rng_guard{tr};
-    const size_t P = (size_t)rows.nrows * w;
-    const uint64_t rays = (uint64_t)P * spp;
-    const int cur = tr->rng_cur, nxt = (cur + 1) % kRngBufs;
-    rc = map_hip(bih::launch_rng_advance(rng_buf(tr, cur), rng_buf(tr, nxt), P, 2 * spp, tr->t.device, st));
-    if (rc) return rc;
+    const uint64_t rays = f.samples();
     if (tr->wh_rays < rays) {
-        hipError_t e = hipStreamSynchronize(st);   // the previous Whitted render's readers
+        const hipError_t e = hipStreamSynchronize(st);   // the previous Whitted render's readers
         if (e != hipSuccess) return map_hip((int)e);
         rc = grow(tr, &tr->wh_mem, &tr->wh_rays, rays, bih::whitted_bytes(rays));
         if (rc) return rc;
     }
-    hipError_t e = hipEventRecord(tr->ev_rng, st);
-    if (e != hipSuccess) return map_hip((int)e);
-    tr->rng_pending = true;
-    bih::RenderArgs a = base_render_args(cam, w, h, spp, rows, seed, frame);
+    bih::RenderArgs a;
+    rc = slot_args(s, f, st, &a);
+    if (rc) return rc;
     a.hdr = tr->t.hdr;
     a.hdr_n_tris = tr->t.n;
     a.n_nodes = tr->t.u > 0 ? tr->t.u - 1 : 0;
     a.nodes = tr->t.nodes;
     a.tris = tr->t.tris_s;
     a.dup_cnt = tr->t.dup_cnt;
-    a.rng_in = rng_buf(tr, cur);
     a.out = d_out;
-    const int slot = tr->slot;
     const bool count = tr->prm.wh_counters != 0;
-    rc = bih::launch_whitted(a, tr->wh_mem, rays, d_hits, st, tr->timing ? tr->ev0[slot] : nullptr,
-                             tr->timing ? tr->ev1[slot] : nullptr, count, mask, mask_tiles_x);
+    rc = bih::launch_whitted(a, tr->wh_mem, rays, d_hits, st, tr->timing ? tr->ev0[s.slot] : nullptr,
+                             tr->timing ? tr->ev1[s.slot] : nullptr, count, mask, masked ? f.tiles_x() : 0);
     if (rc) return map_hip(rc);
     tr->wh_last_rays = rays;
-    tr->wh_last_slot = count ? slot : -1;
-    tr->wh_prev_slot = slot;
-    if (tr->timing) {
-        e = hipEventRecord(tr->ev2[slot], st);
-        if (e != hipSuccess) return map_hip((int)e);
-    }
-    return finish_slot(tr, slot, st, nxt, rng_guard);
+    tr->wh_last_slot = count ? s.slot : -1;
+    tr->wh_prev_slot = s.slot;
+    return finish_slot(tr, s.slot, st, -1, s.nxt, s.guard);
 }
 
 int bih_whitted_work(const bih_tree *ctr, uint32_t rays[BIH_WHITTED_BOUNCES + 1],
@@ -2192,6 +2179,10 @@ static int ensure_trace(bih_tree *tr) {
     return map_hip((int)e);
 }
 
+static bih::WorkArea work_area(const bih_tree *tr) {
+    return bih::WorkArea{tr->tq_cursor, tr->tq_spill, tr->tq_blocks, tr->prm.trace_lds};
+}
+
 // bih_trace_device under the tree's lock, arguments checked.
 static int trace_locked(bih_tree *tr, const void *d_rays, uint32_t n, uint32_t query, void *d_out, hipStream_t st) {
     if (!tr->t.hdr) return BIH_ERR_INVALID;   // no tree was ever built into this buffer
@@ -2204,8 +2195,7 @@ static int trace_locked(bih_tree *tr, const void *d_rays, uint32_t n, uint32_t q
     rc = wait_traces(tr, st);
     if (rc) return rc;
     static_assert(BIH_QUERY_T_HI == bih::kQueryTHi, "BIH_QUERY_T_HI / kQueryTHi");
-    rc = map_hip(bih::launch_trace(tr->t, d_rays, n, query, d_out, tr->prm.trace_lds,
-                                   tr->tq_cursor, tr->tq_spill, tr->tq_blocks, st));
+    rc = map_hip(bih::launch_trace(tr->t, d_rays, n, query, d_out, work_area(tr), st));
     // (a failed launch may have left work on st that uses the cursor: the event covers it)
     const hipError_t e = hipEventRecord(tr->ev_trace, st);
     if (e == hipSuccess) tr->trace_used = true;
@@ -2257,23 +2247,16 @@ int bih_trace(const bih_tree *ctr, const bih_ray *rays, uint64_t n_rays, uint32_
 }
 
 // Argument checks of both G-buffer entries, in the header's order; none
-// touches the tree or a device.  *rows: the rows of the call.
-static int gbuffer_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                         const bih_rows *rows_in, const bih_gbuffer *pl, bih_rows *rows) {
-    if (!tr || !cam || !pl) return BIH_ERR_INVALID;
-    if (w == 0 || h == 0 || spp == 0) return BIH_ERR_INVALID;
-    if (spp > 64) return BIH_ERR_INVALID;   // one wave holds a pixel's samples
+// touches the tree or a device.  f: the call as the entry was given it;
+// f->rows: the rows of the call.
+static int gbuffer_check(const bih_tree *tr, Frame *f, const bih_rows *rows_in, const bih_gbuffer *pl) {
+    if (!tr || !f->cam || !pl) return BIH_ERR_INVALID;
+    if (f->w == 0 || f->h == 0 || f->spp == 0) return BIH_ERR_INVALID;
+    if (f->spp > 64) return BIH_ERR_INVALID;   // one wave holds a pixel's samples
     if (!pl->hits && !pl->depth && !pl->prim && !pl->bary && !pl->normal && !pl->coverage) return BIH_ERR_INVALID;
-    *rows = rows_in ? *rows_in : bih_rows{0, h, h, 1};
-    if (rows->nrows > 0) {
-        if (rows->band_h == 0 || rows->band_step == 0) return BIH_ERR_INVALID;
-        const uint64_t lr = rows->nrows - 1;
-        const uint64_t ylast = rows->row0 + (lr / rows->band_h) * (uint64_t)rows->band_h * rows->band_step +
-                               (lr % rows->band_h);
-        if (ylast >= h) return BIH_ERR_INVALID;
-    }
+    if (const int rc = resolve_rows(rows_in, f->h, &f->rows)) return rc;
     // u32 sample ids and tile cursor (as bih_render_whitted_device)
-    if ((uint64_t)h * w * spp > 0xFFFFFFFFull - (1ull << 20)) return BIH_ERR_TOO_LARGE;
+    if ((uint64_t)f->h * f->w * f->spp > 0xFFFFFFFFull - (1ull << 20)) return BIH_ERR_TOO_LARGE;
     if ((uintptr_t)pl->hits & 15u) return BIH_ERR_INVALID;   // records move as 16-byte words
     return BIH_OK;
 }
@@ -2282,9 +2265,7 @@ static int gbuffer_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, 
 // merged into the kernels' slot order (merge_light_set) and the planes to
 // write (device memory).  The launch's hits go to dr_mem.
 struct DirectJob {
-    float lights[4 * BIH_MAX_LIGHTS];   // n_lights x 4 floats: n_dir bih_light, then bih_point_light, then
-    uint32_t n_lights, n_dir;           // the area lights' {corner, weight}
-    bih::AreaLights area;               // the last area.n lights are area lights (0: no area kernels)
+    bih::Lights lights;
     bih_direct planes;
     // bih_render_indirect*: the second level (planes then holds lit, irradiance, rgba of `ind`)
     bool indirect = false;
@@ -2295,63 +2276,28 @@ struct DirectJob {
 // bih_render_gbuffer_device under the tree's lock, arguments checked, nrows > 0.
 // dj: the call is bih_render_direct_device's (pl.hits = dr_mem, sized for it):
 // the records carry sorted positions and the direct-lighting kernels follow.
-static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                          uint32_t frame, uint64_t seed, const bih_rows &rows, const bih_gbuffer &pl,
-                          void *stream, const DirectJob *dj = nullptr) {
+static int gbuffer_locked(bih_tree *tr, const Frame &f, const bih_gbuffer &pl, void *stream,
+                          const DirectJob *dj = nullptr) {
     if (!tr->t.hdr) return BIH_ERR_INVALID;   // no tree was ever built into this buffer
     hipStream_t st = stream ? (hipStream_t)stream : tr->stream;
     int rc = ensure_trace(tr);
     if (rc) return rc;
-    const size_t P = (size_t)rows.nrows * w;
     // The primary samples' any-hit result from the frustum bins, as bounce 0
-    // of a Whitted render: the any-hit render of the same frame leaves per
-    // tile the mask of its samples that hit, and only those are walked (a
-    // proven miss has no closest hit: same visit set, same test).  Its pixels
-    // go to a scratch image.  BIH_PARAM_GBUFFER_MASK = 0: every sample is walked.
+    // of a Whitted render (mask_prepass); the mask render's pixels go to a
+    // scratch image.  BIH_PARAM_GBUFFER_MASK = 0: every sample is walked.
     unsigned long long *mask = nullptr;
-    if (tr->prm.gb_mask && bins_enabled() && (spp & (spp - 1)) == 0 && tr->t.u > 1) {
-        uint32_t tiles_x = 0;
-        const size_t ntiles = (size_t)bih::gbuffer_tiles(w, rows.nrows, spp, &tiles_x);
-        if (tr->gb_mask_cap < ntiles || tr->gb_scratch_cap < P) {
-            rc = drain_renders(tr);
-            if (rc == BIH_OK) rc = grow(tr, &tr->gb_mask, &tr->gb_mask_cap, ntiles, ntiles * 8);
-            if (rc == BIH_OK) rc = grow(tr, &tr->gb_scratch, &tr->gb_scratch_cap, P, P * 4);
-            if (rc) return rc;
-        } else if (tr->gb_prev_slot >= 0 && tr->used[tr->gb_prev_slot]) {
-            // the mask and the scratch image are rewritten in place: after the
-            // last G-buffer launch (it reads the mask), whatever stream it ran on
-            const hipError_t e = hipStreamWaitEvent(st, tr->evd[tr->gb_prev_slot], 0);
-            if (e != hipSuccess) return map_hip((int)e);
-        }
-        const int mrc = render_device_impl(tr, cam, w, h, spp, frame, seed, &rows, BIH_TRAVERSE_ANYHIT,
-                                           tr->gb_scratch, nullptr, stream, 1, 0, tr->gb_mask, true);
-        if (mrc == BIH_OK) mask = tr->gb_mask;
-        else if (mrc != kRenderPerFrame) return mrc;
+    if (tr->prm.gb_mask && bins_enabled() && (f.spp & (f.spp - 1)) == 0 && tr->t.u > 1) {
+        rc = mask_prepass(tr, f, &tr->gb_mask, &tr->gb_mask_cap, tr->gb_prev_slot, &tr->gb_scratch,
+                          &tr->gb_scratch_cap, stream, st, &mask);
+        if (rc) return rc;
     }
-    // the launch takes a render slot (the XORWOW ring's rotation): after every
-    // render in flight and the last writer of the ring; after the last
-    // (re)build; and after the trace or G-buffer launch before it (the shared
-    // cursor and spill area)
-    rc = wait_renders(tr, st);
+    // the launch takes a render slot (the XORWOW ring's rotation) and borrows
+    // the trace's work area: begin_slot's waits, the trace before it among them
+    SlotRun s{tr};
+    rc = begin_slot(s, f, st, true);
+    bih::RenderArgs a;
+    if (rc == BIH_OK) rc = slot_args(s, f, st, &a);
     if (rc) return rc;
-    {
-        const hipError_t e = wait_rng(tr, st);
-        if (e != hipSuccess) return map_hip((int)e);
-    }
-    rc = wait_tree(tr, st);
-    if (rc == BIH_OK) rc = wait_traces(tr, st);
-    if (rc) return rc;
-    rc = prepare_rng(tr, w, spp, frame, seed, rows, st);
-    if (rc) return rc;
-    RngGuard rng_guard{tr};
-    const int cur = tr->rng_cur, nxt = (cur + 1) % kRngBufs;
-    rc = map_hip(bih::launch_rng_advance(rng_buf(tr, cur), rng_buf(tr, nxt), P, 2 * spp, tr->t.device, st));
-    if (rc) return rc;
-    hipError_t e = hipEventRecord(tr->ev_rng, st);
-    if (e != hipSuccess) return map_hip((int)e);
-    tr->rng_pending = true;
-    bih::RenderArgs a = base_render_args(cam, w, h, spp, rows, seed, frame);
-    a.rng_in = rng_buf(tr, cur);
     bih::GBufferPlanes p;
     p.hits = pl.hits;
     p.depth = pl.depth;
@@ -2359,81 +2305,63 @@ static int gbuffer_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
     p.bary = pl.bary;
     p.normal = pl.normal;
     p.coverage = pl.coverage;
-    const int slot = tr->slot;
-    if (tr->timing) {
-        e = hipEventRecord(tr->ev0[slot], st);
-        if (e != hipSuccess) return map_hip((int)e);
-    }
-    rc = bih::launch_gbuffer(tr->t, a, p, mask, tr->prm.trace_lds, tr->tq_cursor, tr->tq_spill, tr->tq_blocks, st,
-                             dj != nullptr);
+    hipError_t e = tr->timing ? hipEventRecord(tr->ev0[s.slot], st) : hipSuccess;
+    if (e != hipSuccess) return map_hip((int)e);
+    const bih::WorkArea wa = work_area(tr);
+    rc = bih::launch_gbuffer(tr->t, a, p, mask, wa, st, dj != nullptr);
     if (rc == 0 && dj) {
-        // dr_mem: records, facing masks, list (each at a multiple of 8 bytes)
+        // dr_mem: records, facing masks, list (each at a multiple of 8 bytes);
+        // in_mem: bounce records, hit list
         const size_t S = tr->dr_cap;
         char *rec = tr->dr_mem, *face = rec + 16 * S, *list = face + 8 * S;
-        bih::DirectPlanes dp;
-        dp.lit = dj->planes.lit ? reinterpret_cast<unsigned long long *>(dj->planes.lit) : tr->dr_lit;
-        dp.irradiance = dj->planes.irradiance;
-        dp.rgba = dj->planes.rgba;
+        char *rec2 = tr->in_mem, *blist = rec2 + 16 * tr->in_cap;
+        const bih::Scratch sc = {rec, reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
+                                 rec2, reinterpret_cast<uint32_t *>(blist)};
+        bih::IndirectPlanes ip;
+        ip.lit = dj->planes.lit ? reinterpret_cast<unsigned long long *>(dj->planes.lit) : tr->dr_lit;
+        ip.irradiance = dj->planes.irradiance;
+        ip.rgba = dj->planes.rgba;
         if (dj->indirect) {
-            // in_mem: bounce records, hit list
-            char *rec2 = tr->in_mem, *blist = rec2 + 16 * tr->in_cap;
-            bih::IndirectPlanes ip;
-            ip.lit = dp.lit;
             ip.bounce = dj->ind.bounce;
             ip.lit2 = dj->ind.lit2 ? reinterpret_cast<unsigned long long *>(dj->ind.lit2) : tr->in_lit2;
-            ip.irradiance = dp.irradiance;
-            ip.rgba = dp.rgba;
-            rc = bih::launch_indirect(tr->t, a, ip, dj->lights, dj->n_lights, dj->n_dir, dj->area, dj->bounce.albedo,
-                                      dj->bounce.sky, rec, rec2, reinterpret_cast<uint32_t *>(list),
-                                      reinterpret_cast<unsigned long long *>(face),
-                                      reinterpret_cast<uint32_t *>(blist), tr->prm.trace_lds, tr->tq_cursor + 4,
-                                      reinterpret_cast<unsigned long long *>(tr->tq_cursor + 2), tr->tq_cursor + 6,
-                                      tr->tq_spill, tr->tq_blocks, st);
+            rc = bih::launch_indirect(tr->t, a, ip, dj->lights, dj->bounce.albedo, dj->bounce.sky, sc, wa, st);
         } else {
-            rc = bih::launch_direct(tr->t, a, dp, dj->lights, dj->n_lights, dj->n_dir, rec,
-                                    reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
-                                    tr->prm.trace_lds, tr->tq_cursor + 4,
-                                    reinterpret_cast<unsigned long long *>(tr->tq_cursor + 2), tr->tq_spill,
-                                    tr->tq_blocks, st, dj->area.n ? &dj->area : nullptr);
+            rc = bih::launch_direct(tr->t, a, ip, dj->lights, sc, wa, st);
         }
     }
     // (a failed launch may have left work on st that uses the cursor: the event covers it)
     e = hipEventRecord(tr->ev_trace, st);
     if (e == hipSuccess) tr->trace_used = true;
     if (rc) return map_hip(rc);
+    if (e == hipSuccess && tr->timing) e = hipEventRecord(tr->ev1[s.slot], st);
     if (e != hipSuccess) return map_hip((int)e);
-    if (tr->timing) {
-        e = hipEventRecord(tr->ev1[slot], st);
-        if (e == hipSuccess) e = hipEventRecord(tr->ev2[slot], st);
-        if (e != hipSuccess) return map_hip((int)e);
-    }
-    rc = finish_slot(tr, slot, st, nxt, rng_guard);
-    if (rc == BIH_OK) tr->gb_prev_slot = slot;
+    rc = finish_slot(tr, s.slot, st, -1, s.nxt, s.guard);
+    if (rc == BIH_OK) tr->gb_prev_slot = s.slot;
     return rc;
 }
 
 int bih_render_gbuffer_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                               uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_gbuffer *d_planes,
                               void *stream) {
-    bih_rows rows;
-    const int rc = gbuffer_check(ctr, cam, w, h, spp, rows_in, d_planes, &rows);
-    if (rc || rows.nrows == 0) return rc;
+    Frame f = {cam, w, h, spp, frame, seed, {}};
+    const int rc = gbuffer_check(ctr, &f, rows_in, d_planes);
+    if (rc || f.rows.nrows == 0) return rc;
     bih_tree *tr = const_cast<bih_tree *>(ctr);
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
-    return gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, *d_planes, stream);
+    return gbuffer_locked(tr, f, *d_planes, stream);
 }
 
 int bih_render_gbuffer(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                        uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_gbuffer *host_planes) {
-    bih_rows rows;
-    int rc = gbuffer_check(ctr, cam, w, h, spp, rows_in, host_planes, &rows);
-    if (rc || rows.nrows == 0) return rc;
+    Frame f = {cam, w, h, spp, frame, seed, {}};
+    int rc = gbuffer_check(ctr, &f, rows_in, host_planes);
+    if (rc || f.rows.nrows == 0) return rc;
     bih_tree *tr = const_cast<bih_tree *>(ctr);
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
     // device planes of the ones asked for
-    const size_t P = (size_t)rows.nrows * w;
+    const size_t P = f.pixels();
     Stage<6> sg{{host_planes->hits, host_planes->depth, host_planes->prim, host_planes->bary, host_planes->normal,
                  host_planes->coverage},
                 {P * spp * sizeof(bih_hit), P * 4, P * 4, P * 8, P * 12, P * 4}};
@@ -2446,25 +2374,24 @@ int bih_render_gbuffer(const bih_tree *ctr, const bih_camera *cam, uint32_t w, u
     d.bary = static_cast<float *>(sg.dev(3));
     d.normal = static_cast<float *>(sg.dev(4));
     d.coverage = static_cast<uint32_t *>(sg.dev(5));
-    return sg.finish(tr, gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, d, nullptr));
+    return sg.finish(tr, gbuffer_locked(tr, f, d, nullptr));
 }
 
 // Argument checks of the six direct-lighting entries (bih_render_direct*,
 // bih_render_lights*, bih_render_area_lights*), each of which states its
 // lights as a bih_light_set: the G-buffer's checks, then the lights and lit's
 // alignment (BIH_ERR_INVALID all, so one order serves the three headers').
-// None touches the tree or a device.  *rows: the rows of the call.
+// None touches the tree or a device.  f, f->rows: as gbuffer_check.
 // ind: the planes of bih_render_indirect* (pl then holds its lit, irradiance
 // and rgba): "all planes NULL" is about the five, ls may be NULL or empty.
-static int light_set_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                           const bih_rows *rows_in, const bih_light_set *ls, const bih_direct *pl, bih_rows *rows,
-                           const bih_indirect *ind = nullptr) {
+static int light_set_check(const bih_tree *tr, Frame *f, const bih_rows *rows_in, const bih_light_set *ls,
+                           const bih_direct *pl, const bih_indirect *ind = nullptr) {
     // the G-buffer's "all planes NULL" is about the three planes here
     static float some_plane;
     bih_gbuffer g = {};
     if (pl && (pl->lit || pl->irradiance || pl->rgba)) g.depth = &some_plane;
     if (ind && (ind->bounce || ind->lit2)) g.depth = &some_plane;
-    const int rc = gbuffer_check(tr, cam, w, h, spp, rows_in, pl ? &g : nullptr, rows);
+    const int rc = gbuffer_check(tr, f, rows_in, pl ? &g : nullptr);
     if (rc) return rc;
     if (!ls) return BIH_ERR_INVALID;
     const uint64_t n = (uint64_t)ls->n_dir + ls->n_point + ls->n_area;
@@ -2483,22 +2410,22 @@ static void area_normal(const float *u, const float *v, float *nl) {
 }
 
 // The call's lights in the kernels' slot order: directional, point, then the
-// area lights' {corner, weight}; dj->area: what else the area kernels need.
-static void merge_light_set(const bih_light_set *ls, uint32_t spp, uint32_t frame, uint64_t seed, DirectJob *dj) {
+// area lights' {corner, weight}; l->area: what else the area kernels need.
+static void merge_light_set(const bih_light_set *ls, const Frame &f, bih::Lights *l) {
     static_assert(sizeof(bih_light) == 16 && BIH_MAX_LIGHTS == bih::kMaxLights, "bih_light / kMaxLights");
     static_assert(sizeof(bih_point_light) == 16, "bih_point_light shares bih_light's slots");
     static_assert(sizeof(bih_area_light) == 48 && BIH_MAX_AREA_LIGHTS == bih::kMaxAreaLights,
                   "bih_area_light / kMaxAreaLights");
-    dj->n_dir = ls->n_dir;
-    dj->n_lights = ls->n_dir + ls->n_point + ls->n_area;
-    if (ls->n_dir) memcpy(dj->lights, ls->dir, (size_t)ls->n_dir * sizeof(bih_light));
-    float *slot = dj->lights + 4 * (size_t)ls->n_dir;
+    l->n_dir = ls->n_dir;
+    l->n_lights = ls->n_dir + ls->n_point + ls->n_area;
+    if (ls->n_dir) memcpy(l->slots, ls->dir, (size_t)ls->n_dir * sizeof(bih_light));
+    float *slot = l->slots + 4 * (size_t)ls->n_dir;
     if (ls->n_point) memcpy(slot, ls->point, (size_t)ls->n_point * sizeof(bih_point_light));
     slot += 4 * (size_t)ls->n_point;
-    bih::AreaLights *al = &dj->area;
+    bih::AreaLights *al = &l->area;
     al->n = ls->n_area;
-    al->hseed = bih::area_seed_hash(seed);
-    al->fs0 = frame * spp;
+    al->hseed = bih::area_seed_hash(f.seed);
+    al->fs0 = f.frame * f.spp;
     for (uint32_t j = 0; j < ls->n_area; ++j) {
         const bih_area_light &a = ls->area[j];
         memcpy(slot + 4 * j, a.corner, 3 * sizeof(float));
@@ -2511,9 +2438,8 @@ static void merge_light_set(const bih_light_set *ls, uint32_t spp, uint32_t fram
 
 // A direct-lighting render into dj.planes under the tree's lock, arguments
 // checked, nrows > 0.
-static int direct_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t frame,
-                         uint64_t seed, const bih_rows &rows, const DirectJob &dj, void *stream) {
-    const size_t S = (size_t)rows.nrows * w * spp;
+static int direct_locked(bih_tree *tr, const Frame &f, const DirectJob &dj, void *stream) {
+    const size_t S = (size_t)f.samples();
     const bool own_lit = !dj.planes.lit && tr->dr_lit_cap < S;
     const bool own_lit2 = dj.indirect && !dj.ind.lit2 && tr->in_lit2_cap < S;
     const bool own_in = dj.indirect && tr->in_cap < S;
@@ -2529,48 +2455,46 @@ static int direct_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32
     if (rc) return rc;
     bih_gbuffer g = {};
     g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
-    return gbuffer_locked(tr, cam, w, h, spp, frame, seed, rows, g, stream, &dj);
+    return gbuffer_locked(tr, f, g, stream, &dj);
 }
 
 // The body of the six entries: the checks, then under the tree's lock the
 // merged lights and the render -- into the caller's device planes on `stream`,
 // or (host) into device planes of dr_stage on the tree's stream, copied to the
 // caller's before the call returns.
-static int render_light_set(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                            uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light_set *ls,
+static int render_light_set(const bih_tree *ctr, Frame f, const bih_rows *rows_in, const bih_light_set *ls,
                             const bih_direct *planes, void *stream, bool host) {
-    bih_rows rows;
-    int rc = light_set_check(ctr, cam, w, h, spp, rows_in, ls, planes, &rows);
-    if (rc || rows.nrows == 0) return rc;
+    int rc = light_set_check(ctr, &f, rows_in, ls, planes);
+    if (rc || f.rows.nrows == 0) return rc;
     bih_tree *tr = const_cast<bih_tree *>(ctr);
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
     DirectJob dj;
-    merge_light_set(ls, spp, frame, seed, &dj);
+    merge_light_set(ls, f, &dj.lights);
     dj.planes = *planes;
-    if (!host) return direct_locked(tr, cam, w, h, spp, frame, seed, rows, dj, stream);
-    const size_t P = (size_t)rows.nrows * w;
-    Stage<3> sg{{planes->lit, planes->irradiance, planes->rgba}, {P * spp * 8, P * 4, P * 4}};
+    if (!host) return direct_locked(tr, f, dj, stream);
+    const size_t P = f.pixels();
+    Stage<3> sg{{planes->lit, planes->irradiance, planes->rgba}, {P * f.spp * 8, P * 4, P * 4}};
     rc = sg.place(tr, &tr->dr_stage, &tr->dr_stage_cap);
     if (rc) return rc;
     dj.planes.lit = static_cast<uint64_t *>(sg.dev(0));
     dj.planes.irradiance = static_cast<float *>(sg.dev(1));
     dj.planes.rgba = static_cast<uint32_t *>(sg.dev(2));
-    return sg.finish(tr, direct_locked(tr, cam, w, h, spp, frame, seed, rows, dj, nullptr));
+    return sg.finish(tr, direct_locked(tr, f, dj, nullptr));
 }
 
 int bih_render_direct_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                              uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light *lights,
                              uint32_t n_lights, const bih_direct *d_planes, void *stream) {
     const bih_light_set ls = {lights, n_lights, nullptr, 0, nullptr, 0};
-    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, &ls, d_planes, stream, false);
+    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, d_planes, stream, false);
 }
 
 int bih_render_direct(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                       uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light *lights,
                       uint32_t n_lights, const bih_direct *host_planes) {
     const bih_light_set ls = {lights, n_lights, nullptr, 0, nullptr, 0};
-    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, &ls, host_planes, nullptr, true);
+    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, host_planes, nullptr, true);
 }
 
 int bih_render_lights_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
@@ -2578,7 +2502,7 @@ int bih_render_lights_device(const bih_tree *tr, const bih_camera *cam, uint32_t
                              uint32_t n_dir, const bih_point_light *point_lights, uint32_t n_point,
                              const bih_direct *d_planes, void *stream) {
     const bih_light_set ls = {dir_lights, n_dir, point_lights, n_point, nullptr, 0};
-    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, &ls, d_planes, stream, false);
+    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, d_planes, stream, false);
 }
 
 int bih_render_lights(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
@@ -2586,48 +2510,46 @@ int bih_render_lights(const bih_tree *tr, const bih_camera *cam, uint32_t w, uin
                       uint32_t n_dir, const bih_point_light *point_lights, uint32_t n_point,
                       const bih_direct *host_planes) {
     const bih_light_set ls = {dir_lights, n_dir, point_lights, n_point, nullptr, 0};
-    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, &ls, host_planes, nullptr, true);
+    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, host_planes, nullptr, true);
 }
 
 int bih_render_area_lights_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                                   uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                                   const bih_direct *d_planes, void *stream) {
-    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, ls, d_planes, stream, false);
+    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, d_planes, stream, false);
 }
 
 int bih_render_area_lights(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                            uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                            const bih_direct *host_planes) {
-    return render_light_set(tr, cam, w, h, spp, frame, seed, rows, ls, host_planes, nullptr, true);
+    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, host_planes, nullptr, true);
 }
 
 // The body of the two indirect-lighting entries, as render_light_set.
-static int render_indirect(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                           uint32_t frame, uint64_t seed, const bih_rows *rows_in, const bih_light_set *ls_in,
+static int render_indirect(const bih_tree *ctr, Frame f, const bih_rows *rows_in, const bih_light_set *ls_in,
                            const bih_bounce *bounce, const bih_indirect *planes, void *stream, bool host) {
     static const bih_light_set no_lights = {nullptr, 0, nullptr, 0, nullptr, 0};
     const bih_light_set *ls = ls_in ? ls_in : &no_lights;
-    bih_rows rows;
     bih_direct three = {};
     if (planes) three = bih_direct{planes->lit, planes->irradiance, planes->rgba};
-    int rc = light_set_check(ctr, cam, w, h, spp, rows_in, ls, planes ? &three : nullptr, &rows, planes);
+    int rc = light_set_check(ctr, &f, rows_in, ls, planes ? &three : nullptr, planes);
     if (rc) return rc;
     if (!bounce) return BIH_ERR_INVALID;
     if (((uintptr_t)planes->lit2 & 7u) || ((uintptr_t)planes->bounce & 15u)) return BIH_ERR_INVALID;
-    if (rows.nrows == 0) return BIH_OK;
+    if (f.rows.nrows == 0) return BIH_OK;
     bih_tree *tr = const_cast<bih_tree *>(ctr);
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
     DirectJob dj;
-    merge_light_set(ls, spp, frame, seed, &dj);
+    merge_light_set(ls, f, &dj.lights);
     dj.planes = three;
     dj.indirect = true;
     dj.bounce = *bounce;
     dj.ind = *planes;
-    if (!host) return direct_locked(tr, cam, w, h, spp, frame, seed, rows, dj, stream);
-    const size_t P = (size_t)rows.nrows * w;
+    if (!host) return direct_locked(tr, f, dj, stream);
+    const size_t P = f.pixels(), S = (size_t)f.samples();
     Stage<5> sg{{planes->lit, planes->bounce, planes->lit2, planes->irradiance, planes->rgba},
-                {P * spp * 8, P * spp * sizeof(bih_hit), P * spp * 8, P * 4, P * 4}};
+                {S * 8, S * sizeof(bih_hit), S * 8, P * 4, P * 4}};
     rc = sg.place(tr, &tr->in_stage, &tr->in_stage_cap);
     if (rc) return rc;
     dj.planes.lit = static_cast<uint64_t *>(sg.dev(0));
@@ -2635,19 +2557,19 @@ static int render_indirect(const bih_tree *ctr, const bih_camera *cam, uint32_t 
     dj.ind.lit2 = static_cast<uint64_t *>(sg.dev(2));
     dj.planes.irradiance = static_cast<float *>(sg.dev(3));
     dj.planes.rgba = static_cast<uint32_t *>(sg.dev(4));
-    return sg.finish(tr, direct_locked(tr, cam, w, h, spp, frame, seed, rows, dj, nullptr));
+    return sg.finish(tr, direct_locked(tr, f, dj, nullptr));
 }
 
 int bih_render_indirect_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                                uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                                const bih_bounce *bounce, const bih_indirect *d_planes, void *stream) {
-    return render_indirect(tr, cam, w, h, spp, frame, seed, rows, ls, bounce, d_planes, stream, false);
+    return render_indirect(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, bounce, d_planes, stream, false);
 }
 
 int bih_render_indirect(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                         uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                         const bih_bounce *bounce, const bih_indirect *host_planes) {
-    return render_indirect(tr, cam, w, h, spp, frame, seed, rows, ls, bounce, host_planes, nullptr, true);
+    return render_indirect(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, bounce, host_planes, nullptr, true);
 }
 
 int bih_bounce_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s, const float n[3],

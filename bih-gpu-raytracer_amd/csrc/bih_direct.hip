@@ -646,10 +646,10 @@ __global__ void __launch_bounds__(kDSetupT) k_indirect_resolve(const IArgs ia) {
 }
 
 // The argument block of a call: the frame, the tree, the lights in slot order
-// and, with area lights, their panels (else only aa.d is filled and read).
-static void fill_args(AArgs &aa, const DeviceTree &t, const RenderArgs &ra, const float *lights, uint32_t n_lights,
-                      uint32_t n_dir, const AreaLights *area) {
-    const uint32_t n_area = area ? area->n : 0u;
+// with the area lights' panels, the primary level's planes and scratch, and the
+// work area's words.  (Without an area light the direct kernels take aa.d alone.)
+static void fill_args(AArgs &aa, const DeviceTree &t, const RenderArgs &ra, const Lights &l, const DirectPlanes &p,
+                      const Scratch &s, const WorkArea &wa) {
     DArgs &a = aa.d;
     for (int k = 0; k < 12; ++k) a.cam[k] = ra.cam[k];
     a.w = ra.w;
@@ -660,29 +660,45 @@ static void fill_args(AArgs &aa, const DeviceTree &t, const RenderArgs &ra, cons
     a.band_h = ra.band_h;
     a.band_step = ra.band_step;
     a.d_base = ra.d_base;
-    a.n_lights = n_lights;
-    a.n_dir = n_dir;
+    a.n_lights = l.n_lights;
+    a.n_dir = l.n_dir;
     a.hdr = t.hdr;
     a.nodes = t.nodes;
     a.tris = t.tris_s;
     a.dup = t.dup_cnt;
     a.rng_in = ra.rng_in;
+    a.rec = reinterpret_cast<uint4 *>(s.rec);
+    a.list = s.list;
+    a.face = s.face;
+    a.lit = p.lit;
+    a.irradiance = p.irradiance;
+    a.rgba = p.rgba;
+    a.count = wa.word(kCurListed);
+    a.cursor = wa.items();
+    a.spill = wa.spill;
     for (uint32_t k = 0; k < kMaxLights; ++k) {
-        const bool on = k < n_lights;
-        a.lights[k] = DLight{on ? lights[4 * k] : 0.0f, on ? lights[4 * k + 1] : 0.0f, on ? lights[4 * k + 2] : 0.0f,
-                             on ? lights[4 * k + 3] : 0.0f};
+        const bool on = k < l.n_lights;
+        a.lights[k] = DLight{on ? l.slots[4 * k] : 0.0f, on ? l.slots[4 * k + 1] : 0.0f, on ? l.slots[4 * k + 2] : 0.0f,
+                             on ? l.slots[4 * k + 3] : 0.0f};
     }
+    const uint32_t n_area = l.area.n;
+    aa.n_area = n_area;
+    aa.hseed = l.area.hseed;
+    aa.fs0 = l.area.fs0;
     if (n_area) {
-        aa.n_area = n_area;
-        aa.hseed = area->hseed;
-        aa.fs0 = area->fs0;
         for (uint32_t j = 0; j < kMaxAreaLights; ++j)
             for (int c = 0; c < 3; ++c) {
-                aa.panel[j].u[c] = j < n_area ? area->uvn[j][c] : 0.0f;
-                aa.panel[j].v[c] = j < n_area ? area->uvn[j][3 + c] : 0.0f;
-                aa.panel[j].nl[c] = j < n_area ? area->uvn[j][6 + c] : 0.0f;
+                aa.panel[j].u[c] = j < n_area ? l.area.uvn[j][c] : 0.0f;
+                aa.panel[j].v[c] = j < n_area ? l.area.uvn[j][3 + c] : 0.0f;
+                aa.panel[j].nl[c] = j < n_area ? l.area.uvn[j][6 + c] : 0.0f;
             }
     }
+}
+
+// The launch's listed-sample count and item cursor start from zero.
+static hipError_t reset_counts(const DArgs &a, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(a.count, 0, sizeof(uint32_t), st);
+    return e == hipSuccess ? hipMemsetAsync(a.cursor, 0, sizeof(unsigned long long), st) : e;
 }
 
 // The shadow pass over the samples listed in aa.d: the kernel of the call's
@@ -706,32 +722,20 @@ static hipError_t launch_shadow(const AArgs &aa, uint32_t n_area, uint64_t n, ui
 
 }  // namespace
 
-int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes &p, const float *lights,
-                  uint32_t n_lights, uint32_t n_dir, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
-                  uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream,
-                  const AreaLights *area) {
+int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes &p, const Lights &l, const Scratch &s,
+                  const WorkArea &wa, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
-    if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0 || n_lights == 0) return 0;
-    if (n_lights > kMaxLights || n_dir > n_lights) return (int)hipErrorInvalidValue;
-    const uint32_t n_area = area ? area->n : 0u;
-    if (n_area > kMaxAreaLights || n_area > n_lights - n_dir) return (int)hipErrorInvalidValue;
+    const uint32_t n_area = l.area.n;
+    if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0 || l.n_lights == 0) return 0;
+    if (l.n_lights > kMaxLights || l.n_dir > l.n_lights) return (int)hipErrorInvalidValue;
+    if (n_area > kMaxAreaLights || n_area > l.n_lights - l.n_dir) return (int)hipErrorInvalidValue;
     static_assert(offsetof(DArgs, n_dir) + 4 == offsetof(DArgs, hdr) && offsetof(DArgs, n_dir) % 8 == 4,
                   "n_dir sits in what was padding before the pointers: the argument block has not grown");
-    const bool point = n_dir < n_lights;   // else: bih_render_direct's kernels
-    AArgs aa;                              // (n_area == 0: only its DArgs is filled and passed on)
-    DArgs &a = aa.d;
-    fill_args(aa, t, ra, lights, n_lights, n_dir, area);
-    a.rec = reinterpret_cast<uint4 *>(rec);
-    a.list = list;
-    a.face = face;
-    a.lit = p.lit;
-    a.irradiance = p.irradiance;
-    a.rgba = p.rgba;
-    a.count = count;
-    a.cursor = cursor;
-    a.spill = spill;
-    hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), st);
-    if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), st);
+    const bool point = l.n_dir < l.n_lights;   // else: bih_render_direct's kernels
+    AArgs aa;
+    const DArgs &a = aa.d;
+    fill_args(aa, t, ra, l, p, s, wa);
+    hipError_t e = reset_counts(a, st);
     if (e != hipSuccess) return (int)e;
     const uint64_t P = (uint64_t)ra.nrows * ra.w, n = P * ra.spp;
     const dim3 sgrid((uint32_t)((n + kDSetupT - 1) / kDSetupT));
@@ -740,13 +744,13 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
     else hipLaunchKernelGGL(k_direct_setup, sgrid, dim3(kDSetupT), 0, st, a);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    e = launch_shadow(aa, n_area, n, lds_slots, max_blocks, st);
+    e = launch_shadow(aa, n_area, n, wa.lds_slots, wa.max_blocks, st);
     if (e != hipSuccess) return (int)e;
     if (p.irradiance || p.rgba) {
         const dim3 rgrid((uint32_t)((P + kDSetupT - 1) / kDSetupT));
         if (n_area) hipLaunchKernelGGL(k_area_resolve, rgrid, dim3(kDSetupT), 0, st, aa);
-        else if (point) hipLaunchKernelGGL(k_lights_resolve, rgrid, dim3(kDSetupT), 0, st, aa.d);
-        else hipLaunchKernelGGL(k_direct_resolve, rgrid, dim3(kDSetupT), 0, st, aa.d);
+        else if (point) hipLaunchKernelGGL(k_lights_resolve, rgrid, dim3(kDSetupT), 0, st, a);
+        else hipLaunchKernelGGL(k_direct_resolve, rgrid, dim3(kDSetupT), 0, st, a);
         e = hipGetLastError();
     }
     return (int)e;
@@ -756,70 +760,50 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
 // setup, the primary shadow pass, the bounce walk, the secondary setup, the
 // secondary shadow pass (the primary's kernels on the secondary records; list,
 // face, count and cursor are the primary's, free again), the resolve.
-int launch_indirect(const DeviceTree &t, const RenderArgs &ra, const IndirectPlanes &p, const float *lights,
-                    uint32_t n_lights, uint32_t n_dir, const AreaLights &area, float albedo, float sky, void *rec,
-                    void *rec2, uint32_t *list, unsigned long long *face, uint32_t *blist, uint32_t lds_slots,
-                    uint32_t *count, unsigned long long *cursor, uint32_t *bcount, uint32_t *spill,
-                    uint32_t max_blocks, void *stream) {
+int launch_indirect(const DeviceTree &t, const RenderArgs &ra, const IndirectPlanes &p, const Lights &l, float albedo,
+                    float sky, const Scratch &s, const WorkArea &wa, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
     if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0) return 0;
-    if (n_lights > kMaxLights || n_dir > n_lights) return (int)hipErrorInvalidValue;
-    if (area.n > kMaxAreaLights || area.n > n_lights - n_dir) return (int)hipErrorInvalidValue;
+    if (l.n_lights > kMaxLights || l.n_dir > l.n_lights) return (int)hipErrorInvalidValue;
+    if (l.area.n > kMaxAreaLights || l.area.n > l.n_lights - l.n_dir) return (int)hipErrorInvalidValue;
     static_assert(sizeof(IArgs) <= 4096, "kernel arguments");
     IArgs ia;
-    fill_args(ia.a, t, ra, lights, n_lights, n_dir, &area);
-    ia.a.n_area = area.n;      // (fill_args leaves the three alone without an area light)
-    ia.a.hseed = area.hseed;
-    ia.a.fs0 = area.fs0;
-    DArgs &a = ia.a.d;
-    a.rec = reinterpret_cast<uint4 *>(rec);
-    a.list = list;
-    a.face = face;
-    a.lit = p.lit;
-    a.irradiance = p.irradiance;
-    a.rgba = p.rgba;
-    a.count = count;
-    a.cursor = cursor;
-    a.spill = spill;
-    ia.rec2 = reinterpret_cast<uint4 *>(rec2);
+    fill_args(ia.a, t, ra, l, p, s, wa);
+    const DArgs &a = ia.a.d;
+    ia.rec2 = reinterpret_cast<uint4 *>(s.rec2);
     ia.lit2 = p.lit2;
     ia.bounce = reinterpret_cast<uint4 *>(p.bounce);
-    ia.blist = blist;
-    ia.bcount = bcount;
+    ia.blist = s.blist;
+    ia.bcount = wa.word(kCurBounce);
     ia.tri_idx = t.vals;
     ia.albedo = albedo;
     ia.sky = sky;
     const uint64_t P = (uint64_t)ra.nrows * ra.w, n = P * ra.spp;
     const dim3 sgrid((uint32_t)((n + kDSetupT - 1) / kDSetupT));
-    const auto reset = [&](bool with_bcount) {
-        hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), st);
-        if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), st);
-        if (e == hipSuccess && with_bcount) e = hipMemsetAsync(bcount, 0, sizeof(uint32_t), st);
-        return e;
-    };
-    hipError_t e = reset(true);
+    hipError_t e = reset_counts(a, st);
+    if (e == hipSuccess) e = hipMemsetAsync(ia.bcount, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_indirect_setup, sgrid, dim3(kDSetupT), 0, st, ia);
     e = hipGetLastError();
-    if (e == hipSuccess && n_lights) e = launch_shadow(ia.a, area.n, n, lds_slots, max_blocks, st);
-    if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), st);
+    if (e == hipSuccess && l.n_lights) e = launch_shadow(ia.a, l.area.n, n, wa.lds_slots, wa.max_blocks, st);
+    if (e == hipSuccess) e = hipMemsetAsync(a.cursor, 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return (int)e;
     {
         const uint64_t need = (n + kDT - 1) / kDT;
-        const dim3 grid((uint32_t)(need < max_blocks ? need : max_blocks)), block(kDT);
-        if (lds_slots == (uint32_t)kTraceLdsTest) hipLaunchKernelGGL((k_bounce<kTraceLdsTest>), grid, block, 0, st, ia);
+        const dim3 grid((uint32_t)(need < wa.max_blocks ? need : wa.max_blocks)), block(kDT);
+        if (wa.lds_slots == (uint32_t)kTraceLdsTest) hipLaunchKernelGGL((k_bounce<kTraceLdsTest>), grid, block, 0, st, ia);
         else hipLaunchKernelGGL((k_bounce<kTraceLds>), grid, block, 0, st, ia);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = reset(false);
+    if (e == hipSuccess) e = reset_counts(a, st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_indirect_setup2, sgrid, dim3(kDSetupT), 0, st, ia);
     e = hipGetLastError();
-    if (e == hipSuccess && n_lights) {
+    if (e == hipSuccess && l.n_lights) {
         AArgs a2 = ia.a;       // the secondary level: its records and lit words
         a2.d.rec = ia.rec2;
         a2.d.lit = ia.lit2;
-        e = launch_shadow(a2, area.n, n, lds_slots, max_blocks, st);
+        e = launch_shadow(a2, l.area.n, n, wa.lds_slots, wa.max_blocks, st);
     }
     if (e != hipSuccess) return (int)e;
     if (p.irradiance || p.rgba) {

@@ -183,10 +183,9 @@ __global__ void __launch_bounds__(kGT) k_gbuffer(const GArgs a) {
 // over the local rows (*tiles_x across), else waves of 64 / spp local pixels.
 uint64_t gbuffer_tiles(uint32_t w, uint32_t nrows, uint32_t spp, uint32_t *tiles_x) {
     if ((spp & (spp - 1)) == 0) {
-        const uint32_t lpx = 6u - (uint32_t)__builtin_ctz(spp);
-        const uint32_t tw = 1u << ((lpx + 1) / 2), th = 1u << (lpx / 2);
-        *tiles_x = (w + tw - 1) / tw;
-        return (uint64_t)*tiles_x * ((nrows + th - 1) / th);
+        const Tiles t = tiles_of(w, nrows, spp);
+        *tiles_x = t.x;
+        return t.count();
     }
     const uint64_t ppw = 64 / spp;
     *tiles_x = 0;
@@ -194,8 +193,7 @@ uint64_t gbuffer_tiles(uint32_t w, uint32_t nrows, uint32_t spp, uint32_t *tiles
 }
 
 int launch_gbuffer(const DeviceTree &t, const RenderArgs &ra, const GBufferPlanes &p,
-                   const unsigned long long *hit_mask, uint32_t lds_slots, uint32_t *cursor, uint32_t *spill,
-                   uint32_t max_blocks, void *stream, bool sorted_prim) {
+                   const unsigned long long *hit_mask, const WorkArea &wa, void *stream, bool sorted_prim) {
     const hipStream_t st = (hipStream_t)stream;
     if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0 || ra.spp > 64) return 0;
     const bool pow2 = (ra.spp & (ra.spp - 1)) == 0;
@@ -227,12 +225,12 @@ int launch_gbuffer(const DeviceTree &t, const RenderArgs &ra, const GBufferPlane
     a.bary = p.bary;
     a.normal = p.normal;
     a.coverage = p.coverage;
-    a.cursor = cursor;
-    a.spill = spill;
-    hipError_t e = hipMemsetAsync(cursor, 0, sizeof(uint32_t), st);
+    a.cursor = wa.word(kCurTaken);
+    a.spill = wa.spill;
+    hipError_t e = hipMemsetAsync(a.cursor, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return (int)e;
-    const dim3 grid(a.ntiles < max_blocks ? a.ntiles : max_blocks), block(kGT);
-    const bool small = lds_slots == (uint32_t)kTraceLdsTest;
+    const dim3 grid(a.ntiles < wa.max_blocks ? a.ntiles : wa.max_blocks), block(kGT);
+    const bool small = wa.lds_slots == (uint32_t)kTraceLdsTest;
     if (small && pow2) hipLaunchKernelGGL((k_gbuffer<kTraceLdsTest, true>), grid, block, 0, st, a);
     else if (small) hipLaunchKernelGGL((k_gbuffer<kTraceLdsTest, false>), grid, block, 0, st, a);
     else if (pow2) hipLaunchKernelGGL((k_gbuffer<kGLds, true>), grid, block, 0, st, a);

@@ -217,6 +217,19 @@ struct RenderArgs {
     uint32_t st_seq = 0;    // this launch's sequence number (1 .. 1023)
 };
 
+// Packet tiles of a w x nrows launch with spp samples per pixel (a power of
+// two <= 64): tw x th pixels with tw * th * spp = 64 (the kernels'
+// TileShape<log2 spp>, bih_render.hip), x across and y down.
+struct Tiles {
+    uint32_t tw, th, x, y;
+    constexpr uint64_t count() const { return (uint64_t)x * y; }
+};
+constexpr Tiles tiles_of(uint32_t w, uint32_t nrows, uint32_t spp) {
+    const uint32_t lp = 6u - (uint32_t)__builtin_ctz(spp);
+    const uint32_t tw = 1u << ((lp + 1) / 2), th = 1u << (lp / 2);
+    return Tiles{tw, th, (w + tw - 1) / tw, (nrows + th - 1) / th};
+}
+
 // stamp word (RenderArgs::stamps)
 constexpr uint32_t kStampFrameBits = 26;
 constexpr uint32_t kStampFrameMax = (1u << kStampFrameBits) - 1u;
@@ -328,29 +341,44 @@ size_t whitted_bytes(uint64_t rays);
 int launch_whitted(const RenderArgs &a, void *mem, uint64_t rays, uint32_t *d_hits, void *stream, void *ev_k0,
                    void *ev_k1, bool count, const unsigned long long *hit_mask = nullptr, uint32_t tiles_x = 0);
 int whitted_work(const void *mem, uint64_t rays, uint32_t ray_counts[9], unsigned long long work[18], void *stream);
-// ray queries (bih_trace.hip): n caller rays (bih_ray) against tree t, results
-// (bih_hit, or one byte per ray when occluded) to d_out in caller order.
-// cursor: one u32, zeroed by the launch; spill: trace_spill_words(max_blocks)
-// u32, max_blocks = trace_grid_blocks(device), the persistent grid's cap.
-// lds_slots: kTraceLdsTest selects the instantiation that keeps only that many
-// stack slots per lane on chip (BIH_PARAM_TRACE_LDS_SLOTS), anything else kTraceLds.
+// The work area the ray-query, G-buffer and lighting launches share (one user
+// at a time: bih_capi.cpp's ev_trace chain).  cursor: a block of
+// kTraceCursorBytes whose words each launch zeroes before it counts in them;
+// spill: trace_spill_words(max_blocks) u32, max_blocks =
+// trace_grid_blocks(device), the persistent grid's cap.  lds_slots:
+// kTraceLdsTest selects the instantiation that keeps only that many stack
+// slots per lane on chip (BIH_PARAM_TRACE_LDS_SLOTS), anything else kTraceLds.
 // The stack is bih_closest.h's LaneStack, shared with the G-buffer and C4, so
 // the small instantiation exercises the spill code of all three.
+constexpr uint32_t kCurTaken = 0;    // u32: rays (launch_trace) / tiles (launch_gbuffer) taken
+constexpr uint32_t kCurItems = 2;    // u64: shadow / bounce items taken
+constexpr uint32_t kCurListed = 4;   // u32: listed samples
+constexpr uint32_t kCurBounce = 6;   // u32: samples whose bounce hit
+constexpr size_t kTraceCursorBytes = ((kCurBounce + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
+struct WorkArea {
+    uint32_t *cursor = nullptr;
+    uint32_t *spill = nullptr;
+    uint32_t max_blocks = 0;
+    uint32_t lds_slots = 0;
+    uint32_t *word(uint32_t k) const { return cursor + k; }
+    unsigned long long *items() const { return reinterpret_cast<unsigned long long *>(cursor + kCurItems); }
+};
 constexpr int kTraceLds = 10;       // as kWLds (bih_whitted.hip)
 constexpr int kTraceLdsTest = 2;
 uint32_t trace_grid_blocks(int device);
 size_t trace_spill_words(uint32_t blocks);
+// ray queries (bih_trace.hip): n caller rays (bih_ray) against tree t, results
+// (bih_hit, or one byte per ray when occluded) to d_out in caller order.
 // query: BIH_QUERY_CLOSEST / _OCCLUDED, with kQueryTHi for the segment queries
 constexpr uint32_t kQueryTHi = 0x10u;   // BIH_QUERY_T_HI
 int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, uint32_t query, void *d_out,
-                 uint32_t lds_slots, uint32_t *cursor, uint32_t *spill, uint32_t max_blocks, void *stream);
+                 const WorkArea &wa, void *stream);
 // G-buffer render (bih_gbuffer.hip): the closest hit of every primary sample
 // of the frame `a` describes (cam, w, h, spp, rows, d_base, rng_in), to
 // p.hits (bih_hit[P*spp], sample = local pixel * spp + s) and the pixel planes
 // resolved from them; a null plane is not written.  hit_mask (optional, spp a
 // power of two): per tile the samples that can hit (RenderArgs::hit_mask); the
-// others get the miss record unwalked.  cursor, spill, max_blocks, lds_slots:
-// as launch_trace (the kernel borrows the trace's cursor and spill area).
+// others get the miss record unwalked.
 // sorted_prim: the records' prim is the triangle's sorted position, not its
 // file-order index (bih_direct.hip's scratch records).
 struct GBufferPlanes {
@@ -361,20 +389,16 @@ struct GBufferPlanes {
     float *normal = nullptr;
     uint32_t *coverage = nullptr;
 };
+// (any spp <= 64: a power of two takes tiles_of's tiles, else waves of 64 / spp local pixels, *tiles_x = 0)
 uint64_t gbuffer_tiles(uint32_t w, uint32_t nrows, uint32_t spp, uint32_t *tiles_x);
 int launch_gbuffer(const DeviceTree &t, const RenderArgs &a, const GBufferPlanes &p,
-                   const unsigned long long *hit_mask, uint32_t lds_slots, uint32_t *cursor, uint32_t *spill,
-                   uint32_t max_blocks, void *stream, bool sorted_prim = false);
+                   const unsigned long long *hit_mask, const WorkArea &wa, void *stream, bool sorted_prim = false);
 // Direct lighting (bih_direct.hip), behind a launch_gbuffer of the same frame
-// `a` on the same stream that left its hit records, sorted_prim, in rec
-// (bih_hit[P*spp]): per sample the lights (n_lights of 4 floats, host memory,
-// copied into the kernel arguments: the first n_dir {dir[3], weight}, the rest
-// point lights {pos[3], weight}) that face its hit triangle and
-// reach its hit point, to p.lit (u64[P*spp], never null), and the pixel sums
-// resolved from them (a null plane is not written).  list (u32[P*spp]), face
-// (u64[P*spp]): the hit samples with a facing light.  count (one u32) and
-// cursor (one u64) are zeroed by the launch; spill, max_blocks, lds_slots: as
-// launch_trace.
+// `a` on the same stream that left its hit records, sorted_prim, in s.rec:
+// per sample the lights that face its hit triangle and reach its hit point, to
+// p.lit (u64[P*spp], never null), and the pixel sums resolved from them (a
+// null plane is not written).  s.list, s.face: the hit samples with a facing
+// light.
 constexpr uint32_t kMaxLights = 64;   // BIH_MAX_LIGHTS: one bit each of a sample's lit word
 constexpr uint32_t kMaxAreaLights = 16;   // BIH_MAX_AREA_LIGHTS
 // The area lights of a call (bih_render_area_lights*): the last n of its light
@@ -385,34 +409,42 @@ struct AreaLights {
     uint32_t fs0 = 0;           // frame * spp (wrapping)
     float uvn[kMaxAreaLights][9];   // edge_u, edge_v, nl = cross(edge_u, edge_v) in the header's order
 };
+// The lights of a call in the kernels' slot order (host memory, copied into
+// the kernel arguments): n_lights slots of 4 floats, the first n_dir
+// {dir[3], weight}, then point lights {pos[3], weight}, then the area lights.
+struct Lights {
+    float slots[4 * kMaxLights];
+    uint32_t n_lights = 0, n_dir = 0;
+    AreaLights area;
+};
+// Per-sample scratch of a lighting launch (device; P*spp entries each): rec
+// (16 bytes), list (u32), face (u64); one-bounce launches also rec2 (16
+// bytes) and blist (u32) of the second level.
+struct Scratch {
+    void *rec = nullptr;
+    uint32_t *list = nullptr;
+    unsigned long long *face = nullptr;
+    void *rec2 = nullptr;
+    uint32_t *blist = nullptr;
+};
 struct DirectPlanes {
     unsigned long long *lit = nullptr;
     float *irradiance = nullptr;
     uint32_t *rgba = nullptr;
 };
-int launch_direct(const DeviceTree &t, const RenderArgs &a, const DirectPlanes &p, const float *lights,
-                  uint32_t n_lights, uint32_t n_dir, void *rec, uint32_t *list, unsigned long long *face, uint32_t lds_slots,
-                  uint32_t *count, unsigned long long *cursor, uint32_t *spill, uint32_t max_blocks, void *stream,
-                  const AreaLights *area = nullptr);
+int launch_direct(const DeviceTree &t, const RenderArgs &a, const DirectPlanes &p, const Lights &l, const Scratch &s,
+                  const WorkArea &wa, void *stream);
 // One-bounce indirect lighting (bih_direct.hip), behind a launch_gbuffer as
 // launch_direct: the primary level as there (n_lights may be 0: sky only),
 // then per hit sample one bounce ray (bih_bounce.h; area.hseed and area.fs0
 // are read whatever area.n), its hit lit by the same lights, and the sums of
-// both levels.  rec2 (16 bytes per sample) and blist (4) are the call's own
-// next to launch_direct's rec, list and face; lit and lit2 are never null;
-// bcount is a zeroed-by-the-call word as count.
-struct IndirectPlanes {
-    unsigned long long *lit = nullptr;
+// both levels.  lit and lit2 are never null.
+struct IndirectPlanes : DirectPlanes {
     void *bounce = nullptr;             // bih_hit[P*spp], prim in file order, or null
     unsigned long long *lit2 = nullptr;
-    float *irradiance = nullptr;
-    uint32_t *rgba = nullptr;
 };
-int launch_indirect(const DeviceTree &t, const RenderArgs &a, const IndirectPlanes &p, const float *lights,
-                    uint32_t n_lights, uint32_t n_dir, const AreaLights &area, float albedo, float sky, void *rec,
-                    void *rec2, uint32_t *list, unsigned long long *face, uint32_t *blist, uint32_t lds_slots,
-                    uint32_t *count, unsigned long long *cursor, uint32_t *bcount, uint32_t *spill,
-                    uint32_t max_blocks, void *stream);
+int launch_indirect(const DeviceTree &t, const RenderArgs &a, const IndirectPlanes &p, const Lights &l, float albedo,
+                    float sky, const Scratch &s, const WorkArea &wa, void *stream);
 int launch_rng_init(uint32_t *rng, uint32_t w, uint32_t row0, uint32_t nrows, uint32_t band_h,
                     uint32_t band_step, uint64_t seed, uint64_t skip, int device, void *stream);
 // dst = src's per-pixel state advanced by `steps` draws (planes of `pixels`; dst may be src)
@@ -438,16 +470,10 @@ int launch_chunk_order(const uint32_t *cost, uint32_t chunks_x, uint32_t nchunks
 // and m arrival counters
 size_t prim_bytes(uint32_t n, uint32_t m);
 size_t fast_offset(uint32_t n, uint32_t m);   // byte offset of the shortcut boxes
-int launch_prim(const float *tris, uint32_t n, const uint4 *nodes, const int32_t *first_idx,
-                const uint32_t *dup_cnt, const int32_t *leaf_parent, const int32_t *parent,
-                uint32_t m, const float origin[3], const float dmax[3], float *prim,
-                void *stream);
+int launch_prim(const DeviceTree &t, const float origin[3], float *prim, void *stream);
 // node_cull (the second set of node records above) and the alive bytes
-int launch_prim_cull(uint32_t n, const uint4 *nodes, const int32_t *first_idx, const uint32_t *dup_cnt,
-                     uint32_t m, const float origin[3], float *prim, void *stream);
-int launch_fast_boxes(const float *tris, uint32_t n, const uint4 *nodes, const int32_t *first_idx,
-                      const uint32_t *dup_cnt, const int32_t *leaf_parent, const int32_t *parent,
-                      uint32_t m, const float origin[3], const float dmax[3], float *prim, void *stream);
+int launch_prim_cull(const DeviceTree &t, const float origin[3], float *prim, void *stream);
+int launch_fast_boxes(const DeviceTree &t, const float origin[3], const float dmax[3], float *prim, void *stream);
 bool render_uses_prim(uint32_t spp);
 
 // frustum bins (bih_bins.hip): camera setup (false: degenerate camera, no

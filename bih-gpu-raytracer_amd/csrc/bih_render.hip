@@ -501,6 +501,14 @@ struct TileShape {   // TW x TH pixels, TW*TH = 64 >> log2(spp)
     static constexpr uint32_t TH = 1u << (LP / 2);
 };
 
+template <int L>
+constexpr bool host_tiles_agree() {
+    return tiles_of(1, 1, 1u << L).tw == TileShape<L>::TW && tiles_of(1, 1, 1u << L).th == TileShape<L>::TH;
+}
+static_assert(host_tiles_agree<0>() && host_tiles_agree<1>() && host_tiles_agree<2>() && host_tiles_agree<3>() &&
+                  host_tiles_agree<4>() && host_tiles_agree<5>() && host_tiles_agree<6>(),
+              "tiles_of (bih_internal.h) is TileShape on the host");
+
 // Ray id -> (local pixel, sample).  Ids run tile-major: 64 consecutive ids
 // are one TW x TH pixel tile, pixel-major within the tile.
 template <int LOG2SPP>
@@ -3161,18 +3169,19 @@ size_t fast_offset(uint32_t n, uint32_t m) {
     return (size_t)n * 64 + 2 * (size_t)(m + 1) * 16 + alive_bytes(m);
 }
 
-int launch_prim(const float *tris, uint32_t n, const uint4 *nodes, const int32_t *first_idx,
-                const uint32_t *dup_cnt, const int32_t *leaf_parent, const int32_t *parent,
-                uint32_t m, const float origin[3], const float dmax[3], float *prim,
-                void *stream) {
+// (n triangles, m = U-1 internal nodes of the tree the records are for)
+static uint32_t internal_nodes(const DeviceTree &t) { return t.u > 0 ? t.u - 1 : 0; }
+
+int launch_prim(const DeviceTree &t, const float origin[3], float *prim, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
+    const uint32_t n = t.n, m = internal_nodes(t);
     if (n > 0)
         hipLaunchKernelGGL(k_tri_prim, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
-                           tris, n, origin[0], origin[1], origin[2], prim);
+                           t.tris_s, n, origin[0], origin[1], origin[2], prim);
     if (m > 0) {
         uint4 *rec = reinterpret_cast<uint4 *>(prim + 16ull * n);
         const dim3 gn((m + kThreads - 1) / kThreads);
-        hipLaunchKernelGGL(k_node_prim, gn, dim3(kThreads), 0, st, nodes, m, origin[0], origin[1],
+        hipLaunchKernelGGL(k_node_prim, gn, dim3(kThreads), 0, st, t.nodes, m, origin[0], origin[1],
                            origin[2], nullptr, nullptr, rec, nullptr);
     }
     return (int)hipGetLastError();
@@ -3181,24 +3190,24 @@ int launch_prim(const float *tris, uint32_t n, const uint4 *nodes, const int32_t
 // The culled node records (node_cull) for the records launch_prim wrote:
 // only the BIH walk kernels read them, so renders through the frustum bins
 // never pay for them (bih_capi.cpp builds them on first use per camera).
-int launch_prim_cull(uint32_t n, const uint4 *nodes, const int32_t *first_idx, const uint32_t *dup_cnt,
-                     uint32_t m, const float origin[3], float *prim, void *stream) {
+int launch_prim_cull(const DeviceTree &t, const float origin[3], float *prim, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
+    const uint32_t m = internal_nodes(t);
     if (m > 0) {
-        uint4 *rec = reinterpret_cast<uint4 *>(prim + 16ull * n);
+        uint4 *rec = reinterpret_cast<uint4 *>(prim + 16ull * t.n);
         uint8_t *leaf_alive = reinterpret_cast<uint8_t *>(rec + 2 * (size_t)(m + 1));
         uint8_t *node_alive = leaf_alive + (m + 1);
         const dim3 gl((m + 1 + kThreads - 1) / kThreads), gn((m + kThreads - 1) / kThreads);
-        hipLaunchKernelGGL(k_leaf_alive, gl, dim3(kThreads), 0, st, prim, first_idx, dup_cnt, m + 1,
+        hipLaunchKernelGGL(k_leaf_alive, gl, dim3(kThreads), 0, st, prim, t.first_idx, t.dup_cnt, m + 1,
                            leaf_alive);
         hipError_t e = hipMemsetAsync(node_alive, 1, m, st);
         if (e != hipSuccess) return (int)e;
         // dead subtrees of a random soup are a few levels high (1M triangles:
         // 12 % of the nodes, every one found within 7 passes)
         for (int pass = 0; pass < 8; ++pass)
-            hipLaunchKernelGGL(k_node_alive, gn, dim3(kThreads), 0, st, nodes, m, leaf_alive,
+            hipLaunchKernelGGL(k_node_alive, gn, dim3(kThreads), 0, st, t.nodes, m, leaf_alive,
                                node_alive);
-        hipLaunchKernelGGL(k_node_prim, gn, dim3(kThreads), 0, st, nodes, m, origin[0], origin[1],
+        hipLaunchKernelGGL(k_node_prim, gn, dim3(kThreads), 0, st, t.nodes, m, origin[0], origin[1],
                            origin[2], leaf_alive, node_alive, rec, rec + (m + 1));
     }
     return (int)hipGetLastError();
@@ -3206,24 +3215,23 @@ int launch_prim_cull(uint32_t n, const uint4 *nodes, const int32_t *first_idx, c
 
 // The any-hit BIH walk's shortcut boxes for the records launch_prim wrote
 // (only renders without frustum bins read them).
-int launch_fast_boxes(const float *tris, uint32_t n, const uint4 *nodes, const int32_t *first_idx,
-                      const uint32_t *dup_cnt, const int32_t *leaf_parent, const int32_t *parent,
-                      uint32_t m, const float origin[3], const float dmax[3], float *prim, void *stream) {
+int launch_fast_boxes(const DeviceTree &t, const float origin[3], const float dmax[3], float *prim, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
+    const uint32_t m = internal_nodes(t);
     if (m > 0) {
         const dim3 gl((m + 1 + kThreads - 1) / kThreads), gn((m + kThreads - 1) / kThreads);
         hipError_t e = hipSuccess;
         // shortcut boxes of the any-hit walk: tight (pass 1), miss-proof (pass 2)
-        float *fast = reinterpret_cast<float *>(reinterpret_cast<char *>(prim) + fast_offset(n, m));
+        float *fast = reinterpret_cast<float *>(reinterpret_cast<char *>(prim) + fast_offset(t.n, m));
         uint32_t *arrive = reinterpret_cast<uint32_t *>(fast + 2 * 16ull * (m + 1));
         for (int pass = 0; pass < 2; ++pass) {
             float *boxes = fast + pass * 16ull * (m + 1);
             e = hipMemsetAsync(arrive, 0, sizeof(uint32_t) * m, st);
             if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(k_fast_fit, gl, dim3(kThreads), 0, st, tris, prim, first_idx,
-                               dup_cnt, leaf_parent, parent, nodes, m + 1, origin[0], origin[1],
+            hipLaunchKernelGGL(k_fast_fit, gl, dim3(kThreads), 0, st, t.tris_s, prim, t.first_idx,
+                               t.dup_cnt, t.leaf_parent, t.parent, t.nodes, m + 1, origin[0], origin[1],
                                origin[2], pass == 1, dmax[0], dmax[1], dmax[2], arrive, boxes);
-            hipLaunchKernelGGL(k_fast_refs, gn, dim3(kThreads), 0, st, nodes, m, first_idx, dup_cnt,
+            hipLaunchKernelGGL(k_fast_refs, gn, dim3(kThreads), 0, st, t.nodes, m, t.first_idx, t.dup_cnt,
                                boxes);
         }
     }
@@ -3277,13 +3285,10 @@ size_t spill_words(uint32_t blocks) {
 
 uint32_t chunk_count(uint32_t w, uint32_t nrows, uint32_t spp, uint32_t *chunks_x) {
     if (spp == 0 || spp > 64 || (spp & (spp - 1)) != 0) return 0;
-    const int L = __builtin_ctz(spp);
-    const uint32_t pix = 64u >> L;
-    const uint32_t tw = 1u << ((6 - L + 1) / 2), th = pix / tw;
-    const uint32_t tiles_x = (w + tw - 1) / tw, tiles_y = (nrows + th - 1) / th;
-    const uint32_t cx = (tiles_x + kChunkW - 1) / kChunkW;
+    const Tiles t = tiles_of(w, nrows, spp);
+    const uint32_t cx = (t.x + kChunkW - 1) / kChunkW;
     if (chunks_x) *chunks_x = cx;
-    return cx * ((tiles_y + kChunkH - 1) / kChunkH);
+    return cx * ((t.y + kChunkH - 1) / kChunkH);
 }
 
 int launch_chunk_order(const uint32_t *cost, uint32_t chunks_x, uint32_t nchunks, uint32_t *order,
@@ -3416,9 +3421,7 @@ int launch_render(const RenderArgs &a, uint32_t traverse, void *stream, void *ev
     if (spp <= 64 && (spp & (spp - 1)) == 0) {
         static const Variant var = variant_from_env();
         const int L = __builtin_ctz(spp);
-        const uint32_t pix = 64u >> L;
-        const uint32_t tw = 1u << ((6 - L + 1) / 2), th = pix / tw;
-        const uint64_t tiles = (uint64_t)((a.w + tw - 1) / tw) * ((a.nrows + th - 1) / th);
+        const uint64_t tiles = tiles_of(a.w, a.nrows, spp).count();
         if (tiles == 0) return 0;
         uint32_t blocks = (uint32_t)((tiles + 3) / 4);
         if (blocks > grid) blocks = grid;

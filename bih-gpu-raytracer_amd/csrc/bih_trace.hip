@@ -158,7 +158,7 @@ size_t trace_spill_words(uint32_t blocks) {
 }
 
 int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, uint32_t query, void *d_out,
-                 uint32_t lds_slots, uint32_t *cursor, uint32_t *spill, uint32_t max_blocks, void *stream) {
+                 const WorkArea &wa, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
     if (n == 0) return 0;
     TraceArgs a;
@@ -170,13 +170,13 @@ int launch_trace(const DeviceTree &t, const void *d_rays, uint32_t n, uint32_t q
     a.rays = reinterpret_cast<const float4 *>(d_rays);
     a.out = d_out;
     a.n = n;
-    a.cursor = cursor;
-    a.spill = spill;
-    hipError_t e = hipMemsetAsync(cursor, 0, sizeof(uint32_t), st);
+    a.cursor = wa.word(kCurTaken);
+    a.spill = wa.spill;
+    hipError_t e = hipMemsetAsync(a.cursor, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return (int)e;
     const uint32_t need = (n + kTT - 1) / kTT;
-    const dim3 grid(need < max_blocks ? need : max_blocks), block(kTT);
-    const bool small = lds_slots == (uint32_t)kTraceLdsTest;
+    const dim3 grid(need < wa.max_blocks ? need : wa.max_blocks), block(kTT);
+    const bool small = wa.lds_slots == (uint32_t)kTraceLdsTest;
     const bool occluded = (query & ~kQueryTHi) == 1u;   // BIH_QUERY_OCCLUDED
     if (query & kQueryTHi) {
         if (small && occluded) hipLaunchKernelGGL((k_trace_within<kTraceLdsTest, true>), grid, block, 0, st, a);
