@@ -2684,7 +2684,7 @@ int bih_sync(const bih_tree *tr, void *stream) {
 #endif
 #if BIH_FAST_COUNTERS
     if (tr->work && tr->last_slot >= 0) {
-        uint32_t c[84];
+        uint32_t c[bih::kItemWord + 15];
         if (hipMemcpyAsync(c, tr->work + (size_t)tr->last_slot * bih::kWorkWords, sizeof c,
                            hipMemcpyDeviceToHost, st) == hipSuccess &&
             hipStreamSynchronize(st) == hipSuccess) {
@@ -2702,6 +2702,15 @@ int bih_sync(const bih_tree *tr, void *stream) {
                     " unverified %u packets-with-miss %u planned %u plan-disagrees %u cache-hits %u"
                     " | cycles walk %llu verify %llu\n",
                     c[40], c[41], c[42], c[43], c[44], c[45], c[46], c[47], c[39], c[38], c[52], cb[0], cb[1]);
+            // k_render_bins' items: the split the launch used, the queue's
+            // live and heavy tiles, and what each item counted
+            const uint32_t *ci = c + bih::kItemWord;
+            fprintf(stderr,
+                    "bin-items nframes %u ns %u fpi %u hs %u fhv %u stamped %u measuring %u live %u heavy %u"
+                    " | items %u split-items %u heavy-items %u zero-frame-items %u tile-frames %u"
+                    " bg-tile-frames %u\n",
+                    ci[0], ci[1], ci[2], ci[3], ci[4], ci[5], ci[6], ci[7], ci[8], ci[9], ci[10], ci[11], ci[12],
+                    ci[13], ci[14]);
             const unsigned long long *ph = reinterpret_cast<const unsigned long long *>(c + 64);
             fprintf(stderr,
                     "bin-phases (wave cycles) queue %llu background %llu setup %llu walk %llu verify %llu"

@@ -42,8 +42,11 @@ constexpr int kLdsStack = BIH_LDS_STACK;
 // tile slots, so its diagnostic builds use the first slot line's words:
 // [64..76) six u64 phase cycle sums (BIH_PHASES, "bin-phases"), [76..84) the
 // root-path check's site counters (path_site_count, "bin-pathcheck");
-// [84..96) are free
+// [84..96) are free; and the second slot line's: [96..111) the item counters
+// (kItemWord, "bin-items": nine words of the launch's split, six counted per
+// item)
 constexpr uint32_t kSlotStrideWords = 32;
+constexpr uint32_t kItemWord = 96;
 constexpr uint32_t kWorkWords = 64 + kSlotStrideWords * 1024 + 64;   // + histograms (counter builds)
 constexpr uint32_t kHistWord = 64 + kSlotStrideWords * 1024;
 constexpr uint32_t kBinGlobalMax = 4096;          // longer global lists: no bins (the shortcut walk)
@@ -65,8 +68,9 @@ constexpr uint32_t kBinBlockTiles = BIH_BLOCK_TILES;   // tile rectangle of a bi
 //   BIH_FAST_COUNTERS    work counters of the shortcut passes and of
 //                        k_render_bins (BIH_FC(x): x in counter builds only),
 //                        every plan's root path written for the cross-check;
-//                        bih_sync prints "fast-counters" / "bin-counters"
-//                        lines (tools/fast_counters.py, bench.py --full)
+//                        bih_sync prints "fast-counters" / "bin-counters" /
+//                        "bin-items" lines (tools/fast_counters.py, bench.py
+//                        --full, tests/test_item_splits.py)
 //   BIH_PHASES           k_render_bins' wave cycles per phase (BIH_PH), on by
 //                        default in counter builds; bih_sync prints
 //                        "bin-phases"

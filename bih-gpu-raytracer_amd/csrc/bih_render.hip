@@ -2082,7 +2082,24 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
         if (q.hs < ns) q.hs = ns;
     }
     const uint32_t fhv = (a.nframes + q.hs - 1u) / q.hs;   // frames per item of a heavy tile
+    // (as ns above: only the items that have a frame -- 16 frames in 12 items
+    // of 2 left four of them empty; hs == ns then means no heavy tiles, extra())
+    q.hs = (a.nframes + fhv - 1u) / fhv;
     uint32_t it = 0;
+#if BIH_FAST_COUNTERS
+    // item counters (bih_sync prints them, "bin-items"), work[kItemWord ..]:
+    // the split this launch uses and the queue's live and heavy counts, then
+    // what lane 0 of every item counts
+    if (blockIdx.x == 0 && tid == 0) {
+        uint32_t live = 0, heavy = 0;
+        for (uint32_t b = 0; b < 8u; ++b) {
+            live += q.hdr[b].y;
+            heavy += q.extra(b);
+        }
+        const uint32_t v[9] = {a.nframes, q.ns, fpi, q.hs, fhv, STAMP ? 1u : 0u, COST ? 1u : 0u, live, heavy};
+        for (uint32_t k = 0; k < 9u; ++k) a.work[kItemWord + k] = v[k];
+    }
+#endif
 #if BIH_PHASES
     // per-phase wave cycles (s_memtime), summed over waves into work[64..75]
     unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};   // queue, background, setup, walk, verify, write
@@ -2109,6 +2126,9 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
         // order holds for the items; then the background items (`it` past
         // hb.y: 64 tiles each, every frame)
         uint32_t f0 = 0, nf = a.nframes;
+#if BIH_FAST_COUNTERS
+        const bool ic_heavy = it < q.hv * q.hs;
+#endif
         if (q.ns > 1u || q.hv) {   // (one item per tile: `it` is the tile's position already)
             const uint32_t hx = q.hv * q.hs;
             if (it < hx) {
@@ -2128,6 +2148,21 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
                 }
             }
         }
+#if BIH_FAST_COUNTERS
+        if (lane == 0) {
+            if (it < hb.y) {
+                atomicAdd(a.work + kItemWord + 9, 1u);
+                if (f0 > 0u) atomicAdd(a.work + kItemWord + 10, 1u);
+                if (ic_heavy) atomicAdd(a.work + kItemWord + 11, 1u);
+                if (f0 >= nf) atomicAdd(a.work + kItemWord + 12, 1u);
+                else atomicAdd(a.work + kItemWord + 13, nf - f0);
+            } else {
+                const uint32_t k0 = (it - hb.y) * 64u;
+                const uint32_t n = k0 < hb.z ? (hb.z - k0 < 64u ? hb.z - k0 : 64u) : 0u;
+                atomicAdd(a.work + kItemWord + 14, n * (nf - f0));
+            }
+        }
+#endif
         if (it >= hb.y) {
             // background: every sample misses (Color's background), whatever its jitter
             const uint32_t k = (it - hb.y) * 64u + lane;
@@ -2208,6 +2243,15 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
         // tile's stamp is the queue's sequence number; the triangle's leaf
         // word and plan come from its record (the words every list entry of
         // the triangle carries)
+        // A stale id is sound: the cache only chooses which triangle a lane
+        // tries first.  Every cached id is re-tested on the new ray by the
+        // exact intersector on the current soup's record and then by that
+        // record's own plan (the frame loop below), so an id left by another
+        // queue, camera or soup -- or read next to a stamp another item of
+        // the tile just wrote, there is no ordering between the two -- either
+        // proves a hit Color() would find or leaves the lane to the list
+        // walk; only ti < n_tris is needed to read it.
+        // (tests/test_item_splits.py::test_hit_cache_sequence)
         if (use_cache && a.hcache && valid && a.hstamp[tile] == a.hseq) {
             const uint32_t ti = a.hcache[(uint64_t)tile * 64 + lane];
             if (ti < a.hdr_n_tris) {
