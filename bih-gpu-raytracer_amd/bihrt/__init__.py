@@ -203,6 +203,16 @@ class GPUArrayManager:
         check(load().bih_bins_get_stats(self._tree, C.byref(st)), "bih_bins_get_stats")
         return st
 
+    def bins_solid_masks(self):
+        """(sure words [tiles_y, tiles_x] uint16, solid tile count) of the
+        current camera's bins (bih_bins_solid_masks; diagnostic)."""
+        st = self.bins_stats()
+        out = np.zeros((st.tiles_y, st.tiles_x), np.uint16)
+        n = C.c_uint32(0)
+        check(load().bih_bins_solid_masks(self._tree, out.ctypes.data_as(C.POINTER(C.c_uint16)), out.size,
+                                          C.byref(n)), "bih_bins_solid_masks")
+        return out, int(n.value)
+
     def export(self, which: int, dtype) -> np.ndarray:
         n = C.c_size_t(0)
         check(load().bih_tree_export(self._tree, which, None, C.byref(n)), "bih_tree_export")

@@ -216,6 +216,7 @@ def load():
     L.bih_set_timing.argtypes = [vp, i32]
     L.bih_last_render_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.bih_bins_get_stats.argtypes = [vp, C.POINTER(BinsStats)]
+    L.bih_bins_solid_masks.argtypes = [vp, C.POINTER(C.c_uint16), C.c_size_t, C.POINTER(u32)]
     L.bih_reserve.argtypes = [vp, u32, u32, u32, C.POINTER(Rows), u32]
     L.bih_tree_set_param.argtypes = [vp, i32, u64]
     L.bih_whitted_work.argtypes = [vp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64)]
@@ -250,7 +251,7 @@ def load():
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
                  "bih_render_whitted_device", "bih_render_whitted", "bih_render_device_frames",
-                 "bih_bins_get_stats", "bih_reserve", "bih_tree_set_param", "bih_whitted_work",
+                 "bih_bins_get_stats", "bih_bins_solid_masks", "bih_reserve", "bih_tree_set_param", "bih_whitted_work",
                  "bih_host_register", "bih_host_unregister", "bih_render_history", "bih_trace_device", "bih_trace",
                  "bih_render_gbuffer_device", "bih_render_gbuffer", "bih_render_direct_device", "bih_render_direct",
                  "bih_render_lights_device", "bih_render_lights", "bih_render_area_lights_device",

@@ -148,8 +148,9 @@ __device__ __forceinline__ float f32_up(double x) {
 }
 
 // The edge pre-test of one triangle (header comment): 3 x {K0 + M, Ku, Kv}.
+// mup[j] = M of edge j rounded up to f32, for sure_threshold.
 __device__ __forceinline__ void edge_pretest(const float *rr, float a, float b, float cc,
-                                             const BinCamera &c, float *out) {
+                                             const BinCamera &c, float *out, float (&mup)[3]) {
     double e1[3], e2[3], sv[3];
     for (int k = 0; k < 3; ++k) {
         e1[k] = rr[k];
@@ -166,6 +167,7 @@ __device__ __forceinline__ void edge_pretest(const float *rr, float a, float b, 
         G[2][k] = (1.0 + (double)cc) * Nd[k] - Nu[k] - Q[k];
     }
     const double e = 0x1p-24;
+#pragma unroll
     for (int j = 0; j < 3; ++j) {
         const double K0 = dot3(c.A, G[j]), Ku = dot3(c.hh, G[j]), Kv = dot3(c.vert, G[j]);
         const double dg = fabs(G[j][0]) * c.delta[0] + fabs(G[j][1]) * c.delta[1] +
@@ -177,7 +179,16 @@ __device__ __forceinline__ void edge_pretest(const float *rr, float a, float b, 
         out[3 * j] = f32_up(K0 + M + 8.0 * e * M);
         out[3 * j + 1] = (float)Ku;
         out[3 * j + 2] = (float)Kv;
+        mup[j] = f32_up(M);
     }
+}
+
+// One threshold of sure acceptance (bih_bound.h, sure_applies) for an edge
+// inflated by aj: 2 aj U + 2 M rounded up, with 1 % for the f32 test.  The
+// record's f32 evaluation at (u, v), lowered by edge_margin, exceeds D.G_j by
+// at most K0' - K0 <= 1.01 M, the K roundings (<< M) and |delta|.|G| <= M / 4.
+__device__ __forceinline__ float sure_threshold(float aj, double U, float m_up) {
+    return f32_up(1.01 * (2.02 * (double)aj * U + 2.0 * (double)m_up));
 }
 
 
@@ -258,8 +269,9 @@ __device__ __forceinline__ double plane_lmin(double xmin, double xmax, double va
 // chain of selects over the three axes in registers.
 __device__ uint32_t triangle_plan(const double (*X)[3], uint32_t leaf, const TreeHeader *hdr,
                                   const float *o, const uint4 *node_prim, const int32_t *leaf_parent,
-                                  const int32_t *parent, float *vals, double *tab) {
+                                  const int32_t *parent, float *vals, double *tab, bool &slab_ok) {
     constexpr uint32_t kFull = 3u;
+    slab_ok = false;
     double amin[3], amax[3];
     int sgn[3];
     bool finite_ok = true;   // no NaN corner coordinate: the one-value test is exact
@@ -293,6 +305,13 @@ __device__ uint32_t triangle_plan(const double (*X)[3], uint32_t leaf, const Tre
                 if (can_exit) slabX.L[j] = fmin(slabX.L[j], l.L[j]);
             }
         }
+    // The slab test's own outcome (scene_slab, bih_render.hip): each of its
+    // comparisons sets an entry face's t = fl(val fl(1 / D[a])) against an
+    // exit face's, the same form as the tree planes', so by the argument
+    // above no entry face's t exceeds an exit face's -- in_box is true for
+    // every ray the intersector accepts -- when slabE.L + slabX.L > 0 at the
+    // three corners (inf - inf = NaN compares false: not proven).
+    slab_ok = slabE.L[0] + slabX.L[0] > 0.0 && slabE.L[1] + slabX.L[1] > 0.0 && slabE.L[2] + slabX.L[2] > 0.0;
     // the root path, root first (Karras: leaf k lies left of node n iff
     // k <= split(n); every thread reads the top levels from cache), each
     // plane against the last plane of the other kind.  The last planes are
@@ -398,7 +417,8 @@ __device__ void write_path(const uint4 *__restrict__ node_prim, uint32_t k, uint
 // bx1 << 16, by0 | by1 << 16; empty = bx0 > bx1) and its list entry
 // binrec[i]; the global list takes the rest.  leaf = the leaf of each sorted
 // triangle (DeviceTree::tri_leaf).  The triangle's verification plan
-// (triangle_plan) is computed here too (128 VGPRs, 4 waves/SIMD).
+// (triangle_plan) is computed here too, and with `solid` the thresholds of
+// sure acceptance for the triangles the plan and the slab bit admit.
 __global__ void __launch_bounds__(kThreads) k_bin_fp(const float *__restrict__ prim, uint32_t n, BinCamera c,
                                                       const TreeHeader *__restrict__ hdr,
                                                      const uint4 *__restrict__ node_prim,
@@ -410,7 +430,7 @@ __global__ void __launch_bounds__(kThreads) k_bin_fp(const float *__restrict__ p
                                                      uint32_t *__restrict__ gcount,
                                                      uint32_t *__restrict__ glist,
                                                      const uint32_t *__restrict__ live,
-                                                     const uint32_t *__restrict__ live_count) {
+                                                     const uint32_t *__restrict__ live_count, uint32_t solid) {
     __shared__ double s_tab[12 * kThreads];
     const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
     if (j >= *live_count) return;
@@ -431,13 +451,15 @@ __global__ void __launch_bounds__(kThreads) k_bin_fp(const float *__restrict__ p
     if (ok) {
         // corners of the inflated triangle: depth and image (u, v)
         int front = 0, back = 0;
-        double max_depth = 0.0;
+        double max_depth = 0.0, min_depth = INFINITY;
+        double Lsure = 0.0;            // the det bound behind a, b, cc (sure acceptance, bih_bound.h)
         double cx[3][3];               // corners X_j (camera-relative)
         auto corners = [&](float a_, float b_, float c_) {
             const double cu[3] = {-(double)a_, 1.0 + (double)b_ + (double)c_, -(double)a_};
             const double cv[3] = {-(double)b_, -(double)b_, 1.0 + (double)a_ + (double)c_};
             front = back = 0;
             max_depth = 0.0;
+            min_depth = INFINITY;
             umin = vmin = INFINITY;
             umax = vmax = -INFINITY;
             for (int j = 0; j < 3; ++j) {
@@ -449,6 +471,7 @@ __global__ void __launch_bounds__(kThreads) k_bin_fp(const float *__restrict__ p
                 if (depth > 1e-9 * mag) {
                     ++front;
                     max_depth = fmax(max_depth, depth);
+                    min_depth = fmin(min_depth, depth);
                     // X = lambda (A + u h + v vert), lambda = depth / (A.n)
                     const double inv = c.an / depth;
                     const double u = dot3(X, c.hu) * inv - c.ahu;
@@ -476,6 +499,7 @@ __global__ void __launch_bounds__(kThreads) k_bin_fp(const float *__restrict__ p
                     a = a2;
                     b = b2;
                     cc = c2;
+                    Lsure = L;
                     corners(a, b, cc);
                 }
             }
@@ -522,9 +546,34 @@ __global__ void __launch_bounds__(kThreads) k_bin_fp(const float *__restrict__ p
             rect = make_uint2((x0 / c.tw) | ((x1 / c.tw) << 16), (y0 / c.th) | ((y1 / c.th) << 16));
         }
         // the edge pre-test now (rr, a, b, cc end here), the plan after
-        edge_pretest(rr, a, b, cc, c, rec);
+        float mup[3];
+        edge_pretest(rr, a, b, cc, c, rec, mup);
+        bool slab_ok = false;
         if (side == 1)
-            plan = triangle_plan(cx, leaf, hdr, c.o, node_prim, leaf_parent, parent, plan_vals, s_tab + threadIdx.x);
+            plan = triangle_plan(cx, leaf, hdr, c.o, node_prim, leaf_parent, parent, plan_vals, s_tab + threadIdx.x,
+                                 slab_ok);
+        // Sure acceptance, only for a triangle whose every decision is proven
+        // (plan 0: the kernel reads no plan value) and whose rays provably
+        // pass the slab test: a, b, cc came from den = Lsure (>= 2e-6 >
+        // miss_bary's own 0.99e-6 - Ed), U bounds the det over the refined
+        // triangle.  Such a triangle carries kPlanSure in word 11 and the
+        // three thresholds in the plan values' place (k_bin_count; the list
+        // entries hold words 0..11 only, without the bit).  The record is
+        // read again: its registers went to the plan.
+        if (solid && plan == 0u && slab_ok && (float)Lsure >= 2e-6f) {
+            float r2[13];
+#pragma unroll
+            for (int k = 0; k < 13; ++k) r2[k] = r[k];
+            const double U = det_upper_bound(r2, 2.0 * c.an - c.dn_lb, min_depth);
+            const float t0 = sure_threshold(a, U, mup[0]), t1 = sure_threshold(b, U, mup[1]),
+                        t2 = sure_threshold(cc, U, mup[2]);
+            if (sure_applies(r2, Lsure, U, a, b, cc) && t0 < 1e30f && t1 < 1e30f && t2 < 1e30f) {
+                plan_vals[0] = t0;
+                plan_vals[1] = t1;
+                plan_vals[2] = t2;
+                plan |= kPlanSure;
+            }
+        }
         brect[i] = rect;
     } else {
         // no bound: the always-passing pre-test, every packet tests it
@@ -537,10 +586,10 @@ __global__ void __launch_bounds__(kThreads) k_bin_fp(const float *__restrict__ p
     }
     // the list entry: edge pre-test, triangle, leaf, plan
     rec[9] = __uint_as_float(i);
-    rec[10] = __uint_as_float(leaf | (plan == 0u ? 0x80000000u : 0u));
+    rec[10] = __uint_as_float(leaf | ((plan & ~kPlanSure) == 0u ? 0x80000000u : 0u));
     rec[11] = __uint_as_float(plan);
     // counter builds check every plan against the root-path check: all paths
-    if (plan == 3u || BIH_FAST_COUNTERS) write_path(node_prim, leaf, path);
+    if ((plan & 3u) == 3u || BIH_FAST_COUNTERS) write_path(node_prim, leaf, path);
     for (int k = 0; k < 4; ++k) rec[12 + k] = plan_vals[k];
     float4 *o = reinterpret_cast<float4 *>(binrec + 16ull * i);
     for (int k = 0; k < 4; ++k) o[k] = make_float4(rec[4 * k], rec[4 * k + 1], rec[4 * k + 2], rec[4 * k + 3]);
@@ -637,6 +686,56 @@ __device__ __forceinline__ uint32_t pixel_mask(const float4 r0, const float4 r1,
     return m;
 }
 
+// Sure mask of a 4 x 4-pixel tile for a triangle that carries the sure
+// thresholds (k_bin_fp: kPlanSure, s.x .. s.z).  Each pixel is cut into
+// kSureQ x kSureQ sub-rectangles of its (u, v) range, kSureN = 4 kSureQ per
+// tile side; bit row * kSureN + col of m[] is set only when every sample in
+// that sub-rectangle is accepted by the f32 intersector and reaches the
+// triangle in the reference walk (bih_bound.h, sure_applies).  A pixel whose
+// sub-rectangles are all sure -- each by some triangle of the tile, not
+// necessarily the same one -- has every sample hit whatever its jitter: with
+// triangles a few pixels across, a pixel wholly inside one triangle is much
+// rarer than one covered by two or three.  The sub-rectangles of a pixel,
+// padded like pixel_mask's rectangles, overlap by the pads and together cover
+// the pixel's rectangle (the bounds (x + j / kSureQ) are exact in f32).
+// pixel_mask's terms with min where it takes max: the smallest value of edge
+// e over the sub-rectangle, lowered by the evaluation's margin T, must exceed
+// s[e].  A NaN sum compares false: not sure.
+constexpr uint32_t kSureN = 4u * kSureQ;
+__device__ __forceinline__ void sure_mask(const float4 r0, const float4 r1, const float4 r2, const float4 s,
+                                          uint32_t bx, uint32_t by, uint32_t w, uint32_t h, uint32_t *m) {
+    const float k[9] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x};
+    const float st[3] = {s.x, s.y, s.z};
+    const float pad = 0x1p-20f, step = 1.0f / (float)kSureQ;
+    const float iw = 1.0f / (float)w, ih = 1.0f / (float)h;
+    float ua[kSureN], ub[kSureN], va[kSureN], vb[kSureN];
+#pragma unroll
+    for (uint32_t j = 0; j < kSureN; ++j) {
+        const float x = (float)(bx * kSureN + j) * step, y = (float)(by * kSureN + j) * step;
+        ua[j] = x * iw - pad;
+        ub[j] = (x + step) * iw + pad;
+        va[j] = y * ih - pad;
+        vb[j] = (y + step) * ih + pad;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kSureWords; ++i) m[i] = 0xFFFFFFFFu;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        const float K0 = k[3 * e], Ku = k[3 * e + 1], Kv = k[3 * e + 2];
+        const float T = edge_margin(K0, Ku, Kv) + st[e];
+        float cu[kSureN], cv[kSureN];
+#pragma unroll
+        for (uint32_t j = 0; j < kSureN; ++j) {
+            cu[j] = K0 + fminf(Ku * ua[j], Ku * ub[j]);
+            cv[j] = fminf(Kv * va[j], Kv * vb[j]);
+        }
+#pragma unroll
+        for (uint32_t py = 0; py < kSureN; ++py)
+#pragma unroll
+            for (uint32_t px = 0; px < kSureN; ++px)
+                if (!(cu[px] + cv[py] > T)) m[(py * kSureN + px) >> 5] &= ~(1u << ((py * kSureN + px) & 31u));
+    }
+}
 // The (triangle, tile) pairs of a block's alive triangles (k_cam_tris' list,
 // entries blockIdx.x * kThreads ..): the tile rectangles' areas are scanned in
 // LDS and the block's threads take the pairs in turn (pair p: the triangle
@@ -736,6 +835,9 @@ __device__ __forceinline__ uint32_t entry_bucket(int cls, uint32_t pm) {
 // counts also go to blkcnt[block][..] for k_bin_fill, which takes the same
 // blocks and rectangles (a pass of its own would recount them).
 constexpr uint32_t kBlockTiles = kBinBlockTiles;
+// SURE: also the tiles' sure words (an instance of its own: sure_mask costs
+// registers, and only bins builds that classify solid tiles pay them).
+template <bool SURE>
 __global__ void __launch_bounds__(kThreads) k_bin_count(const uint2 *__restrict__ brect,
                                                         const uint32_t *__restrict__ live,
                                                         const uint32_t *__restrict__ live_count,
@@ -746,7 +848,8 @@ __global__ void __launch_bounds__(kThreads) k_bin_count(const uint2 *__restrict_
                                                         unsigned long long *__restrict__ total64,
                                                         uint32_t *__restrict__ pres, uint32_t pres_cap,
                                                         unsigned long long *__restrict__ pcount,
-                                                        uint32_t *__restrict__ pbase_out) {
+                                                        uint32_t *__restrict__ pbase_out,
+                                                        uint32_t *__restrict__ sure) {
     __shared__ unsigned long long s_cnt[kBlockTiles];
     __shared__ uint32_t s_rect[4];   // x0, x1, y0, y1 of the block's footprints
     __shared__ unsigned long long s_tot;   // the block's entries (64-bit: the list total may pass 2^32)
@@ -797,6 +900,18 @@ __global__ void __launch_bounds__(kThreads) k_bin_count(const uint2 *__restrict_
         if (pb != ~0u) pres[pb + p] = cls ? (0x80000000u | (pm << 8) | q) : 0u;
         if (!cls) return;
         ++mine;
+        // the tile's sure pixels (4 x 4-pixel tiles): the union over its
+        // entries that carry the thresholds (k_bin_fp: no-check plan, bit 31)
+        if (SURE && (__float_as_uint(r2.w) & kPlanSure)) {
+            // (gathering the bits per block in LDS first, one pair of global
+            // atomics per tile and block, left the kernel's time where it was)
+            const float4 r3 = binrec[4ull * i + 3];
+            uint32_t sm[kSureWords];
+            sure_mask(r0, r1, r2, r3, bx, by, w, h, sm);
+#pragma unroll
+            for (uint32_t k = 0; k < kSureWords; ++k)
+                if (sm[k]) atomicOr(sure + (uint64_t)kSureWords * (by * bins_x + bx) + k, sm[k]);
+        }
         if (use_lds) {
             atomicAdd(&s_cnt[(by - ry0) * rw + (bx - rx0)], 1ull << (kBucketBits * q));
         } else {
@@ -930,7 +1045,7 @@ __global__ void __launch_bounds__(kThreads) k_bin_fill(const uint2 *__restrict__
         float4 *o = list + (uint64_t)kBinEntryF4 * pos;
         o[0] = r0;
         o[1] = r1;
-        o[2] = make_float4(r2.x, r2.y, r2.z, __uint_as_float((__float_as_uint(r2.w) & 0xFFFFu) | (pm << 16)));
+        o[2] = make_float4(r2.x, r2.y, r2.z, __uint_as_float((__float_as_uint(r2.w) & 0xFFFFu & ~kPlanSure) | (pm << 16)));
     });
 }
 
@@ -980,8 +1095,9 @@ __global__ void k_bin_status(uint32_t *__restrict__ g, uint32_t cap) {
 // frame ranges.  Built once per camera, image, row set and cost state.
 constexpr uint32_t kQBands = 8, kQClasses = 65;   // live classes 0..63 (costliest first), 64: background
 constexpr uint32_t kQCount = 0, kQStart = kQBands * kQClasses, kQCur = 2 * kQBands * kQClasses,
-                   kQHdr = 3 * kQBands * kQClasses, kQHeavy = kQHdr + 4 * kQBands, kQWords = 2048;
-static_assert(kQHeavy + kQBands <= kQWords, "queue words");
+                   kQHdr = 3 * kQBands * kQClasses, kQHeavy = kQHdr + 4 * kQBands, kQSolid = kQHeavy + kQBands,
+                   kQWords = 2048;
+static_assert(kQSolid < kQWords && kQSolid - kQHdr == kBinQSolidWord, "queue words");
 constexpr float kHeavyFactor = 2.0f;
 __device__ __forceinline__ uint32_t queue_bin(uint32_t t, uint32_t tiles_x, uint32_t row0,
                                               uint32_t band_h, uint32_t band_step, uint32_t th,
@@ -1013,12 +1129,16 @@ __global__ void __launch_bounds__(kThreads) k_queue_class(const uint32_t *__rest
                                                           uint32_t band_h, uint32_t band_step,
                                                           uint32_t th, uint32_t bins_x, uint32_t lpt,
                                                           const uint32_t *__restrict__ cost,
+                                                          const uint32_t *__restrict__ sure, uint32_t w,
+                                                          uint32_t h, uint32_t nrows,
                                                           uint16_t *__restrict__ cls,
                                                           uint32_t *__restrict__ qw) {
     // class counts aggregated per block in LDS: one global atomic per class
     // present (a tile row band has a handful), not one per tile
     __shared__ uint32_t hist[kQBands * kQClasses];
+    __shared__ uint32_t s_solid;
     for (uint32_t k = threadIdx.x; k < kQBands * kQClasses; k += kThreads) hist[k] = 0;
+    if (threadIdx.x == 0) s_solid = 0;
     __syncthreads();
     const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
     if (t < ntiles) {
@@ -1028,13 +1148,42 @@ __global__ void __launch_bounds__(kThreads) k_queue_class(const uint32_t *__rest
         const uint32_t len = off[b + 1] - off[b] + gn;
         const uint32_t band = (uint32_t)(((uint64_t)(t / tiles_x) * kQBands) / tiles_y);
         const uint32_t lc = !lpt ? 0u : (cost ? cost_class(cost[b]) : (uint32_t)__clz(len));
-        const uint32_t k = band * kQClasses + (len ? lc : kQClasses - 1);
-        cls[t] = (uint16_t)k;
+        // Solid: the tile's sure word (k_bin_count) covers every pixel of the
+        // tile that lies in the image and in the launch's rows -- every sample
+        // hits, whatever its jitter.  Only with 4 x 4-pixel tiles (sure is
+        // null otherwise), an empty global list (with one, every tile is live)
+        // and the tile's rows in its bin's rows of the same number.
+        bool solid = false;
+        if (sure && g == 0u && len && th == 4u) {
+            const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
+            uint32_t need[kSureWords];
+            for (uint32_t i = 0; i < kSureWords; ++i) need[i] = 0u;
+            bool any = false;
+            solid = true;
+            for (uint32_t r = 0; r < 4u; ++r) {
+                const uint32_t lr = ty * 4u + r;
+                if (lr >= nrows) break;
+                const uint32_t gy = row0 + (lr / band_h) * band_h * band_step + (lr % band_h);
+                if (gy >= h) break;
+                if (gy != (b / bins_x) * 4u + r) solid = false;
+                for (uint32_t c = 0; c < 4u && tx * 4u + c < w; ++c) {
+                    any = true;
+                    for (uint32_t i = 0; i < kSureWords; ++i) need[i] |= sure_pixel_bits(c, r, i);
+                }
+            }
+            solid = solid && any;
+            for (uint32_t i = 0; i < kSureWords; ++i)
+                solid = solid && (sure[(uint64_t)kSureWords * b + i] & need[i]) == need[i];
+            if (solid) atomicAdd(&s_solid, 1u);
+        }
+        const uint32_t k = band * kQClasses + ((len && !solid) ? lc : kQClasses - 1);
+        cls[t] = (uint16_t)(k | (solid ? 0x8000u : 0u));   // k_queue_fill flags the queue word
         atomicAdd(&hist[k], 1u);
     }
     __syncthreads();
     for (uint32_t k = threadIdx.x; k < kQBands * kQClasses; k += kThreads)
         if (hist[k]) atomicAdd(qw + kQCount + k, hist[k]);
+    if (threadIdx.x == 0 && s_solid) atomicAdd(qw + kQSolid, s_solid);
 }
 __global__ void __launch_bounds__(kThreads) k_queue_scan(uint32_t *__restrict__ qw, uint32_t heavy) {
     // one block: the counts to LDS in one parallel load, band totals and
@@ -1096,16 +1245,17 @@ __global__ void __launch_bounds__(kThreads) k_queue_fill(const uint16_t *__restr
     for (uint32_t k = threadIdx.x; k < kQBands * kQClasses; k += kThreads) hist[k] = 0;
     __syncthreads();
     const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
-    uint32_t k = 0, r = 0;
+    uint32_t k = 0, r = 0, solid = 0;
     if (t < ntiles) {
-        k = cls[t];
+        k = cls[t] & 0x7FFFu;
+        solid = cls[t] >> 15;   // in the background class: the queue word's bit 31 (kQueueSolid)
         r = atomicAdd(&hist[k], 1u);
     }
     __syncthreads();
     for (uint32_t j = threadIdx.x; j < kQBands * kQClasses; j += kThreads)
         if (hist[j]) base[j] = qw[kQStart + j] + atomicAdd(qw + kQCur + j, hist[j]);
     __syncthreads();
-    if (t < ntiles) queue[base[k] + r] = t;
+    if (t < ntiles) queue[base[k] + r] = t | (solid ? kQueueSolid : 0u);
 }
 
 }  // namespace
@@ -1193,9 +1343,9 @@ int launch_bin_footprints(const float *tris, uint32_t n, const uint4 *nodes, uin
     if (n > 0) {
         // gcount[0] = global list length, gcount[3] = alive triangles,
         // gcount[4..5] = the list total as a 64-bit sum (k_bin_count); cnt,
-        // cntq and cur (adjacent) zeroed
+        // cntq, cur and sure (adjacent) zeroed
         const dim3 g((n + kThreads - 1) / kThreads);
-        const uint32_t zero_words = (uint32_t)((reinterpret_cast<const char *>(b.cur + (size_t)kBuckets * nb) -
+        const uint32_t zero_words = (uint32_t)((reinterpret_cast<const char *>(b.sure + (size_t)kSureWords * nb) -
                                                 reinterpret_cast<const char *>(b.cnt)) / 4);
         hipLaunchKernelGGL(k_cam_tris, g, dim3(kThreads), 0, st, tris, n, origin[0], origin[1], origin[2], prim,
                            nodes, m, reinterpret_cast<uint4 *>(prim + 16ull * n),
@@ -1206,13 +1356,14 @@ int launch_bin_footprints(const float *tris, uint32_t n, const uint4 *nodes, uin
                            reinterpret_cast<const unsigned long long *>(b.bmask), b.boff, b.live);
         hipLaunchKernelGGL(k_bin_fp, g, dim3(kThreads), 0, st, prim, n, c, hdr, node_prim, tri_leaf, leaf_parent,
                            parent, b.path, b.brect, b.binrec, b.gcount,
-                           b.glist, b.live, b.gcount + 3);
-        hipLaunchKernelGGL(k_bin_count, g, dim3(kThreads), 0, st, b.brect, b.live, b.gcount + 3, b.bins_x,
+                           b.glist, b.live, b.gcount + 3, b.solid ? 1u : 0u);
+        const auto count = b.solid ? k_bin_count<true> : k_bin_count<false>;
+        hipLaunchKernelGGL(count, g, dim3(kThreads), 0, st, b.brect, b.live, b.gcount + 3, b.bins_x,
                            reinterpret_cast<const float4 *>(b.binrec), c.w, c.h, c.tw, c.th, b.cnt, b.cntq,
                            reinterpret_cast<unsigned long long *>(b.blkcnt),
                            reinterpret_cast<unsigned long long *>(b.gcount + 4), b.pres, b.pres_cap,
                            reinterpret_cast<unsigned long long *>(b.gcount + 6),
-                           b.pbase);
+                           b.pbase, b.solid ? b.sure : nullptr);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
@@ -1253,7 +1404,8 @@ size_t bin_queue_bytes(uint32_t ntiles) {
 
 int launch_bin_queue(const uint32_t *off, const uint32_t *gstat, uint32_t bins_x, uint32_t tiles_x, uint32_t ntiles,
                      uint32_t row0, uint32_t band_h, uint32_t band_step, uint32_t th, void *mem,
-                     uint32_t **queue, uint32_t **qhdr, void *stream, const uint32_t *cost, uint32_t **qheavy) {
+                     uint32_t **queue, uint32_t **qhdr, void *stream, const uint32_t *cost, uint32_t **qheavy,
+                     const uint32_t *sure, uint32_t w, uint32_t h, uint32_t nrows) {
     const hipStream_t st = (hipStream_t)stream;
     uint32_t *qw = reinterpret_cast<uint32_t *>(mem);
     uint32_t *q = qw + kQWords;
@@ -1272,7 +1424,7 @@ int launch_bin_queue(const uint32_t *off, const uint32_t *gstat, uint32_t bins_x
     if (ntiles > 0) {
         const dim3 g((ntiles + kThreads - 1) / kThreads);
         hipLaunchKernelGGL(k_queue_class, g, dim3(kThreads), 0, st, off, gstat, ntiles, tiles_x, tiles_y, row0,
-                           band_h, band_step, th, bins_x, lpt, cost, cls, qw);
+                           band_h, band_step, th, bins_x, lpt, cost, sure, w, h, nrows, cls, qw);
     }
     hipLaunchKernelGGL(k_queue_scan, dim3(1), dim3(kThreads), 0, st, qw, (cost && lpt) ? 1u : 0u);
     if (ntiles > 0)

@@ -82,4 +82,47 @@ __device__ __forceinline__ double det_lower_bound(const float *r, double dn_lb, 
     return (L < 1e30) ? L : 0.0;
 }
 
+// The mirror of det_lower_bound: an upper bound of the exact det over every
+// f32 primary ray whose exact line meets the triangle's plane inside the
+// inflated triangle (all corners at depth >= min_depth > 0):
+//   det = tnum D.n / depth(P) <= (tnum_c + 8e |e2|.Q) dn_ub / min depth,
+// dn_ub >= D.n of every f32 primary ray.  Returns +inf when it does not apply.
+__device__ __forceinline__ double det_upper_bound(const float *r, double dn_ub, double min_depth) {
+    const double as[3] = {fabs((double)r[6]), fabs((double)r[7]), fabs((double)r[8])};
+    const double ae1[3] = {fabs((double)r[0]), fabs((double)r[1]), fabs((double)r[2])};
+    const double Q[3] = {as[1] * ae1[2] + ae1[1] * as[2], as[2] * ae1[0] + ae1[2] * as[0],
+                         as[0] * ae1[1] + ae1[0] * as[1]};
+    const double et = 8.0 * 0x1p-24 * (fabs((double)r[3]) * Q[0] + fabs((double)r[4]) * Q[1] +
+                                       fabs((double)r[5]) * Q[2]);
+    if (!(min_depth > 0.0) || !(dn_ub > 0.0)) return INFINITY;
+    const double U = 1.01 * ((double)r[12] + et) * dn_ub / min_depth;   // 1 % for the f64 evaluation
+    return (U == U) ? U : INFINITY;
+}
+
+// Sure acceptance (the solid tiles of bih_bins.hip): the converse of
+// miss_bary.  Eu, Ed, Ev above bound the f32 evaluation's error on both
+// sides, so with L <= the exact det (det_lower_bound) and a, b, c formed by
+// miss_bary with den = L: a direction D whose exact line has barycentrics
+//   u* >= a,  v* >= b,  u* + v* <= 1 - c
+// is accepted by the f32 intersector, given L >= 2e-6 (miss_bary returned
+// true, so Ed < 0.49e-6):
+//   det_c >= det - Ed >= 2e-6 - 0.49e-6 > 1e-6;
+//   un_c >= un - Eu = u* det - Eu >= (Eu / L) det - Eu >= 0, so u_c =
+//     fl(un_c fl(1 / det_c)) >= 0; v_c >= 0 alike;
+//   u_c + v_c <= ((u* + v*) det + Eu + Ev) / (det - Ed) (1 + 2.01e) <= 1
+//     as u* + v* <= 1 - 2.1e - (Eu + Ev + Ed) / det, and fl keeps <= 1; with
+//     v_c >= 0 also u_c <= 1;
+//   t_c = fl(tnum_c fl(1 / det_c)) lies in (0, FLT_MAX) for 1e-30 < tnum_c <
+//     1e30 and 1e-6 < det_c < 1e6 + Ed.
+// In terms of the edge pre-test's normals (edge_pretest: D.G_j >= 0, G_j
+// inflated by a_j = a, b, c): the deflated G'_j = G_j - 2 a_j Nd has
+// D.G'_j = D.G_j - 2 a_j det.  A direction with D.G_j > 2 a_j U >= 0 for
+// all three j (U = det_upper_bound) has det > 0 (the G_j sum to
+// (1 + a + b + c) Nd), so its line meets the plane inside the inflated
+// triangle, L <= det <= U hold, and D.G'_j > 0: the three conditions above.
+// tests/test_solid_tiles.py checks the claim.
+__device__ __forceinline__ bool sure_applies(const float *r, double L, double U, float a, float b, float c) {
+    return (float)L >= 2e-6f && U < 1e6 && r[12] > 1e-30f && r[12] < 1e30f && a + b + c < 0.5f;
+}
+
 }  // namespace bih

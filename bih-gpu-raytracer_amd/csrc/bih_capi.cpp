@@ -1167,6 +1167,13 @@ static bool bins_enabled() {
     return on;
 }
 
+// Solid tiles (bih_bins.hip: sure_mask; k_render_bins writes them as
+// constants) are on unless BIH_SOLID_TILES=0 (A/B); they never change a pixel.
+static bool solid_tiles_enabled() {
+    static const bool on = !env_off("BIH_SOLID_TILES");
+    return on;
+}
+
 // Runs the camera's primary-ray records (launch_prim) when `need_prim` and
 // the bins take no part.
 static int prim_only(bih_tree *tr, CamSet &c, const bih_camera *cam, bool need_prim, hipStream_t st) {
@@ -1202,9 +1209,12 @@ static int build_bins(bih_tree *tr, CamSet &c, const Frame &f, const float dmax[
     const size_t nb = (size_t)b.bins_x * b.bins_y;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const uint32_t nblk = (n + 255) / 256;   // k_cam_tris blocks (bih::kThreads)
-    // cnt, cntq and cur follow each other with no gap (k_cam_tris zeroes them as one range)
+    // cnt, cntq, cur and sure follow each other with no gap (k_cam_tris zeroes them as one range)
     const size_t s_brect = al((size_t)n * 8), s_cnt = nb * 4, s_cntq = nb * 4 * (bih::kBinBuckets - 1),
-                 s_cur = al(nb * 4 * bih::kBinBuckets),
+                 s_cur = nb * 4 * bih::kBinBuckets,
+                 // (sure ends the zeroed range: padded so that the four together end on a 256-byte boundary)
+                 s_zeroed = al(s_cnt + s_cntq + s_cur + nb * 4 * bih::kSureWords),
+                 s_sure = s_zeroed - (s_cnt + s_cntq + s_cur),
                  s_off = al((nb + 1) * 4),
                  s_g = al(8 * 4), s_glist = al((size_t)n * 4 + 4),
                  s_part = al(bih::scan_partials_words((uint32_t)nb) * 4),
@@ -1221,7 +1231,7 @@ static int build_bins(bih_tree *tr, CamSet &c, const Frame &f, const float dmax[
     uint32_t pres_cap = (uint32_t)std::min<uint64_t>(4ull * n + (1u << 20), 0x3FFFFFFFull);
     pres_cap = std::min<uint32_t>(pres_cap, tr->prm.pair_cap);   // tests: blocks past a small buffer recompute
     const size_t s_pres = al((size_t)pres_cap * 4);
-    const size_t need = s_brect + s_cnt + s_cntq + s_cur + s_off + s_g + s_glist + s_part + s_rec + s_path + s_gent +
+    const size_t need = s_brect + s_cnt + s_cntq + s_cur + s_sure + s_off + s_g + s_glist + s_part + s_rec + s_path + s_gent +
                         s_live + s_bmask + s_bcnt + s_boff + s_bpart + s_blkcnt + s_pbase + s_pres + s_cost;
     if (c.bins_mem_cap < need) {
         hipError_t e = hipStreamSynchronize(st);   // renders that read the old bins
@@ -1235,6 +1245,14 @@ static int build_bins(bih_tree *tr, CamSet &c, const Frame &f, const float dmax[
     b.cnt = reinterpret_cast<uint32_t *>(p); p += s_cnt;
     b.cntq = reinterpret_cast<uint32_t *>(p); p += s_cntq;
     b.cur = reinterpret_cast<uint32_t *>(p); p += s_cur;
+    b.sure = reinterpret_cast<uint32_t *>(p); p += s_sure;
+    // (4 x 4-pixel tiles only: the pixel masks' shape)
+    b.solid = solid_tiles_enabled() && full.tw == 4 && full.th == 4;
+    if (reinterpret_cast<char *>(b.cntq) != reinterpret_cast<char *>(b.cnt) + s_cnt ||
+        reinterpret_cast<char *>(b.cur) != reinterpret_cast<char *>(b.cntq) + s_cntq ||
+        reinterpret_cast<char *>(b.sure) != reinterpret_cast<char *>(b.cur) + s_cur ||
+        reinterpret_cast<char *>(b.sure + (size_t)bih::kSureWords * nb) > p || ((uintptr_t)p & 255u) != 0)
+        return BIH_ERR_INVALID;   // (the zeroed range cnt .. sure is one piece and off stays aligned: never)
     b.off = reinterpret_cast<uint32_t *>(p); p += s_off;
     b.gcount = reinterpret_cast<uint32_t *>(p); p += s_g;
     b.glist = reinterpret_cast<uint32_t *>(p); p += s_glist;
@@ -1405,7 +1423,8 @@ static int prepare_bin_queue(bih_tree *tr, CamSet &c, int ci, const Frame &f, in
         }
         int le = bih::launch_bin_queue(c.bins.off, c.bins.gcount + 1, c.bins.bins_x, t.x, ntiles, rows.row0,
                                        rows.band_h, rows.band_step, t.th, c.q_mem, &c.q_list, &c.q_hdr,
-                                       st, measured ? c.bins.cost : nullptr);
+                                       st, measured ? c.bins.cost : nullptr, nullptr,
+                                       c.bins.solid ? c.bins.sure : nullptr, f.w, f.h, rows.nrows);
         if (le) return map_hip(le);
         memcpy(c.q_key, key, sizeof key);
         c.q_valid = true;
@@ -2684,7 +2703,7 @@ int bih_sync(const bih_tree *tr, void *stream) {
 #endif
 #if BIH_FAST_COUNTERS
     if (tr->work && tr->last_slot >= 0) {
-        uint32_t c[bih::kItemWord + 15];
+        uint32_t c[bih::kItemWord + 16];
         if (hipMemcpyAsync(c, tr->work + (size_t)tr->last_slot * bih::kWorkWords, sizeof c,
                            hipMemcpyDeviceToHost, st) == hipSuccess &&
             hipStreamSynchronize(st) == hipSuccess) {
@@ -2708,9 +2727,9 @@ int bih_sync(const bih_tree *tr, void *stream) {
             fprintf(stderr,
                     "bin-items nframes %u ns %u fpi %u hs %u fhv %u stamped %u measuring %u live %u heavy %u"
                     " | items %u split-items %u heavy-items %u zero-frame-items %u tile-frames %u"
-                    " bg-tile-frames %u\n",
+                    " bg-tile-frames %u solid %u\n",
                     ci[0], ci[1], ci[2], ci[3], ci[4], ci[5], ci[6], ci[7], ci[8], ci[9], ci[10], ci[11], ci[12],
-                    ci[13], ci[14]);
+                    ci[13], ci[14], ci[15]);
             const unsigned long long *ph = reinterpret_cast<const unsigned long long *>(c + 64);
             fprintf(stderr,
                     "bin-phases (wave cycles) queue %llu background %llu setup %llu walk %llu verify %llu"
@@ -2828,6 +2847,51 @@ int bih_bins_get_stats(const bih_tree *ctr, bih_bins_stats *out) {
     out->tiles_y = c.bins.bins_y;
     out->list_entries = c.bin_entries;
     out->global_entries = c.bin_gn;
+    return BIH_OK;
+}
+
+int bih_bins_solid_masks(const bih_tree *ctr, uint16_t *out, size_t n_bins, uint32_t *n_solid) {
+    if (!ctr || !out || !n_solid) return BIH_ERR_INVALID;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    CamSet &c = tr->cs[tr->cs_cur];   // the latest render's camera
+    resolve_bins(c, true);
+    *n_solid = 0;
+    memset(out, 0, n_bins * sizeof(uint16_t));
+    if (!(c.bins_usable && c.bins_valid)) return BIH_OK;
+    const size_t nb = (size_t)c.bins.bins_x * c.bins.bins_y;
+    if (n_bins != nb) return BIH_ERR_INVALID;
+    if (!c.bins.solid) return BIH_OK;
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return map_hip((int)e);
+    uint32_t gstat = 0;
+    e = hipMemcpy(&gstat, c.bins.gcount + 1, sizeof gstat, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return map_hip((int)e);
+    if (gstat != 0) return BIH_OK;   // a global list or unusable bins: nothing is classified
+    std::vector<uint32_t> words(nb * bih::kSureWords);
+    e = hipMemcpy(words.data(), c.bins.sure, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return map_hip((int)e);
+    const uint32_t w = c.bins_key[0], h = c.bins_key[1];
+    for (size_t b = 0; b < nb; ++b) {
+        // a pixel is sure when all its sub-rectangles are
+        uint32_t px = 0;
+        for (uint32_t r = 0; r < 4; ++r)
+            for (uint32_t k = 0; k < 4; ++k) {
+                bool all = true;
+                for (uint32_t i = 0; i < bih::kSureWords; ++i) {
+                    const uint32_t m = bih::sure_pixel_bits(k, r, i);
+                    all = all && (words[b * bih::kSureWords + i] & m) == m;
+                }
+                if (all) px |= 1u << (4 * r + k);
+            }
+        out[b] = (uint16_t)px;
+        const uint32_t x0 = (uint32_t)(b % c.bins.bins_x) * 4, y0 = (uint32_t)(b / c.bins.bins_x) * 4;
+        uint32_t need = 0;
+        for (uint32_t r = 0; r < 4 && y0 + r < h; ++r)
+            for (uint32_t k = 0; k < 4 && x0 + k < w; ++k) need |= 1u << (4 * r + k);
+        if (need && (px & need) == need) ++*n_solid;
+    }
     return BIH_OK;
 }
 

@@ -42,9 +42,9 @@ constexpr int kLdsStack = BIH_LDS_STACK;
 // tile slots, so its diagnostic builds use the first slot line's words:
 // [64..76) six u64 phase cycle sums (BIH_PHASES, "bin-phases"), [76..84) the
 // root-path check's site counters (path_site_count, "bin-pathcheck");
-// [84..96) are free; and the second slot line's: [96..111) the item counters
+// [84..96) are free; and the second slot line's: [96..112) the item counters
 // (kItemWord, "bin-items": nine words of the launch's split, six counted per
-// item)
+// item, the queue's solid tiles)
 constexpr uint32_t kSlotStrideWords = 32;
 constexpr uint32_t kItemWord = 96;
 constexpr uint32_t kWorkWords = 64 + kSlotStrideWords * 1024 + 64;   // + histograms (counter builds)
@@ -53,6 +53,32 @@ constexpr uint32_t kBinGlobalMax = 4096;          // longer global lists: no bin
 constexpr uint32_t kBinEntryF4 = 3;               // list entry: 3 x float4 = 48 bytes (bih_bins.hip)
 constexpr uint32_t kBinsUnusable = 0xFFFFFFFFu;   // bins status: lists not built (k_bin_status)
 constexpr uint32_t kBinSetWords = (16 + 1024) * 32;   // k_render_bins queue state per set
+// A solid tile (every sample of every pixel provably hits, whatever its
+// jitter: bih_bins.hip, sure_mask) sits in the queue's background section
+// with bit 31 of its queue word set; the queue's count of them is word
+// kBinQSolidWord of RenderArgs::bin_qhdr (after the 8 band headers and the 8
+// heavy counts).
+constexpr uint32_t kQueueSolid = 0x80000000u;
+constexpr uint32_t kBinQSolidWord = 40;
+// kPlanSure: bit of word 11 (plan meta) of a triangle's bins record that
+// carries the sure thresholds in words 12..14 (k_bin_fp); never in a list entry.
+constexpr uint32_t kPlanSure = 1u << 14;
+// The bins' sure words (BinBuffers::sure): each pixel of a 4 x 4-pixel tile is
+// cut into kSureQ x kSureQ sub-rectangles, one bit each (bit row * 4 kSureQ +
+// col over the tile's 4 kSureQ x 4 kSureQ grid), kSureWords u32 per tile.
+constexpr uint32_t kSureQ = 2;
+constexpr uint32_t kSureWords = (4 * kSureQ) * (4 * kSureQ) / 32;
+static_assert(kSureWords * 32 == (4 * kSureQ) * (4 * kSureQ), "sure words");
+// the sub-rectangle bits of pixel (col, row) of a tile in word i of its sure words
+constexpr uint32_t sure_pixel_bits(uint32_t col, uint32_t row, uint32_t i) {
+    uint32_t m = 0u;
+    for (uint32_t sy = row * kSureQ; sy < (row + 1u) * kSureQ; ++sy)
+        for (uint32_t sx = col * kSureQ; sx < (col + 1u) * kSureQ; ++sx) {
+            const uint32_t bit = sy * (4u * kSureQ) + sx;
+            if ((bit >> 5) == i) m |= 1u << (bit & 31u);
+        }
+    return m;
+}
 #ifndef BIH_BUCKETS
 #define BIH_BUCKETS 6
 #endif
@@ -261,6 +287,10 @@ struct BinBuffers {
     uint32_t *cnt = nullptr;      // [nb] entries per tile (k_bin_count); cntq and cur follow (zeroed together)
     uint32_t *cntq = nullptr;     // [nb][kBinBuckets - 1] entries per tile in the buckets but the last
     uint32_t *cur = nullptr;      // [nb][kBinBuckets] the fill's cursors per tile and bucket
+    uint32_t *sure = nullptr;     // [nb][kSureWords] sure bits per 4 x 4-pixel tile (k_bin_count; follows cur,
+                                  // zeroed with it): a set bit = every sample of that sub-rectangle of a pixel
+                                  // hits, whatever its jitter
+    bool solid = false;           // the sure masks are computed and the queue classifies solid tiles
     uint32_t *blkcnt = nullptr;   // [blocks][kBinBlockTiles] u64: k_bin_count's per-block (tile, bucket) counts
     uint32_t *off = nullptr;      // [nb + 1] list offsets, off[nb] = list length
     uint32_t *gcount = nullptr;   // [8] global list length, status (k_bin_status), list total, alive count,
@@ -505,11 +535,15 @@ int launch_bin_fill(uint32_t n, const BinCamera &c, const BinBuffers &b, float *
 // measured cost (finer classes than the list length) and each band's tiles
 // costing over kHeavyFactor x the launch's mean come first and are counted in
 // *qheavy (k_render_bins splits them over frame ranges: RenderArgs::hsplit).
+// sure (optional; with the image's w, h and the launch's nrows): the bins'
+// sure words (BinBuffers::sure); the solid tiles leave the live classes for
+// the background section, flagged kQueueSolid.
 size_t bin_queue_bytes(uint32_t ntiles);
 int launch_bin_queue(const uint32_t *off, const uint32_t *gstat, uint32_t bins_x, uint32_t tiles_x, uint32_t ntiles,
                      uint32_t row0, uint32_t band_h, uint32_t band_step, uint32_t th, void *mem,
                      uint32_t **queue, uint32_t **qhdr, void *stream, const uint32_t *cost = nullptr,
-                     uint32_t **qheavy = nullptr);
+                     uint32_t **qheavy = nullptr, const uint32_t *sure = nullptr, uint32_t w = 0, uint32_t h = 0,
+                     uint32_t nrows = 0);
 // exclusive scan of n u32 (bih_build.hip); *total_dev = the sum
 int scan_exclusive(const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *partials,
                    uint32_t *total_dev, void *stream);

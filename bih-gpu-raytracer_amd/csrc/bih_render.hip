@@ -2043,7 +2043,7 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
     const uint32_t tiles_x = (a.w + TW - 1) / TW;
     const float fw = (float)a.w, fh = (float)a.h;
     const uint32_t pix = lane >> LOG2SPP;
-    const uint32_t bgpix = pixel_from_hits(0u, SPP);
+    const uint32_t misspix = pixel_from_hits(0u, SPP), solidpix = pixel_from_hits(SPP, SPP);
     // the bins' status word (k_bin_status wrote it before this launch, nothing
     // writes it during one): read once per wave, as a scalar.  bins_ok: the
     // lists were built; else the exact walk decides
@@ -2098,6 +2098,7 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
         }
         const uint32_t v[9] = {a.nframes, q.ns, fpi, q.hs, fhv, STAMP ? 1u : 0u, COST ? 1u : 0u, live, heavy};
         for (uint32_t k = 0; k < 9u; ++k) a.work[kItemWord + k] = v[k];
+        a.work[kItemWord + 15] = a.bin_qhdr[kBinQSolidWord];   // the queue's solid tiles
     }
 #endif
 #if BIH_PHASES
@@ -2164,13 +2165,27 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
         }
 #endif
         if (it >= hb.y) {
-            // background: every sample misses (Color's background), whatever its jitter
+            // background: every sample misses (Color's background), whatever its jitter;
+            // a solid tile (kQueueSolid: launch_bin_queue): every sample of every
+            // pixel hits, whatever its jitter -- the constant of SPP hits, and the
+            // hit mask the live path would write (its valid lanes)
             const uint32_t k = (it - hb.y) * 64u + lane;
             if (k < hb.z && !(a.dbg & 1u)) {
-                const uint32_t t = a.bin_queue[hb.x + hb.y + k];
-                if (MASK) a.hit_mask[t] = 0ull;      // (one-frame launches)
+                const uint32_t tq = a.bin_queue[hb.x + hb.y + k];
+                const uint32_t t = tq & ~kQueueSolid;
+                const bool solid = (tq & kQueueSolid) != 0u;
                 const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
                 const uint32_t x0 = tx * TW;
+                if (MASK) {                          // (one-frame launches)
+                    unsigned long long hm = 0ull;
+                    if (solid) {
+                        const unsigned long long m = (SPP == 64) ? ~0ull : ((1ull << SPP) - 1ull);
+                        for (uint32_t p = 0; p < 64u / SPP; ++p)
+                            if (x0 + p % TW < a.w && ty * TH + p / TW < a.nrows) hm |= m << (p * SPP);
+                    }
+                    a.hit_mask[t] = hm;
+                }
+                const uint32_t bgpix = solid ? solidpix : misspix;
                 for (uint32_t fj = f0; fj < nf; ++fj) {
                     uint32_t *const fout = a.out + (uint64_t)fj * a.out_stride;
                     for (uint32_t r = 0; r < TH; ++r) {

@@ -759,6 +759,15 @@ typedef struct bih_bins_stats {
     uint32_t global_entries;
 } bih_bins_stats;
 int bih_bins_get_stats(const bih_tree *tree, bih_bins_stats *out);
+/* Diagnostic (tests): the sure words of the current camera's bins, one per
+ * tile in row-major order (n_bins = tiles_x * tiles_y of bih_bins_get_stats,
+ * else BIH_ERR_INVALID).  Bit 4 * row + col of a 4 x 4-pixel tile is set when
+ * every sample of that pixel is proven to hit whatever its jitter; a tile
+ * whose word covers all its pixels inside the image is solid (*n_solid counts
+ * them) and any-hit renders write it as a constant.  All zero when nothing is
+ * classified: a sample count other than 4, a non-empty global list, unusable
+ * bins, BIH_SOLID_TILES=0.  Waits for the device. */
+int bih_bins_solid_masks(const bih_tree *tree, uint16_t *out, size_t n_bins, uint32_t *n_solid);
 
 #ifdef __cplusplus
 }
