@@ -22,6 +22,7 @@ from . import scenes  # noqa: F401
 from ._lib import (PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_STATIC_SOUP,
                    PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS, PARAM_GBUFFER_MASK,
                    AREA_LIGHT_DTYPE, MAX_AREA_LIGHTS, AreaLight, LightSet, BOUNCE_SLOT, Bounce, Indirect,
+                   MAX_BOUNCES, Path,
                    NO_HIT, LIGHT_DTYPE, POINT_LIGHT_DTYPE, MAX_LIGHTS, SHADOW_T_LO, QUERY_CLOSEST, QUERY_OCCLUDED,
                    QUERY_T_HI, QUERY_CLOSEST_WITHIN, QUERY_OCCLUDED_WITHIN, PointLight, Direct, GBuffer, Hit, Light, Ray, TRAVERSE_ANYHIT,
                    TRAVERSE_REFERENCE, BihError, Camera, Framebuffer, Rows, Scene, TreeInfo, check, load)
@@ -70,6 +71,13 @@ DIRECT_PLANES = {"lit": (np.uint64, 0), "irradiance": (np.float32, 1), "rgba": (
 INDIRECT_PLANES = {"lit": (np.uint64, 0), "bounce": (HIT_DTYPE, 0), "lit2": (np.uint64, 0),
                    "irradiance": (np.float32, 1), "rgba": (np.uint32, 1)}
 INDIRECT = tuple(INDIRECT_PLANES)
+
+
+# the planes of a path render (bih_path), as INDIRECT_PLANES; values per pixel
+# -1: one per sample and level ("bounces" and "lits", level-major)
+PATH_PLANES = {"lit": (np.uint64, 0), "bounces": (HIT_DTYPE, -1), "lits": (np.uint64, -1),
+               "irradiance": (np.float32, 1), "rgba": (np.uint32, 1)}
+PATH = tuple(PATH_PLANES)
 
 
 def _rows_ref(rows: Rows | None):
@@ -136,6 +144,16 @@ def bounce_sample(seed: int, pixel: int, frame: int, spp: int, s: int, n) -> np.
     nn = (C.c_float * 3)(*[float(x) for x in np.asarray(n, np.float32).reshape(3)])
     d = (C.c_float * 3)()
     check(load().bih_bounce_sample(seed, pixel, frame, spp, s, nn, d), "bih_bounce_sample")
+    return np.array(d[:], np.float32)
+
+
+def path_sample(seed: int, pixel: int, frame: int, spp: int, s: int, level: int, n) -> np.ndarray:
+    """bih_path_sample (host only): the direction B_k (3,) float32 of level
+    `level` = k (1 .. MAX_BOUNCES) of a path, as bounce_sample; level 1 is
+    bounce_sample's."""
+    nn = (C.c_float * 3)(*[float(x) for x in np.asarray(n, np.float32).reshape(3)])
+    d = (C.c_float * 3)()
+    check(load().bih_path_sample(seed, pixel, frame, spp, s, level, nn, d), "bih_path_sample")
     return np.array(d[:], np.float32)
 
 
@@ -542,6 +560,48 @@ class Renderer:
               "bih_render_indirect_device")
         del keep
 
+    def render_path(self, dir_lights, point_lights, area_lights, bounce, n_bounces: int, frame: int | None = None,
+                    rows: Rows | None = None, planes=PATH) -> dict:
+        """render_indirect carried on for n_bounces (1 .. MAX_BOUNCES) levels
+        (bih_render_path; synchronous): a sample's path goes on from each bounce
+        hit until a ray escapes or level n_bounces is reached.  Returns a dict
+        of the planes asked for (PATH_PLANES): "lit" (nrows*w*spp,) uint64 of
+        the primary hit, "bounces" (n_bounces, nrows*w*spp) HIT_DTYPE and "lits"
+        (n_bounces, nrows*w*spp) uint64, row k-1 level k's bounce records and
+        lit words, "irradiance" (nrows, w) float32, "rgba" (nrows, w) uint32.
+        With n_bounces = 1 they are render_indirect's planes."""
+        f = self.frame if frame is None else frame
+        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
+        nrows = rows.nrows if rows is not None else self.h
+        S = nrows * self.w * self.spp
+        out, pp = {}, Path()
+        for name in planes:
+            dt, k = PATH_PLANES[name]
+            out[name] = np.zeros((nrows, self.w) if k > 0 else ((n_bounces, S) if k < 0 else S), dt)
+            setattr(pp, name, out[name].ctypes.data)
+        bn = self._bounce(bounce)
+        check(load().bih_render_path(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
+                                     self.seed, _rows_ref(rows), C.byref(ls), C.byref(bn), n_bounces, C.byref(pp)),
+              "bih_render_path")
+        del keep
+        self.frame = f + 1
+        return out
+
+    def render_path_device(self, ptrs: dict, dir_lights, point_lights, area_lights, bounce, n_bounces: int,
+                           frame: int, rows: Rows | None = None, stream: int | None = None):
+        """Asynchronous render_path into device memory (bih_render_path_device):
+        ptrs maps plane names (PATH_PLANES) to device pointers; planes left out
+        are not written.  The light arrays and bounce are host memory, copied by
+        the call."""
+        pp = _device_planes(Path(), PATH_PLANES, ptrs)
+        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
+        bn = self._bounce(bounce)
+        check(load().bih_render_path_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
+                                            frame, self.seed, _rows_ref(rows), C.byref(ls), C.byref(bn), n_bounces,
+                                            C.byref(pp), C.c_void_p(stream or 0)),
+              "bih_render_path_device")
+        del keep
+
     def whitted_work(self) -> dict:
         """Per bounce d = 0..8 of the last Whitted render (run with
         PARAM_WHITTED_COUNTERS on): rays traced, BIH nodes entered, triangles
@@ -642,4 +702,4 @@ __all__ = ["GPUArrayManager", "Renderer", "Model", "load_obj", "host_register", 
            "QUERY_T_HI", "QUERY_CLOSEST_WITHIN", "QUERY_OCCLUDED_WITHIN", "PointLight", "POINT_LIGHT_DTYPE",
            "pack_point_lights", "AreaLight", "LightSet", "AREA_LIGHT_DTYPE", "MAX_AREA_LIGHTS",
            "pack_area_lights", "area_light_sample", "Bounce", "Indirect", "INDIRECT", "INDIRECT_PLANES",
-           "BOUNCE_SLOT", "bounce_sample"]
+           "BOUNCE_SLOT", "bounce_sample", "Path", "PATH", "PATH_PLANES", "MAX_BOUNCES", "path_sample"]

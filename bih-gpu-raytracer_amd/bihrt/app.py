@@ -19,6 +19,7 @@ usage:  python -m bihrt --mesh sponza --resources path/to/resources --frames 10 
                      [--lamp X,Y,Z[,W]]...            (point lights next to them; --sky 0: lamps only)
                      [--panel CX,CY,CZ,UX,UY,UZ,VX,VY,VZ[,W]]...   (area lights: soft shadows)
                      [--bounce ALBEDO[,SKY]]          (one bounce of indirect light and a sky term; alone: sky only)
+                     [--bounces N]                    (with --bounce: paths of N = 1..8 bounces)
         python -m bihrt --obj file.obj ...     (explicit path)
         python -m bihrt --scene cornell|torus|soup[:N] ...   (built-in scenes)
 """
@@ -31,7 +32,7 @@ import time
 
 import numpy as np
 
-from . import (RAYS_PER_PIXEL, SCREEN_HEIGHT, SCREEN_WIDTH, SEED, GPUArrayManager, Renderer,
+from . import (MAX_BOUNCES, RAYS_PER_PIXEL, SCREEN_HEIGHT, SCREEN_WIDTH, SEED, GPUArrayManager, Renderer,
                load_obj, scenes, write_ppm)
 
 
@@ -76,7 +77,7 @@ class App:
 
     def run(self, frames: int, out_pattern: str | None = None, rebuild: bool = True,
             every: int = 1, gbuffer_pattern: str | None = None, direct_pattern: str | None = None,
-            lights=None, lamps=None, panels=None, bounce=None):
+            lights=None, lamps=None, panels=None, bounce=None, bounces=None):
         """App::Run for a fixed number of frames: Renderer::Render each frame
         (BIH rebuild + render), optional PPM output; returns the frames.
         gbuffer_pattern: one .npz of the frame's G-buffer planes
@@ -87,7 +88,8 @@ class App:
         panels: area lights, (k, 10) rows {corner, edge_u, edge_v, weight}, next
         to both (Renderer.render_area_lights).  bounce: (albedo, sky) adds one
         bounce of indirect light and the sky term (Renderer.render_indirect);
-        lights = None is then no directional light."""
+        lights = None is then no directional light.  bounces: with bounce,
+        paths of that many bounces (Renderer.render_path)."""
         assert self.renderer is not None, "load_models first"
         if direct_pattern and lights is None and bounce is None:
             lights = scenes.sky_dome(8)
@@ -118,7 +120,10 @@ class App:
                 d = os.path.dirname(path)
                 if d:
                     os.makedirs(d, exist_ok=True)
-                if bounce is not None:
+                if bounce is not None and bounces is not None:
+                    shade = self.renderer.render_path(lights, lamps, panels, bounce, bounces, f,
+                                                      planes=("rgba",))["rgba"]
+                elif bounce is not None:
                     shade = self.renderer.render_indirect(lights, lamps, panels, bounce, f, planes=("rgba",))["rgba"]
                 elif panels is not None and len(panels):
                     shade = self.renderer.render_area_lights(lights, lamps, panels, f, planes=("rgba",))["rgba"]
@@ -159,6 +164,9 @@ def main(argv=None) -> int:
                     help="--direct: add one bounce of indirect light of reflectance ALBEDO and a sky of irradiance "
                          "SKY (default 1) for bounce rays that escape; --sky then defaults to 0, and without any "
                          "light the image is the sky term alone (ambient occlusion)")
+    ap.add_argument("--bounces", type=int, default=None, metavar="N",
+                    help="--direct --bounce: follow each path for N = 1..8 bounces (without it: the one-bounce "
+                         "render)")
     ap.add_argument("--every", type=int, default=1, help="write every k-th frame")
     ap.add_argument("--no-rebuild", action="store_true",
                     help="build once (the reference rebuilds every frame)")
@@ -185,6 +193,10 @@ def main(argv=None) -> int:
         ap.error("--lamp belongs to --direct")
     if not a.direct and a.bounce is not None:
         ap.error("--bounce belongs to --direct")
+    if a.bounces is not None and a.bounce is None:
+        ap.error("--bounces belongs to --bounce")
+    if a.bounces is not None and not 1 <= a.bounces <= MAX_BOUNCES:
+        ap.error("--bounces takes 1..%d" % MAX_BOUNCES)
     bounce = None
     if a.direct:
         if a.bounce is not None:
@@ -238,5 +250,6 @@ def main(argv=None) -> int:
     app = App(a.width, a.height, a.spp, device=a.device)
     app.load_models(scene)
     app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every, gbuffer_pattern=a.gbuffer,
-            direct_pattern=a.direct, lights=lights, lamps=lamps, panels=panels, bounce=bounce)
+            direct_pattern=a.direct, lights=lights, lamps=lamps, panels=panels, bounce=bounce,
+            bounces=a.bounces)
     return 0

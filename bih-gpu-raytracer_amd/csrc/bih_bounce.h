@@ -4,6 +4,8 @@
 // bih_bounce_sample on the host, as bih_area.h is for the panels.  The
 // direction comes from the area lights' counter-based hash with the slot
 // kBounceSlot, which no light index takes: no XORWOW draw of any frame moves.
+// Level k of a path (bih_render_path*, section 4.5.7; k_path_bounce,
+// bih_path_sample) takes the slot kBounceSlot + (k - 1), wrapping.
 // B = n + w, w a point of the unit sphere: cosine-distributed about a unit n.
 // No library trigonometry (host and device sinf differ): the circle's point is
 // a quadrant and a degree-9 Taylor sine of (pi/2)x, every f32 operation
@@ -27,11 +29,11 @@ BIH_AREA_FN float bounce_sin(float x) {
 }
 
 // B of sample `fs` = frame*spp + s (wrapping) of global pixel gp = y*w + x for
-// the normal n; hseed = area_seed_hash(seed).
-BIH_AREA_FN void bounce_dir(uint32_t hseed, uint32_t gp, uint32_t fs, const float *n, float *d) {
+// the normal n; hseed = area_seed_hash(seed); slot: the hash's last mix.
+BIH_AREA_FN void bounce_dir(uint32_t hseed, uint32_t gp, uint32_t fs, uint32_t slot, const float *n, float *d) {
     uint32_t h = area_mix(hseed ^ gp);
     h = area_mix(h ^ fs);
-    h = area_mix(h ^ kBounceSlot);
+    h = area_mix(h ^ slot);
     const uint32_t ha = area_mix(h + 0x9E3779B9u);
     const uint32_t hb = area_mix(h + 0x3C6EF372u);
     const float a = (float)(ha >> 8) * 0x1p-24f;   // 24 bits: exact, in [0, 1)

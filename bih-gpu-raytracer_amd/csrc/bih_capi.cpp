@@ -47,6 +47,7 @@ constexpr size_t kEntryBytes = 16 * bih::kBinEntryF4;   // frustum-bin list entr
 using bih::kTraceCursorBytes;                           // the work area's cursor block (bih::WorkArea)
 constexpr size_t kDirectSampleBytes = 16 + 8 + 4;       // dr_mem per sample: record, facing mask, list entry
 constexpr size_t kIndirectSampleBytes = 16 + 4;         // in_mem per sample: bounce record, hit-list entry
+constexpr size_t kPathSampleBytes = 4 + 4 + 1;          // pt_mem per sample: sum, second live-list entry, primary-hit flag
 
 // Per-camera structures (bih_render.hip / bih_bins.hip): primary-ray records,
 // frustum bins and the tile queue of one camera.  A tree keeps kCamSets of
@@ -334,6 +335,14 @@ struct bih_tree {
     size_t in_lit2_cap = 0;          // samples
     char *in_stage = nullptr;
     size_t in_stage_cap = 0;         // bytes
+    // Path renders (bih_render_path*) are an indirect-lighting render with more
+    // levels: next to dr_mem, in_mem and (for calls without `lits`) in_lit2 per
+    // sample its sum, the second live list's entry and the primary-hit flag;
+    // the host entry's device planes.  Same users, same waits.
+    char *pt_mem = nullptr;
+    size_t pt_cap = 0;               // samples (kPathSampleBytes each)
+    char *pt_stage = nullptr;
+    size_t pt_stage_cap = 0;         // bytes
 };
 
 namespace {
@@ -828,6 +837,8 @@ void bih_free(bih_tree *tr) {
     if (tr->in_mem) (void)hipFree(tr->in_mem);
     if (tr->in_lit2) (void)hipFree(tr->in_lit2);
     if (tr->in_stage) (void)hipFree(tr->in_stage);
+    if (tr->pt_mem) (void)hipFree(tr->pt_mem);
+    if (tr->pt_stage) (void)hipFree(tr->pt_stage);
     if (tr->ev_trace) (void)hipEventDestroy(tr->ev_trace);
     for (int k = 0; k < kSlots; ++k) {
         if (tr->ev0[k]) (void)hipEventDestroy(tr->ev0[k]);
@@ -890,7 +901,8 @@ int bih_tree_get_info(const bih_tree *tr, bih_tree_info *info) {
                          (tr->tq_cursor ? kTraceCursorBytes : 0) + tr->tq_spill_words * 4 + tr->tq_stage_cap +
                          tr->gb_mask_cap * 8 + tr->gb_scratch_cap * 4 + tr->gb_stage_cap +
                          tr->dr_cap * kDirectSampleBytes + tr->dr_lit_cap * 8 + tr->dr_stage_cap +
-                         tr->in_cap * kIndirectSampleBytes + tr->in_lit2_cap * 8 + tr->in_stage_cap;
+                         tr->in_cap * kIndirectSampleBytes + tr->in_lit2_cap * 8 + tr->in_stage_cap +
+                         tr->pt_cap * kPathSampleBytes + tr->pt_stage_cap;
     info->build_ms = tr->build_ms;
     info->device_allocs = tr->allocs + tr->t.allocs + tr->back[0].allocs + tr->back[1].allocs;
     return BIH_OK;
@@ -2290,6 +2302,9 @@ struct DirectJob {
     bool indirect = false;
     bih_bounce bounce;
     bih_indirect ind;
+    // bih_render_path*: n_bounces > 0 (with indirect set; ind.bounce and ind.lit2 then hold
+    // the level planes `bounces` and `lits`)
+    uint32_t n_bounces = 0;
 };
 
 // bih_render_gbuffer_device under the tree's lock, arguments checked, nrows > 0.
@@ -2330,17 +2345,27 @@ static int gbuffer_locked(bih_tree *tr, const Frame &f, const bih_gbuffer &pl, v
     rc = bih::launch_gbuffer(tr->t, a, p, mask, wa, st, dj != nullptr);
     if (rc == 0 && dj) {
         // dr_mem: records, facing masks, list (each at a multiple of 8 bytes);
-        // in_mem: bounce records, hit list
+        // in_mem: bounce records, hit list; pt_mem: sums, second live list, primary-hit flags
         const size_t S = tr->dr_cap;
         char *rec = tr->dr_mem, *face = rec + 16 * S, *list = face + 8 * S;
         char *rec2 = tr->in_mem, *blist = rec2 + 16 * tr->in_cap;
+        char *acc = tr->pt_mem, *blist2 = acc + 4 * tr->pt_cap, *hit0 = blist2 + 4 * tr->pt_cap;
         const bih::Scratch sc = {rec, reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
-                                 rec2, reinterpret_cast<uint32_t *>(blist)};
+                                 rec2, reinterpret_cast<uint32_t *>(blist), reinterpret_cast<uint32_t *>(blist2),
+                                 reinterpret_cast<float *>(acc), reinterpret_cast<uint8_t *>(hit0)};
         bih::IndirectPlanes ip;
         ip.lit = dj->planes.lit ? reinterpret_cast<unsigned long long *>(dj->planes.lit) : tr->dr_lit;
         ip.irradiance = dj->planes.irradiance;
         ip.rgba = dj->planes.rgba;
-        if (dj->indirect) {
+        if (dj->n_bounces) {
+            bih::PathPlanes pp;
+            static_cast<bih::DirectPlanes &>(pp) = ip;
+            pp.bounces = dj->ind.bounce;
+            pp.lits = reinterpret_cast<unsigned long long *>(dj->ind.lit2);
+            pp.lit_scratch = tr->in_lit2;
+            rc = bih::launch_path(tr->t, a, pp, dj->lights, dj->bounce.albedo, dj->bounce.sky, dj->n_bounces, sc, wa,
+                                  st);
+        } else if (dj->indirect) {
             ip.bounce = dj->ind.bounce;
             ip.lit2 = dj->ind.lit2 ? reinterpret_cast<unsigned long long *>(dj->ind.lit2) : tr->in_lit2;
             rc = bih::launch_indirect(tr->t, a, ip, dj->lights, dj->bounce.albedo, dj->bounce.sky, sc, wa, st);
@@ -2462,7 +2487,8 @@ static int direct_locked(bih_tree *tr, const Frame &f, const DirectJob &dj, void
     const bool own_lit = !dj.planes.lit && tr->dr_lit_cap < S;
     const bool own_lit2 = dj.indirect && !dj.ind.lit2 && tr->in_lit2_cap < S;
     const bool own_in = dj.indirect && tr->in_cap < S;
-    if ((tr->dr_cap < S || own_lit || own_lit2 || own_in) && tr->trace_used) {
+    const bool own_pt = dj.n_bounces && tr->pt_cap < S;
+    if ((tr->dr_cap < S || own_lit || own_lit2 || own_in || own_pt) && tr->trace_used) {
         // (the users of both buffers are direct-lighting launches: each ends before its ev_trace record)
         const hipError_t e = hipEventSynchronize(tr->ev_trace);
         if (e != hipSuccess) return map_hip((int)e);
@@ -2471,6 +2497,7 @@ static int direct_locked(bih_tree *tr, const Frame &f, const DirectJob &dj, void
     if (rc == BIH_OK) rc = grow(tr, &tr->dr_mem, &tr->dr_cap, S, S * kDirectSampleBytes);
     if (rc == BIH_OK && own_lit2) rc = grow(tr, &tr->in_lit2, &tr->in_lit2_cap, S, S * 8);
     if (rc == BIH_OK && own_in) rc = grow(tr, &tr->in_mem, &tr->in_cap, S, S * kIndirectSampleBytes);
+    if (rc == BIH_OK && own_pt) rc = grow(tr, &tr->pt_mem, &tr->pt_cap, S, S * kPathSampleBytes);
     if (rc) return rc;
     bih_gbuffer g = {};
     g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
@@ -2595,7 +2622,70 @@ int bih_bounce_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t sp
                       float d[3]) {
     static_assert(BIH_BOUNCE_SLOT == bih::kBounceSlot, "BIH_BOUNCE_SLOT / kBounceSlot");
     if (!n || !d || spp == 0 || s >= spp) return BIH_ERR_INVALID;
-    bih::bounce_dir(bih::area_seed_hash(seed), pixel, frame * spp + s, n, d);
+    bih::bounce_dir(bih::area_seed_hash(seed), pixel, frame * spp + s, bih::kBounceSlot, n, d);
+    return BIH_OK;
+}
+
+// The body of the two path entries, as render_indirect.
+static int render_path(const bih_tree *ctr, Frame f, const bih_rows *rows_in, const bih_light_set *ls_in,
+                       const bih_bounce *bounce, uint32_t n_bounces, const bih_path *planes, void *stream, bool host) {
+    static_assert(BIH_MAX_BOUNCES == bih::kMaxBounces, "BIH_MAX_BOUNCES / kMaxBounces");
+    static const bih_light_set no_lights = {nullptr, 0, nullptr, 0, nullptr, 0};
+    const bih_light_set *ls = ls_in ? ls_in : &no_lights;
+    bih_direct three = {};
+    bih_indirect five = {};   // (the level planes in the places of bih_indirect's bounce and lit2)
+    if (planes) {
+        three = bih_direct{planes->lit, planes->irradiance, planes->rgba};
+        five = bih_indirect{planes->lit, planes->bounces, planes->lits, planes->irradiance, planes->rgba};
+    }
+    int rc = light_set_check(ctr, &f, rows_in, ls, planes ? &three : nullptr, planes ? &five : nullptr);
+    if (rc) return rc;
+    if (!bounce) return BIH_ERR_INVALID;
+    if (n_bounces == 0 || n_bounces > BIH_MAX_BOUNCES) return BIH_ERR_INVALID;
+    if (((uintptr_t)planes->lits & 7u) || ((uintptr_t)planes->bounces & 15u)) return BIH_ERR_INVALID;
+    if (f.rows.nrows == 0) return BIH_OK;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    DirectJob dj;
+    merge_light_set(ls, f, &dj.lights);
+    dj.planes = three;
+    dj.indirect = true;
+    dj.bounce = *bounce;
+    dj.ind = five;
+    dj.n_bounces = n_bounces;
+    if (!host) return direct_locked(tr, f, dj, stream);
+    const size_t P = f.pixels(), S = (size_t)f.samples(), B = n_bounces;
+    Stage<5> sg{{planes->lit, planes->bounces, planes->lits, planes->irradiance, planes->rgba},
+                {S * 8, B * S * sizeof(bih_hit), B * S * 8, P * 4, P * 4}};
+    rc = sg.place(tr, &tr->pt_stage, &tr->pt_stage_cap);
+    if (rc) return rc;
+    dj.planes.lit = static_cast<uint64_t *>(sg.dev(0));
+    dj.ind.bounce = static_cast<bih_hit *>(sg.dev(1));
+    dj.ind.lit2 = static_cast<uint64_t *>(sg.dev(2));
+    dj.planes.irradiance = static_cast<float *>(sg.dev(3));
+    dj.planes.rgba = static_cast<uint32_t *>(sg.dev(4));
+    return sg.finish(tr, direct_locked(tr, f, dj, nullptr));
+}
+
+int bih_render_path_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                           uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
+                           const bih_bounce *bounce, uint32_t n_bounces, const bih_path *d_planes, void *stream) {
+    return render_path(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, bounce, n_bounces, d_planes, stream,
+                       false);
+}
+
+int bih_render_path(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t frame,
+                    uint64_t seed, const bih_rows *rows, const bih_light_set *ls, const bih_bounce *bounce,
+                    uint32_t n_bounces, const bih_path *host_planes) {
+    return render_path(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, bounce, n_bounces, host_planes, nullptr,
+                       true);
+}
+
+int bih_path_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s, uint32_t level,
+                    const float n[3], float d[3]) {
+    if (!n || !d || spp == 0 || s >= spp || level == 0 || level > BIH_MAX_BOUNCES) return BIH_ERR_INVALID;
+    bih::bounce_dir(bih::area_seed_hash(seed), pixel, frame * spp + s, bih::kBounceSlot + (level - 1), n, d);
     return BIH_OK;
 }
 

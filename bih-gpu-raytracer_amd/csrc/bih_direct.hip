@@ -48,6 +48,10 @@
 //
 // One-bounce indirect lighting (bih_render_indirect*) runs the stages twice,
 // with the bounce walk k_bounce between the levels: see IArgs below.
+//
+// Multi-bounce paths (bih_render_path*) run them once per level, list-driven
+// past the primary level, with the walk k_path_bounce between the levels: see
+// PArgs below.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stddef.h>
@@ -564,7 +568,7 @@ __global__ void __launch_bounds__(kDT) k_bounce(const IArgs ia) {
                     dev::tri_normal(a.tris + 9ull * q.w, nrm);
                     uint32_t s;
                     const uint32_t gp = sample_pixel(a, r.i, &s);
-                    bounce_dir(ia.a.hseed, gp, ia.a.fs0 + s, nrm, r.w.d);
+                    bounce_dir(ia.a.hseed, gp, ia.a.fs0 + s, kBounceSlot, nrm, r.w.d);
                     has = dev::closest_start<dev::kWalkClosest>(sc, r.w, r.o, kShadowTLo);
                     if (!has) bray_write(ia, sc, r);   // missed the box / one-leaf tree: final
                 }
@@ -643,6 +647,234 @@ __global__ void __launch_bounds__(kDSetupT) k_indirect_resolve(const IArgs ia) {
         const uint32_t g = (uint32_t)(int)fmaxf(0.0f, fminf(255.0f, 255.0f * E));
         a.rgba[lp] = any ? (g | (g << 8) | (g << 16)) : kMissShade;
     }
+}
+
+// ---- Multi-bounce paths (bih_render_path*) ----
+// The stages above once per level, list-driven past the primary one.  Level 0
+// is bih_render_indirect's primary level (k_path_setup0: every hit sample's
+// record becomes {P, sorted position}, the hit samples are level 0's live
+// list).  Level k = 1..n_bounces: k_path_bounce walks one hashed ray (slot
+// kBounceSlot + k - 1) per sample of level k-1's live list, reads its record
+// from one of two record buffers and leaves {P_k, sorted position} in the
+// other, appends the samples it stopped to level k's live list and adds an
+// escaped sample's thr_{k-1} * sky; k_path_setup lists the live samples a
+// light faces for the shadow pass, which is the kernels above on the level's
+// records and lit plane; k_path_accum adds thr_k * e_k.  The sums go forward
+// into one f32 per sample (acc), so k_path_resolve needs no level's data.
+// thr_k is the same for every sample alive at level k: it travels as a scalar.
+struct PArgs {
+    AArgs a;                    // a.d.rec, a.d.lit: the level's records and lit plane (k_path_bounce: a.d.rec the level
+                                // before's); a.d.list, face, count, cursor: the shadow list, as everywhere
+    uint4 *rec_out;             // k_path_bounce: the level's records, the other buffer
+    uint4 *bounce;              // [P*spp] the level's plane of the caller's bih_hit, prim in file order, or null
+    const uint32_t *live;       // the live samples: of the level before (k_path_bounce), else of the level
+    const uint32_t *n_live;
+    uint32_t *live_out;         // k_path_bounce, k_path_setup0: the level's live samples
+    uint32_t *n_live_out;       // (zero at launch)
+    float *acc;                 // [P*spp] the sample's sum so far
+    uint8_t *hit0;              // [P*spp] 1: the primary sample hit (the pixel's miss shade)
+    const uint32_t *tri_idx;    // sorted position -> file order
+    uint32_t slot;              // k_path_bounce: the hash slot of the level's direction
+    float thr;                  // k_path_bounce: thr_{k-1}; k_path_accum: thr_k
+    float sky;
+};
+
+constexpr uint32_t kPListBlocks = 2048;   // the list-driven kernels' grid cap (they stride)
+
+// Level 0's setup over every sample of the call: k_indirect_setup's, which
+// also starts the sample's sum and notes whether it hit.
+__global__ void __launch_bounds__(kDSetupT) k_path_setup0(const PArgs pa) {
+    const DArgs &a = pa.a.d;
+    const uint64_t P = (uint64_t)a.nrows * a.w;
+    const uint64_t n = P * a.spp;
+    const uint64_t i = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
+    unsigned long long face = 0ull;
+    uint32_t bi = kNoHit;
+    if (i < n) {
+        const uint4 h = a.rec[i];
+        bi = h.w;
+        if (bi != kNoHit) {
+            const uint64_t lp = i / a.spp;
+            const uint32_t s = (uint32_t)(i - lp * a.spp);
+            const uint32_t lr = (uint32_t)(lp / a.w), x = (uint32_t)(lp - (uint64_t)lr * a.w);
+            const uint32_t y = dev::global_row(lr, a.row0, a.band_h, a.band_step);
+            float d[3], nrm[3], pt[3];
+            dev::primary_dir(a.cam, a.rng_in, P, lp, a.d_base, s, x, y, a.w, a.h, d);
+            const float t = __uint_as_float(h.x);
+            for (int k = 0; k < 3; ++k) pt[k] = a.cam[k] + t * d[k];
+            dev::tri_normal(a.tris + 9ull * bi, nrm);
+            face = facing_mask<kArea>(a, &pa.a, nrm, pt, y * a.w + x, s);
+            a.rec[i] = make_uint4(__float_as_uint(pt[0]), __float_as_uint(pt[1]), __float_as_uint(pt[2]), bi);
+        }
+        a.lit[i] = 0ull;
+        pa.acc[i] = 0.0f;
+        pa.hit0[i] = bi != kNoHit ? 1 : 0;
+    }
+    const uint32_t jb = wave_append(bi != kNoHit, pa.n_live_out);
+    if (bi != kNoHit) pa.live_out[jb] = (uint32_t)i;
+    const uint32_t j = wave_append(face != 0ull, a.count);
+    if (face != 0ull) {
+        a.list[j] = (uint32_t)i;
+        a.face[j] = face;
+    }
+}
+
+// The end of a level's walk for the lane's sample: a stopped ray leaves {P_k,
+// sorted position} in the level's record buffer and stays alive (returns true);
+// an escaped one collects thr_{k-1} * sky and ends.  The caller's bih_hit as
+// bray_write's.
+__device__ __forceinline__ bool pray_write(const PArgs &pa, const ClosestScene &s, const BRay &r) {
+    const bool stopped = r.w.bi != kNoHit;
+    float t = FLT_MAX, u = 0.0f, v = 0.0f;
+    uint32_t prim = kNoHit;
+    if (stopped) {
+        (void)dev::mt_tuv(s.tris + 9ull * r.w.bi, r.o, r.w.d, t, u, v);
+        prim = pa.tri_idx[r.w.bi];
+        pa.rec_out[r.i] = make_uint4(__float_as_uint(r.o[0] + t * r.w.d[0]), __float_as_uint(r.o[1] + t * r.w.d[1]),
+                                     __float_as_uint(r.o[2] + t * r.w.d[2]), r.w.bi);
+    } else {
+        pa.acc[r.i] = pa.acc[r.i] + pa.thr * pa.sky;
+    }
+    if (pa.bounce) pa.bounce[r.i] = make_uint4(__float_as_uint(t), __float_as_uint(u), __float_as_uint(v), prim);
+    return stopped;
+}
+
+// A level's bounce walk, k_bounce's shape: persistent one-wave blocks; work
+// item = a sample of the level before's live list, taken from the global
+// cursor; a lane whose walk has ended takes the next item while its wave-mates
+// keep walking.  The lanes whose walks ended in one round write together, so
+// that the stopped ones take consecutive slots of the level's live list with
+// one atomic (wave_append needs the whole wave).
+template <int LDS>
+__global__ void __launch_bounds__(kDT) k_path_bounce(const PArgs pa) {
+    __shared__ uint32_t s_node[LDS * kDT];
+    __shared__ float s_min[LDS * kDT];
+    __shared__ float s_max[LDS * kDT];
+    const DArgs &a = pa.a.d;
+    const uint32_t lane = threadIdx.x;
+    const dev::LaneStack<LDS> stk(s_node, s_min, s_max, a.spill);
+    const ClosestScene sc = dev::load_closest_scene(a.hdr, a.nodes, a.tris, a.dup);
+    const uint64_t n = *pa.n_live;
+    BRay r;
+    bool has = false;          // this lane walks a ray
+    bool more = true;          // (wave-uniform) the cursor may still be short of n
+    for (;;) {
+        bool fin = false;      // this lane's walk ended in this round
+        const unsigned long long idle = __ballot(!has);
+        if (more && (__popcll(idle) >= kDRefill || idle == ~0ull)) {
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            unsigned long long first = 0;
+            if (lane == 0) first = atomicAdd(a.cursor, (unsigned long long)cnt);
+            first = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(first >> 32)) << 32) |
+                    __builtin_amdgcn_readfirstlane((uint32_t)first);
+            if (first + cnt >= n) more = false;
+            if (!has) {
+                const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (first + rk < n) {
+                    r.i = pa.live[first + rk];
+                    const uint4 q = a.rec[r.i];   // {P, sorted position} of the level before
+                    r.o[0] = __uint_as_float(q.x); r.o[1] = __uint_as_float(q.y); r.o[2] = __uint_as_float(q.z);
+                    float nrm[3];
+                    dev::tri_normal(a.tris + 9ull * q.w, nrm);
+                    uint32_t s;
+                    const uint32_t gp = sample_pixel(a, r.i, &s);
+                    bounce_dir(pa.a.hseed, gp, pa.a.fs0 + s, pa.slot, nrm, r.w.d);
+                    has = dev::closest_start<dev::kWalkClosest>(sc, r.w, r.o, kShadowTLo);
+                    fin = !has;   // missed the box / one-leaf tree: final
+                }
+            }
+        }
+        if (has) {
+            for (int k = 0; k < kDSteps && !fin; ++k)
+                fin = dev::closest_step<dev::kWalkClosest>(sc, r.w, r.o, kShadowTLo, stk);
+            if (fin) has = false;
+        }
+        if (__ballot(fin)) {
+            const bool stopped = fin && pray_write(pa, sc, r);
+            const uint32_t j = wave_append(stopped, pa.n_live_out);
+            if (stopped) pa.live_out[j] = r.i;
+        }
+        if (!__ballot(has) && !more) break;
+    }
+}
+
+// A level's setup over its live samples: the facing mask at {P_k, n_k}; the
+// samples a light faces go to the shadow list; the level's lit word starts at 0.
+__global__ void __launch_bounds__(kDSetupT) k_path_setup(const PArgs pa) {
+    const DArgs &a = pa.a.d;
+    const uint32_t n = *pa.n_live;
+    // (the trip count is the block's: wave_append needs the whole wave)
+    for (uint32_t base = blockIdx.x * kDSetupT; base < n; base += gridDim.x * kDSetupT) {
+        const uint32_t j0 = base + threadIdx.x;
+        unsigned long long face = 0ull;
+        uint32_t i = 0;
+        if (j0 < n) {
+            i = pa.live[j0];
+            if (a.n_lights) {
+                const uint4 h = a.rec[i];
+                const float pt[3] = {__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(h.z)};
+                float nrm[3];
+                dev::tri_normal(a.tris + 9ull * h.w, nrm);
+                uint32_t s;
+                const uint32_t gp = sample_pixel(a, i, &s);
+                face = facing_mask<kArea>(a, &pa.a, nrm, pt, gp, s);
+            }
+            a.lit[i] = 0ull;
+        }
+        const uint32_t j = wave_append(face != 0ull, a.count);
+        if (face != 0ull) {
+            a.list[j] = i;
+            a.face[j] = face;
+        }
+    }
+}
+
+// A level's sum over its live samples, behind its shadow pass: acc += thr_k * e_k.
+__global__ void __launch_bounds__(kDSetupT) k_path_accum(const PArgs pa) {
+    __shared__ DLight s_light[kMaxLights];
+    const DArgs &a = pa.a.d;
+    if (threadIdx.x < a.n_lights) s_light[threadIdx.x] = a.lights[threadIdx.x];
+    __syncthreads();
+    const uint32_t n = *pa.n_live;
+    for (uint32_t j = blockIdx.x * kDSetupT + threadIdx.x; j < n; j += gridDim.x * kDSetupT) {
+        const uint32_t i = pa.live[j];
+        uint32_t s;
+        const uint32_t gp = sample_pixel(a, i, &s);
+        const float e = sample_sum<kArea>(a, &pa.a, s_light, a.rec + i, a.rec[i].w, a.lit[i], gp, s);
+        pa.acc[i] = pa.acc[i] + pa.thr * e;
+    }
+}
+
+// Per pixel: E over the samples' sums in the header's order, and the shade.
+__global__ void __launch_bounds__(kDSetupT) k_path_resolve(const PArgs pa) {
+    const DArgs &a = pa.a.d;
+    const uint64_t P = (uint64_t)a.nrows * a.w;
+    const uint64_t lp = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
+    if (lp >= P) return;
+    float E = 0.0f;
+    bool any = false;
+    for (uint32_t s = 0; s < a.spp; ++s) {
+        const uint64_t i = lp * a.spp + s;
+        any = any || pa.hit0[i] != 0;
+        const float e = pa.acc[i];
+        E = s == 0 ? e : E + e;
+    }
+    E = E / (float)a.spp;
+    if (a.irradiance) a.irradiance[lp] = E;
+    if (a.rgba) {
+        const uint32_t g = (uint32_t)(int)fmaxf(0.0f, fminf(255.0f, 255.0f * E));
+        a.rgba[lp] = any ? (g | (g << 8) | (g << 16)) : kMissShade;
+    }
+}
+
+// The caller's level planes before any level writes them: the miss record and
+// lit word 0, which an ended path's elements keep.
+__global__ void __launch_bounds__(kDSetupT) k_path_fill(uint4 *bounces, unsigned long long *lits, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
+    if (i >= n) return;
+    if (bounces) bounces[i] = make_uint4(__float_as_uint(FLT_MAX), 0u, 0u, kNoHit);
+    if (lits) lits[i] = 0ull;
 }
 
 // The argument block of a call: the frame, the tree, the lights in slot order
@@ -809,6 +1041,104 @@ int launch_indirect(const DeviceTree &t, const RenderArgs &ra, const IndirectPla
     if (p.irradiance || p.rgba) {
         const dim3 rgrid((uint32_t)((P + kDSetupT - 1) / kDSetupT));
         hipLaunchKernelGGL(k_indirect_resolve, rgrid, dim3(kDSetupT), 0, st, ia);
+        e = hipGetLastError();
+    }
+    return (int)e;
+}
+
+// The call's passes, each behind the one before on the stream: the fill of the
+// caller's level planes, level 0's setup, shadow pass and sum, then per level
+// the bounce walk, the setup, the shadow pass and the sum, and the resolve.
+// Nothing comes back to the host between them: every grid is sized for the
+// call's samples and the kernels read the lists' counts on the device.
+//
+// Two record buffers and two live lists suffice.  Level k's records go to
+// buffer k & 1 and its live list to list k & 1; its bounce walk reads level
+// k-1's (the other ones).  Level k's bounce, setup, shadow pass and sum have all
+// ended, in stream order, before level k+1's bounce overwrites level k-1's
+// records and list, which nothing reads after level k's bounce.  The shadow
+// list (list, face, count, cursor) is free again after each level's shadow pass.
+int launch_path(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l, float albedo, float sky,
+                uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0) return 0;
+    if (l.n_lights > kMaxLights || l.n_dir > l.n_lights) return (int)hipErrorInvalidValue;
+    if (l.area.n > kMaxAreaLights || l.area.n > l.n_lights - l.n_dir) return (int)hipErrorInvalidValue;
+    if (n_bounces == 0 || n_bounces > kMaxBounces) return (int)hipErrorInvalidValue;
+    static_assert(sizeof(PArgs) <= 4096, "kernel arguments");
+    PArgs pa;
+    fill_args(pa.a, t, ra, l, p, s, wa);
+    uint4 *const recs[2] = {reinterpret_cast<uint4 *>(s.rec), reinterpret_cast<uint4 *>(s.rec2)};
+    uint32_t *const lists[2] = {s.blist, s.blist2};
+    uint32_t *const counts[2] = {wa.word(kCurBounce), wa.word(kCurBounce2)};
+    pa.rec_out = nullptr;
+    pa.bounce = nullptr;
+    pa.live = nullptr;
+    pa.n_live = nullptr;
+    pa.live_out = lists[0];
+    pa.n_live_out = counts[0];
+    pa.acc = s.acc;
+    pa.hit0 = s.hit0;
+    pa.tri_idx = t.vals;
+    pa.slot = kBounceSlot;
+    pa.thr = 1.0f;
+    pa.sky = sky;
+    const uint64_t P = (uint64_t)ra.nrows * ra.w, n = P * ra.spp;
+    const dim3 sgrid((uint32_t)((n + kDSetupT - 1) / kDSetupT));
+    const dim3 lgrid(sgrid.x < kPListBlocks ? sgrid.x : kPListBlocks);
+    hipError_t e = hipSuccess;
+    if (p.bounces || p.lits) {
+        const uint64_t m = n * n_bounces;
+        hipLaunchKernelGGL(k_path_fill, dim3((uint32_t)((m + kDSetupT - 1) / kDSetupT)), dim3(kDSetupT), 0, st,
+                           reinterpret_cast<uint4 *>(p.bounces), p.lits, m);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = reset_counts(pa.a.d, st);
+    if (e == hipSuccess) e = hipMemsetAsync(counts[0], 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_path_setup0, sgrid, dim3(kDSetupT), 0, st, pa);
+    e = hipGetLastError();
+    float thr = 1.0f;   // thr_k
+    for (uint32_t k = 0;; ++k) {
+        // level k's shadow pass and sum over its live samples (pa.a.d.rec, lit: the level's)
+        pa.live = lists[k & 1];
+        pa.n_live = counts[k & 1];
+        pa.thr = thr;
+        if (e == hipSuccess && l.n_lights) e = launch_shadow(pa.a, l.area.n, n, wa.lds_slots, wa.max_blocks, st);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(k_path_accum, lgrid, dim3(kDSetupT), 0, st, pa);
+        e = hipGetLastError();
+        if (k == n_bounces) break;
+        // level k+1: the walk from level k's records into the other buffer, then its setup
+        pa.rec_out = recs[(k + 1) & 1];
+        pa.live_out = lists[(k + 1) & 1];
+        pa.n_live_out = counts[(k + 1) & 1];
+        pa.bounce = p.bounces ? reinterpret_cast<uint4 *>(p.bounces) + (uint64_t)k * n : nullptr;
+        pa.slot = kBounceSlot + k;
+        if (e == hipSuccess) e = reset_counts(pa.a.d, st);
+        if (e == hipSuccess) e = hipMemsetAsync(pa.n_live_out, 0, sizeof(uint32_t), st);
+        if (e != hipSuccess) return (int)e;
+        {
+            const uint64_t need = (n + kDT - 1) / kDT;
+            const dim3 grid((uint32_t)(need < wa.max_blocks ? need : wa.max_blocks)), block(kDT);
+            if (wa.lds_slots == (uint32_t)kTraceLdsTest) hipLaunchKernelGGL((k_path_bounce<kTraceLdsTest>), grid, block, 0, st, pa);
+            else hipLaunchKernelGGL((k_path_bounce<kTraceLds>), grid, block, 0, st, pa);
+            e = hipGetLastError();
+        }
+        thr = thr * albedo;
+        pa.a.d.rec = pa.rec_out;
+        pa.a.d.lit = p.lits ? p.lits + (uint64_t)k * n : p.lit_scratch;
+        pa.live = pa.live_out;
+        pa.n_live = pa.n_live_out;
+        if (e == hipSuccess) e = hipMemsetAsync(pa.a.d.cursor, 0, sizeof(unsigned long long), st);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(k_path_setup, lgrid, dim3(kDSetupT), 0, st, pa);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return (int)e;
+    if (p.irradiance || p.rgba) {
+        const dim3 rgrid((uint32_t)((P + kDSetupT - 1) / kDSetupT));
+        hipLaunchKernelGGL(k_path_resolve, rgrid, dim3(kDSetupT), 0, st, pa);
         e = hipGetLastError();
     }
     return (int)e;

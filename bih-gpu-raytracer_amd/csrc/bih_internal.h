@@ -387,8 +387,9 @@ int whitted_work(const void *mem, uint64_t rays, uint32_t ray_counts[9], unsigne
 constexpr uint32_t kCurTaken = 0;    // u32: rays (launch_trace) / tiles (launch_gbuffer) taken
 constexpr uint32_t kCurItems = 2;    // u64: shadow / bounce items taken
 constexpr uint32_t kCurListed = 4;   // u32: listed samples
-constexpr uint32_t kCurBounce = 6;   // u32: samples whose bounce hit
-constexpr size_t kTraceCursorBytes = ((kCurBounce + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
+constexpr uint32_t kCurBounce = 6;   // u32: samples whose bounce hit / a path's live samples, even levels
+constexpr uint32_t kCurBounce2 = 7;  // u32: a path's live samples, odd levels
+constexpr size_t kTraceCursorBytes = ((kCurBounce2 + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
 struct WorkArea {
     uint32_t *cursor = nullptr;
     uint32_t *spill = nullptr;
@@ -453,13 +454,17 @@ struct Lights {
 };
 // Per-sample scratch of a lighting launch (device; P*spp entries each): rec
 // (16 bytes), list (u32), face (u64); one-bounce launches also rec2 (16
-// bytes) and blist (u32) of the second level.
+// bytes) and blist (u32) of the second level; path launches also the second
+// live list blist2 (u32), the samples' sums acc (f32) and hit0 (one byte).
 struct Scratch {
     void *rec = nullptr;
     uint32_t *list = nullptr;
     unsigned long long *face = nullptr;
     void *rec2 = nullptr;
     uint32_t *blist = nullptr;
+    uint32_t *blist2 = nullptr;
+    float *acc = nullptr;
+    uint8_t *hit0 = nullptr;
 };
 struct DirectPlanes {
     unsigned long long *lit = nullptr;
@@ -479,6 +484,19 @@ struct IndirectPlanes : DirectPlanes {
 };
 int launch_indirect(const DeviceTree &t, const RenderArgs &a, const IndirectPlanes &p, const Lights &l, float albedo,
                     float sky, const Scratch &s, const WorkArea &wa, void *stream);
+// Multi-bounce paths (bih_direct.hip), behind a launch_gbuffer as
+// launch_indirect: level 0 as there, then n_bounces (1 .. kMaxBounces) levels
+// of one bounce ray per sample still alive.  bounces and lits (either may be
+// null) hold one plane of P*spp per level 1..n_bounces; lit_scratch
+// (u64[P*spp], never null when lits is) stands in for a level's lit plane.
+constexpr uint32_t kMaxBounces = 8;   // BIH_MAX_BOUNCES
+struct PathPlanes : DirectPlanes {
+    void *bounces = nullptr;
+    unsigned long long *lits = nullptr;
+    unsigned long long *lit_scratch = nullptr;
+};
+int launch_path(const DeviceTree &t, const RenderArgs &a, const PathPlanes &p, const Lights &l, float albedo, float sky,
+                uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream);
 int launch_rng_init(uint32_t *rng, uint32_t w, uint32_t row0, uint32_t nrows, uint32_t band_h,
                     uint32_t band_step, uint64_t seed, uint64_t skip, int device, void *stream);
 // dst = src's per-pixel state advanced by `steps` draws (planes of `pixels`; dst may be src)

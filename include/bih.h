@@ -40,7 +40,7 @@ extern "C" {
                                (4, added since: bih_trace*, bih_render_gbuffer*, BIH_PARAM_GBUFFER_MASK,
                                 bih_render_direct*, BIH_QUERY_T_HI and bih_ray.t_hi, bih_render_lights*,
                                 bih_render_area_lights*, bih_area_light_sample, bih_render_indirect*,
-                                bih_bounce_sample) */
+                                bih_bounce_sample, bih_render_path*, bih_path_sample, BIH_MAX_BOUNCES) */
 
 /* error codes */
 #define BIH_OK               0
@@ -716,6 +716,95 @@ int bih_render_indirect(const bih_tree *tree, const bih_camera *camera, uint32_t
  * BIH_ERR_INVALID. */
 int bih_bounce_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s,
                       const float n[3], float d[3]);
+
+/* Multi-bounce paths: bih_render_indirect carried on for n_bounces = 1 ..
+ * BIH_MAX_BOUNCES levels, in one call.  A sample's
+ * path goes on from each bounce hit with one more hashed, cosine-distributed
+ * ray until a ray escapes (it collects the sky) or level n_bounces is reached.
+ * Every level is lit by the same lights under bih_render_area_lights' rules.
+ * No new walk rule.
+ *
+ * Any plane may be NULL (not written); all five NULL -> BIH_ERR_INVALID.
+ * P = rows->nrows * w local pixels, sample index i = p*spp + s.  `bounces` and
+ * `lits` are level-major: level k's whole plane of P*spp elements starts at
+ * (k-1)*P*spp, k = 1 .. n_bounces.
+ *
+ * Semantics.  Every f32 operation is one separately rounded IEEE operation.
+ * Level 0 is bih_render_indirect's primary sample:
+ *  - hit {t, u, v, prim}, hit point P_0, normal n_0, the `lit` word and the
+ *    direct sum e_0 (bih_render_indirect's e_dir), exactly as defined there.
+ *  - `lit` is byte-identical to bih_render_area_lights' `lit` for the same
+ *    light set, whatever `bounce` and n_bounces hold.
+ *  - A sample is alive at level 0 when it hit.
+ * Level k = 1 .. n_bounces of a sample alive at level k-1:
+ *  - B_k[c] = n_{k-1}[c] + w_k[c], where w_k is bih_render_indirect's point of
+ *    the unit sphere with the hash's last mix taking the slot
+ *    BIH_BOUNCE_SLOT + (k-1) (wrapping uint32_t) in place of BIH_BOUNCE_SLOT:
+ *      h = mix(h ^ (frame*spp + s)); h = mix(h ^ (BIH_BOUNCE_SLOT + (k-1)));
+ *    No area light index (below BIH_MAX_AREA_LIGHTS = 16) reaches such a slot.
+ *    bih_path_sample(.., level = k, ..) returns exactly this B_k; at level 1 it
+ *    equals bih_bounce_sample on every bit.
+ *  - bounces[(k-1)*P*spp + i] is exactly the bih_hit of bih_trace(..,
+ *    BIH_QUERY_CLOSEST) for {o = P_{k-1}, t_lo = BIH_SHADOW_T_LO, d = B_k}; prim
+ *    is in file order, the miss record marks an escape.
+ *  - At a hit {t_k, prim_k} the sample is alive at level k: P_k[c] = P_{k-1}[c] +
+ *    t_k*B_k[c]; n_k = the `normal` formula on triangle prim_k;
+ *    lits[(k-1)*P*spp + i] and e_k are the lit word and per-sample sum
+ *    bih_render_area_lights' rules give with P_k, n_k in place of P, n (as
+ *    bih_render_indirect's lit2 and e2).  An area light's point Q is the same Q
+ *    at every level: same gp, same frame*spp + s, same j.
+ * Sums, forward along the path:
+ *  - thr_0 = 1.0f; acc = e_0.
+ *  - A hit at level k: thr_k = thr_{k-1} * albedo (one multiply), then
+ *    acc = acc + thr_k * e_k (one multiply, one add).
+ *  - An escape at level k: acc = acc + thr_{k-1} * sky (one multiply, one add);
+ *    the path ends.
+ *  - A hit at level n_bounces ends the path with no further term.
+ *  - e_s = acc; a missed primary sample has e_s = 0.  E, rgba and the miss shade
+ *    are bih_render_direct's.
+ * Ended paths: at every level after the one a sample's path ended at, and at
+ * every level of a missed primary sample, `bounces` holds the miss record
+ * {FLT_MAX, 0, 0, BIH_NO_HIT} and `lits` holds 0: every element of every plane
+ * passed is defined.
+ * n_bounces == 1: lit, bounces, lits, irradiance and rgba are byte-identical to
+ * bih_render_indirect's lit, bounce, lit2, irradiance and rgba (1.0f * x is x).
+ * Sky only: lights may be NULL or empty, as for bih_render_indirect; then lit
+ * and lits are 0, no shadow kernel runs, and with albedo = 1 E = sky x (paths
+ * of the pixel that escape at a level <= n_bounces) / spp.
+ * Errors: bih_render_indirect's, in its order, with one more right after
+ * bounce (the bih_bounce) == NULL: n_bounces == 0 or n_bounces >
+ * BIH_MAX_BOUNCES -> BIH_ERR_INVALID.  The alignment checks are lit and lits
+ * (8 bytes) and bounces (16 bytes).  nrows == 0 -> BIH_OK, nothing launched.
+ * RNG accounting, ordering (the ev_trace chain, rebuilds) and memory are
+ * bih_render_indirect's.  Scratch: next to its 48 bytes per sample 9 more (the
+ * sample's sum, an entry of a second live list, a hit flag), and 8 more (one
+ * lit word, reused by every level) once a call passes no `lits`; two record
+ * buffers and two live lists serve every n_bounces.  All of it is counted in
+ * bih_tree_info.device_bytes.  After the first call of a shape, light set,
+ * choice of planes and n_bounces further calls allocate nothing.  Nothing is
+ * read back between the levels: the device entry is asynchronous. */
+#define BIH_MAX_BOUNCES 8
+typedef struct bih_path {
+    uint64_t *lit;         /* u64[P*spp]       level 0's lit word; 8-byte aligned */
+    bih_hit  *bounces;     /* bih_hit[B*P*spp] level k's bounce record at (k-1)*P*spp + i; 16-byte aligned */
+    uint64_t *lits;        /* u64[B*P*spp]     level k's lit word at (k-1)*P*spp + i; 8-byte aligned */
+    float    *irradiance;  /* f32[P] */
+    uint32_t *rgba;        /* u32[P] 0x00BBGGRR */
+} bih_path;
+int bih_render_path_device(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                           uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                           const bih_light_set *lights, const bih_bounce *bounce, uint32_t n_bounces,
+                           const bih_path *d_planes, void *stream);          /* async; bih_sync waits */
+int bih_render_path(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                    uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                    const bih_light_set *lights, const bih_bounce *bounce, uint32_t n_bounces,
+                    const bih_path *host_planes);                            /* synchronous, host memory */
+/* Host only, no device: the direction B_k of level `level` = k that sample s of
+ * global pixel `pixel` = y*w + x uses in frame `frame` of a render with `spp`
+ * samples per pixel, for the normal n (n_{k-1}).  n or d NULL, spp == 0, s >=
+ * spp, level == 0 or level > BIH_MAX_BOUNCES -> BIH_ERR_INVALID. */
+int bih_path_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s,
+                    uint32_t level, const float n[3], float d[3]);
 
 /* The drop-in host loop (bih_render into a caller's framebuffer) ends in a
  * device-to-host copy of w*h*4 bytes.  Into pageable memory the runtime
