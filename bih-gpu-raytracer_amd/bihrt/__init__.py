@@ -22,7 +22,7 @@ from . import scenes  # noqa: F401
 from ._lib import (PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_STATIC_SOUP,
                    PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS, PARAM_GBUFFER_MASK,
                    AREA_LIGHT_DTYPE, MAX_AREA_LIGHTS, AreaLight, LightSet, BOUNCE_SLOT, Bounce, Indirect,
-                   MAX_BOUNCES, Path,
+                   MAX_BOUNCES, Path, MATERIAL_DTYPE, MAX_MATERIALS, Material, PathRgb,
                    NO_HIT, LIGHT_DTYPE, POINT_LIGHT_DTYPE, MAX_LIGHTS, SHADOW_T_LO, QUERY_CLOSEST, QUERY_OCCLUDED,
                    QUERY_T_HI, QUERY_CLOSEST_WITHIN, QUERY_OCCLUDED_WITHIN, PointLight, Direct, GBuffer, Hit, Light, Ray, TRAVERSE_ANYHIT,
                    TRAVERSE_REFERENCE, BihError, Camera, Framebuffer, Rows, Scene, TreeInfo, check, load)
@@ -80,6 +80,13 @@ PATH_PLANES = {"lit": (np.uint64, 0), "bounces": (HIT_DTYPE, -1), "lits": (np.ui
 PATH = tuple(PATH_PLANES)
 
 
+# the planes of a colour path render (bih_path_rgb), as PATH_PLANES; "radiance"
+# holds R, G, B per pixel
+PATH_RGB_PLANES = {"lit": (np.uint64, 0), "bounces": (HIT_DTYPE, -1), "lits": (np.uint64, -1),
+                   "radiance": (np.float32, 3), "rgba": (np.uint32, 1)}
+PATH_RGB = tuple(PATH_RGB_PLANES)
+
+
 def _rows_ref(rows: Rows | None):
     """The bih_rows * argument of an optional Rows (NULL: the whole image)."""
     return C.byref(rows) if rows is not None else None
@@ -121,6 +128,17 @@ def pack_area_lights(lights) -> np.ndarray:
         rows = np.ascontiguousarray(a, np.float32).reshape(-1, 10)
         a = np.zeros(rows.shape[0], AREA_LIGHT_DTYPE)
         a["corner"], a["edge_u"], a["edge_v"], a["weight"] = rows[:, 0:3], rows[:, 3:6], rows[:, 6:9], rows[:, 9]
+    return np.ascontiguousarray(a).reshape(-1)
+
+
+def pack_materials(materials) -> np.ndarray:
+    """(k,) MATERIAL_DTYPE array (bih_material records) of such an array or of
+    (k, 6) rows {albedo R G B, emission R G B}."""
+    a = np.asarray(materials)
+    if a.dtype != MATERIAL_DTYPE:
+        rows = np.ascontiguousarray(a, np.float32).reshape(-1, 6)
+        a = np.zeros(rows.shape[0], MATERIAL_DTYPE)
+        a["albedo"], a["emission"] = rows[:, 0:3], rows[:, 3:6]
     return np.ascontiguousarray(a).reshape(-1)
 
 
@@ -208,6 +226,20 @@ class GPUArrayManager:
     def set_param(self, param: int, value: int):
         """bih_tree_set_param (PARAM_*): work-order and test knobs; none changes a pixel."""
         check(load().bih_tree_set_param(self._tree, param, value), "bih_tree_set_param")
+
+    def set_materials(self, materials, tri_material=None):
+        """bih_tree_set_materials (synchronous; host arrays, copied): the tree's
+        palette -- MATERIAL_DTYPE records or (k, 6) rows {albedo, emission} -- and
+        per triangle in file order the index of its material (None: every
+        triangle uses material 0).  materials None or empty: the tree's
+        materials are removed.  Ids stay valid across rebuild()."""
+        pal = pack_materials(materials) if materials is not None else np.zeros(0, MATERIAL_DTYPE)
+        ids = np.ascontiguousarray(tri_material, np.uint32).reshape(-1) if tri_material is not None else None
+        if ids is not None and ids.shape[0] != self.info().n_tris:
+            raise ValueError("tri_material holds one id per triangle")
+        check(load().bih_tree_set_materials(self._tree, C.c_void_p(pal.ctypes.data) if pal.shape[0] else None,
+                                            pal.shape[0], C.c_void_p(ids.ctypes.data) if ids is not None else None),
+              "bih_tree_set_materials")
 
     def reserve(self, w: int, h: int, spp: int, rows: Rows | None = None, max_frames: int = 1):
         """bih_reserve: size every per-call buffer of renders of this shape (calls
@@ -602,6 +634,48 @@ class Renderer:
               "bih_render_path_device")
         del keep
 
+    @staticmethod
+    def _sky3(sky):
+        return (C.c_float * 3)(*[float(x) for x in np.asarray(sky, np.float32).reshape(3)])
+
+    def render_path_rgb(self, dir_lights, point_lights, area_lights, sky, n_bounces: int, frame: int | None = None,
+                        rows: Rows | None = None, planes=PATH_RGB) -> dict:
+        """render_path with the tree's materials (GPUArrayManager.set_materials)
+        and an RGB sky, a 3-vector (bih_render_path_rgb; synchronous).  Returns
+        a dict of the planes asked for (PATH_RGB_PLANES): "lit", "bounces",
+        "lits" and "rgba" as render_path's, "radiance" (nrows, w, 3) float32."""
+        f = self.frame if frame is None else frame
+        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
+        nrows = rows.nrows if rows is not None else self.h
+        S = nrows * self.w * self.spp
+        out, pp = {}, PathRgb()
+        for name in planes:
+            dt, k = PATH_RGB_PLANES[name]
+            shape = ((nrows, self.w) if k == 1 else (nrows, self.w, k)) if k > 0 else ((n_bounces, S) if k < 0 else S)
+            out[name] = np.zeros(shape, dt)
+            setattr(pp, name, out[name].ctypes.data)
+        check(load().bih_render_path_rgb(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
+                                         self.seed, _rows_ref(rows), C.byref(ls), self._sky3(sky), n_bounces,
+                                         C.byref(pp)),
+              "bih_render_path_rgb")
+        del keep
+        self.frame = f + 1
+        return out
+
+    def render_path_rgb_device(self, ptrs: dict, dir_lights, point_lights, area_lights, sky, n_bounces: int,
+                               frame: int, rows: Rows | None = None, stream: int | None = None):
+        """Asynchronous render_path_rgb into device memory
+        (bih_render_path_rgb_device): ptrs maps plane names (PATH_RGB_PLANES) to
+        device pointers; planes left out are not written.  The light arrays and
+        sky are host memory, copied by the call."""
+        pp = _device_planes(PathRgb(), PATH_RGB_PLANES, ptrs)
+        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
+        check(load().bih_render_path_rgb_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
+                                                frame, self.seed, _rows_ref(rows), C.byref(ls), self._sky3(sky),
+                                                n_bounces, C.byref(pp), C.c_void_p(stream or 0)),
+              "bih_render_path_rgb_device")
+        del keep
+
     def whitted_work(self) -> dict:
         """Per bounce d = 0..8 of the last Whitted render (run with
         PARAM_WHITTED_COUNTERS on): rays traced, BIH nodes entered, triangles
@@ -702,4 +776,5 @@ __all__ = ["GPUArrayManager", "Renderer", "Model", "load_obj", "host_register", 
            "QUERY_T_HI", "QUERY_CLOSEST_WITHIN", "QUERY_OCCLUDED_WITHIN", "PointLight", "POINT_LIGHT_DTYPE",
            "pack_point_lights", "AreaLight", "LightSet", "AREA_LIGHT_DTYPE", "MAX_AREA_LIGHTS",
            "pack_area_lights", "area_light_sample", "Bounce", "Indirect", "INDIRECT", "INDIRECT_PLANES",
-           "BOUNCE_SLOT", "bounce_sample", "Path", "PATH", "PATH_PLANES", "MAX_BOUNCES", "path_sample"]
+           "BOUNCE_SLOT", "bounce_sample", "Path", "PATH", "PATH_PLANES", "MAX_BOUNCES", "path_sample",
+           "MATERIAL_DTYPE", "Material", "PathRgb", "PATH_RGB", "PATH_RGB_PLANES", "MAX_MATERIALS", "pack_materials"]

@@ -40,6 +40,9 @@ POINT_LIGHT_DTYPE = np.dtype([("pos", np.float32, 3), ("weight", np.float32)])  
 SHADOW_T_LO = 1e-4        # BIH_SHADOW_T_LO
 BOUNCE_SLOT = 0x80000000  # BIH_BOUNCE_SLOT: the hash slot of the bounce direction
 MAX_BOUNCES = 8           # BIH_MAX_BOUNCES: levels of a path (bih_render_path*)
+MAX_MATERIALS = 65536     # BIH_MAX_MATERIALS: records of a tree's palette (bih_tree_set_materials)
+MATERIAL_DTYPE = np.dtype([("albedo", np.float32, 3), ("reserved0", np.float32),       # numpy view of a
+                           ("emission", np.float32, 3), ("reserved1", np.float32)])    # bih_material array
 MAX_AREA_LIGHTS = 16      # bih_render_area_lights*: area lights of one call
 AREA_LIGHT_DTYPE = np.dtype([("corner", np.float32, 3), ("weight", np.float32),       # numpy view of a
                              ("edge_u", np.float32, 3), ("reserved0", np.float32),    # bih_area_light array
@@ -155,6 +158,19 @@ class Path(C.Structure):
                 ("rgba", C.c_void_p)]
 
 
+class Material(C.Structure):
+    """bih_material: diffuse reflectance and emitted radiance, R G B (32 bytes)."""
+    _fields_ = [("albedo", C.c_float * 3), ("reserved0", C.c_float), ("emission", C.c_float * 3),
+                ("reserved1", C.c_float)]
+
+
+class PathRgb(C.Structure):
+    """bih_path_rgb: bih_path's planes with radiance (three floats per pixel) in
+    the place of irradiance."""
+    _fields_ = [("lit", C.c_void_p), ("bounces", C.c_void_p), ("lits", C.c_void_p), ("radiance", C.c_void_p),
+                ("rgba", C.c_void_p)]
+
+
 class BinsStats(C.Structure):
     _fields_ = [("usable", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
                 ("list_entries", C.c_uint64), ("global_entries", C.c_uint32)]
@@ -260,6 +276,11 @@ def load():
     L.bih_render_path.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
                                   C.POINTER(LightSet), C.POINTER(Bounce), u32, C.POINTER(Path)]
     L.bih_path_sample.argtypes = [u64, u32, u32, u32, u32, u32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.bih_tree_set_materials.argtypes = [vp, vp, u32, vp]
+    L.bih_render_path_rgb_device.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                             C.POINTER(LightSet), C.POINTER(C.c_float), u32, C.POINTER(PathRgb), vp]
+    L.bih_render_path_rgb.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
+                                      C.POINTER(LightSet), C.POINTER(C.c_float), u32, C.POINTER(PathRgb)]
     for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
@@ -270,7 +291,7 @@ def load():
                  "bih_render_lights_device", "bih_render_lights", "bih_render_area_lights_device",
                  "bih_render_area_lights", "bih_area_light_sample", "bih_render_indirect_device",
                  "bih_render_indirect", "bih_bounce_sample", "bih_render_path_device", "bih_render_path",
-                 "bih_path_sample"):
+                 "bih_path_sample", "bih_tree_set_materials", "bih_render_path_rgb_device", "bih_render_path_rgb"):
         getattr(L, name).restype = i32
     _lib = L
     return L

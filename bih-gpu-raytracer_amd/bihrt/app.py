@@ -20,6 +20,7 @@ usage:  python -m bihrt --mesh sponza --resources path/to/resources --frames 10 
                      [--panel CX,CY,CZ,UX,UY,UZ,VX,VY,VZ[,W]]...   (area lights: soft shadows)
                      [--bounce ALBEDO[,SKY]]          (one bounce of indirect light and a sky term; alone: sky only)
                      [--bounces N]                    (with --bounce: paths of N = 1..8 bounces)
+                     [--colour]                       (with --bounces, --scene cornell: its materials, RGB)
         python -m bihrt --obj file.obj ...     (explicit path)
         python -m bihrt --scene cornell|torus|soup[:N] ...   (built-in scenes)
 """
@@ -77,7 +78,7 @@ class App:
 
     def run(self, frames: int, out_pattern: str | None = None, rebuild: bool = True,
             every: int = 1, gbuffer_pattern: str | None = None, direct_pattern: str | None = None,
-            lights=None, lamps=None, panels=None, bounce=None, bounces=None):
+            lights=None, lamps=None, panels=None, bounce=None, bounces=None, materials=None):
         """App::Run for a fixed number of frames: Renderer::Render each frame
         (BIH rebuild + render), optional PPM output; returns the frames.
         gbuffer_pattern: one .npz of the frame's G-buffer planes
@@ -89,8 +90,13 @@ class App:
         to both (Renderer.render_area_lights).  bounce: (albedo, sky) adds one
         bounce of indirect light and the sky term (Renderer.render_indirect);
         lights = None is then no directional light.  bounces: with bounce,
-        paths of that many bounces (Renderer.render_path)."""
+        paths of that many bounces (Renderer.render_path).  materials: with
+        bounces, a (palette, tri_material) pair: colour paths under a sky
+        (s, s, s), s = bounce's sky (Renderer.render_path_rgb); bounce's albedo
+        is not used."""
         assert self.renderer is not None, "load_models first"
+        if materials is not None:
+            self.arrays.set_materials(*materials)
         if direct_pattern and lights is None and bounce is None:
             lights = scenes.sky_dome(8)
         imgs = []
@@ -120,7 +126,10 @@ class App:
                 d = os.path.dirname(path)
                 if d:
                     os.makedirs(d, exist_ok=True)
-                if bounce is not None and bounces is not None:
+                if bounce is not None and bounces is not None and materials is not None:
+                    shade = self.renderer.render_path_rgb(lights, lamps, panels, (bounce[1],) * 3, bounces, f,
+                                                          planes=("rgba",))["rgba"]
+                elif bounce is not None and bounces is not None:
                     shade = self.renderer.render_path(lights, lamps, panels, bounce, bounces, f,
                                                       planes=("rgba",))["rgba"]
                 elif bounce is not None:
@@ -167,11 +176,20 @@ def main(argv=None) -> int:
     ap.add_argument("--bounces", type=int, default=None, metavar="N",
                     help="--direct --bounce: follow each path for N = 1..8 bounces (without it: the one-bounce "
                          "render)")
+    ap.add_argument("--colour", action="store_true",
+                    help="--direct --bounce --bounces, --scene cornell: a colour path render with the scene's "
+                         "built-in materials (red and green walls, the lamp quad emissive) under a sky (SKY, SKY, "
+                         "SKY); ALBEDO is not used, and there is no light but the lamp's emission unless --sky K, "
+                         "--sun, --lamp or --panel add one")
     ap.add_argument("--every", type=int, default=1, help="write every k-th frame")
     ap.add_argument("--no-rebuild", action="store_true",
                     help="build once (the reference rebuilds every frame)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.colour and a.bounces is None:
+        ap.error("--colour belongs to --bounces")
+    if a.colour and a.scene != "cornell":
+        ap.error("--colour needs a scene with built-in materials (--scene cornell)")
     if a.mesh:
         path = mesh_path(a.resources, a.mesh)
         if not os.path.exists(path):
@@ -251,5 +269,5 @@ def main(argv=None) -> int:
     app.load_models(scene)
     app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every, gbuffer_pattern=a.gbuffer,
             direct_pattern=a.direct, lights=lights, lamps=lamps, panels=panels, bounce=bounce,
-            bounces=a.bounces)
+            bounces=a.bounces, materials=scenes.cornell_materials() if a.colour else None)
     return 0

@@ -292,3 +292,17 @@ def cornell_panel(weight: float = 1.0) -> np.ndarray:
     centimetre below it (geometry coincident with a panel may or may not shadow
     it), facing down; (1,) bihrt.AREA_LIGHT_DTYPE."""
     return _panel_rows([((0.1, 0.98, 1.0), (0.6, 0.0, 0.0), (0.0, 0.0, 0.6), weight)])
+
+
+def cornell_materials():
+    """cornell()'s colours for GPUArrayManager.set_materials: a palette
+    (4,) bihrt.MATERIAL_DTYPE -- 0 white (floor, ceiling, back wall, blocks),
+    1 red (left wall), 2 green (right wall), 3 the lamp quad (triangles 30 and
+    31), which emits (17, 12, 4) -- and the (32,) uint32 material of each
+    triangle in file order."""
+    from . import pack_materials
+    pal = pack_materials([(0.73, 0.73, 0.73, 0, 0, 0), (0.65, 0.05, 0.05, 0, 0, 0), (0.12, 0.45, 0.15, 0, 0, 0),
+                          (0.78, 0.78, 0.78, 17.0, 12.0, 4.0)])
+    ids = np.zeros(32, np.uint32)
+    ids[6:8], ids[8:10], ids[30:32] = 1, 2, 3
+    return pal, ids

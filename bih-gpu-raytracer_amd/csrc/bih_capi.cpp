@@ -48,6 +48,7 @@ using bih::kTraceCursorBytes;                           // the work area's curso
 constexpr size_t kDirectSampleBytes = 16 + 8 + 4;       // dr_mem per sample: record, facing mask, list entry
 constexpr size_t kIndirectSampleBytes = 16 + 4;         // in_mem per sample: bounce record, hit-list entry
 constexpr size_t kPathSampleBytes = 4 + 4 + 1;          // pt_mem per sample: sum, second live-list entry, primary-hit flag
+constexpr size_t kPathRgbSampleBytes = 16 + 16;         // pc_mem per sample: RGB sum record, RGB throughput record
 
 // Per-camera structures (bih_render.hip / bih_bins.hip): primary-ray records,
 // frustum bins and the tile queue of one camera.  A tree keeps kCamSets of
@@ -343,6 +344,18 @@ struct bih_tree {
     size_t pt_cap = 0;               // samples (kPathSampleBytes each)
     char *pt_stage = nullptr;
     size_t pt_stage_cap = 0;         // bytes
+    // Colour path renders (bih_render_path_rgb*) are a path render whose sums
+    // and throughputs are RGB records per sample (pc_mem, next to pt_mem, whose
+    // scalar sums they leave alone); the host entry's device planes.  Same
+    // users, same waits.  The materials (bih_tree_set_materials) are the
+    // tree's, by file position: no tree buffer holds them, a rebuild keeps them.
+    char *pc_mem = nullptr;
+    size_t pc_cap = 0;               // samples (kPathRgbSampleBytes each)
+    char *pc_stage = nullptr;
+    size_t pc_stage_cap = 0;         // bytes
+    bih_material *mt_pal = nullptr;  // the palette; null: the tree has no materials
+    uint32_t *mt_ids = nullptr;      // [t.n] material of a file-order triangle; null: material 0
+    size_t mt_bytes = 0;             // of both
 };
 
 namespace {
@@ -839,6 +852,10 @@ void bih_free(bih_tree *tr) {
     if (tr->in_stage) (void)hipFree(tr->in_stage);
     if (tr->pt_mem) (void)hipFree(tr->pt_mem);
     if (tr->pt_stage) (void)hipFree(tr->pt_stage);
+    if (tr->pc_mem) (void)hipFree(tr->pc_mem);
+    if (tr->pc_stage) (void)hipFree(tr->pc_stage);
+    if (tr->mt_pal) (void)hipFree(tr->mt_pal);
+    if (tr->mt_ids) (void)hipFree(tr->mt_ids);
     if (tr->ev_trace) (void)hipEventDestroy(tr->ev_trace);
     for (int k = 0; k < kSlots; ++k) {
         if (tr->ev0[k]) (void)hipEventDestroy(tr->ev0[k]);
@@ -902,7 +919,8 @@ int bih_tree_get_info(const bih_tree *tr, bih_tree_info *info) {
                          tr->gb_mask_cap * 8 + tr->gb_scratch_cap * 4 + tr->gb_stage_cap +
                          tr->dr_cap * kDirectSampleBytes + tr->dr_lit_cap * 8 + tr->dr_stage_cap +
                          tr->in_cap * kIndirectSampleBytes + tr->in_lit2_cap * 8 + tr->in_stage_cap +
-                         tr->pt_cap * kPathSampleBytes + tr->pt_stage_cap;
+                         tr->pt_cap * kPathSampleBytes + tr->pt_stage_cap +
+                         tr->pc_cap * kPathRgbSampleBytes + tr->pc_stage_cap + tr->mt_bytes;
     info->build_ms = tr->build_ms;
     info->device_allocs = tr->allocs + tr->t.allocs + tr->back[0].allocs + tr->back[1].allocs;
     return BIH_OK;
@@ -2305,6 +2323,10 @@ struct DirectJob {
     // bih_render_path*: n_bounces > 0 (with indirect set; ind.bounce and ind.lit2 then hold
     // the level planes `bounces` and `lits`)
     uint32_t n_bounces = 0;
+    // bih_render_path_rgb*: rgb set (with n_bounces; bounce is unused, planes.irradiance null)
+    bool rgb = false;
+    float sky[3] = {0.0f, 0.0f, 0.0f};
+    float *radiance = nullptr;
 };
 
 // bih_render_gbuffer_device under the tree's lock, arguments checked, nrows > 0.
@@ -2363,8 +2385,19 @@ static int gbuffer_locked(bih_tree *tr, const Frame &f, const bih_gbuffer &pl, v
             pp.bounces = dj->ind.bounce;
             pp.lits = reinterpret_cast<unsigned long long *>(dj->ind.lit2);
             pp.lit_scratch = tr->in_lit2;
-            rc = bih::launch_path(tr->t, a, pp, dj->lights, dj->bounce.albedo, dj->bounce.sky, dj->n_bounces, sc, wa,
-                                  st);
+            if (dj->rgb) {
+                bih::PathRgb c;
+                c.palette = tr->mt_pal;
+                c.ids = tr->mt_ids;
+                c.acc3 = tr->pc_mem;
+                c.thr3 = tr->pc_mem + 16 * tr->pc_cap;
+                c.radiance = dj->radiance;
+                memcpy(c.sky, dj->sky, sizeof c.sky);
+                rc = bih::launch_path_rgb(tr->t, a, pp, dj->lights, c, dj->n_bounces, sc, wa, st);
+            } else {
+                rc = bih::launch_path(tr->t, a, pp, dj->lights, dj->bounce.albedo, dj->bounce.sky, dj->n_bounces, sc,
+                                      wa, st);
+            }
         } else if (dj->indirect) {
             ip.bounce = dj->ind.bounce;
             ip.lit2 = dj->ind.lit2 ? reinterpret_cast<unsigned long long *>(dj->ind.lit2) : tr->in_lit2;
@@ -2488,7 +2521,8 @@ static int direct_locked(bih_tree *tr, const Frame &f, const DirectJob &dj, void
     const bool own_lit2 = dj.indirect && !dj.ind.lit2 && tr->in_lit2_cap < S;
     const bool own_in = dj.indirect && tr->in_cap < S;
     const bool own_pt = dj.n_bounces && tr->pt_cap < S;
-    if ((tr->dr_cap < S || own_lit || own_lit2 || own_in || own_pt) && tr->trace_used) {
+    const bool own_pc = dj.rgb && tr->pc_cap < S;
+    if ((tr->dr_cap < S || own_lit || own_lit2 || own_in || own_pt || own_pc) && tr->trace_used) {
         // (the users of both buffers are direct-lighting launches: each ends before its ev_trace record)
         const hipError_t e = hipEventSynchronize(tr->ev_trace);
         if (e != hipSuccess) return map_hip((int)e);
@@ -2498,6 +2532,7 @@ static int direct_locked(bih_tree *tr, const Frame &f, const DirectJob &dj, void
     if (rc == BIH_OK && own_lit2) rc = grow(tr, &tr->in_lit2, &tr->in_lit2_cap, S, S * 8);
     if (rc == BIH_OK && own_in) rc = grow(tr, &tr->in_mem, &tr->in_cap, S, S * kIndirectSampleBytes);
     if (rc == BIH_OK && own_pt) rc = grow(tr, &tr->pt_mem, &tr->pt_cap, S, S * kPathSampleBytes);
+    if (rc == BIH_OK && own_pc) rc = grow(tr, &tr->pc_mem, &tr->pc_cap, S, S * kPathRgbSampleBytes);
     if (rc) return rc;
     bih_gbuffer g = {};
     g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
@@ -2680,6 +2715,103 @@ int bih_render_path(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint3
                     uint32_t n_bounces, const bih_path *host_planes) {
     return render_path(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, bounce, n_bounces, host_planes, nullptr,
                        true);
+}
+
+int bih_tree_set_materials(bih_tree *tr, const bih_material *materials, uint32_t n_materials,
+                           const uint32_t *tri_material) {
+    static_assert(sizeof(bih_material) == 32, "bih_material: two 16-byte words (the kernels' float4 pairs)");
+    if (!tr) return BIH_ERR_INVALID;
+    if (n_materials > BIH_MAX_MATERIALS) return BIH_ERR_INVALID;
+    if ((materials == nullptr) != (n_materials == 0)) return BIH_ERR_INVALID;
+    if (n_materials == 0 && tri_material) return BIH_ERR_INVALID;
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    const size_t n = tr->t.n;
+    if (tri_material)
+        for (size_t k = 0; k < n; ++k)
+            if (tri_material[k] >= n_materials) return BIH_ERR_INVALID;
+    // the new copies first: a failure leaves the tree's set as it was
+    bih_material *pal = nullptr;
+    uint32_t *ids = nullptr;
+    const size_t pal_bytes = (size_t)n_materials * sizeof(bih_material), ids_bytes = tri_material ? n * 4 : 0;
+    hipError_t e = hipSuccess;
+    if (pal_bytes) e = tree_malloc(tr, &pal, pal_bytes);
+    if (e == hipSuccess && ids_bytes) e = tree_malloc(tr, &ids, ids_bytes);
+    if (e == hipSuccess && pal_bytes) e = hipMemcpy(pal, materials, pal_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && ids_bytes) e = hipMemcpy(ids, tri_material, ids_bytes, hipMemcpyHostToDevice);
+    // the renders that read the old set are links of the ev_trace chain
+    if (e == hipSuccess && tr->trace_used) e = hipEventSynchronize(tr->ev_trace);
+    if (e != hipSuccess) {
+        if (pal) (void)hipFree(pal);
+        if (ids) (void)hipFree(ids);
+        return map_hip((int)e);
+    }
+    if (tr->mt_pal) (void)hipFree(tr->mt_pal);
+    if (tr->mt_ids) (void)hipFree(tr->mt_ids);
+    tr->mt_pal = pal;
+    tr->mt_ids = ids;
+    tr->mt_bytes = pal_bytes + ids_bytes;
+    return BIH_OK;
+}
+
+// The body of the two colour path entries, as render_path.
+static int render_path_rgb(const bih_tree *ctr, Frame f, const bih_rows *rows_in, const bih_light_set *ls_in,
+                           const float *sky, uint32_t n_bounces, const bih_path_rgb *planes, void *stream, bool host) {
+    static const bih_light_set no_lights = {nullptr, 0, nullptr, 0, nullptr, 0};
+    const bih_light_set *ls = ls_in ? ls_in : &no_lights;
+    bih_direct three = {};    // (radiance in the place of irradiance: "all planes NULL" counts it)
+    bih_indirect five = {};
+    if (planes) {
+        three = bih_direct{planes->lit, planes->radiance, planes->rgba};
+        five = bih_indirect{planes->lit, planes->bounces, planes->lits, planes->radiance, planes->rgba};
+    }
+    int rc = light_set_check(ctr, &f, rows_in, ls, planes ? &three : nullptr, planes ? &five : nullptr);
+    if (rc) return rc;
+    if (!sky) return BIH_ERR_INVALID;
+    if (n_bounces == 0 || n_bounces > BIH_MAX_BOUNCES) return BIH_ERR_INVALID;
+    if (((uintptr_t)planes->lits & 7u) || ((uintptr_t)planes->bounces & 15u)) return BIH_ERR_INVALID;
+    if (f.rows.nrows == 0) return BIH_OK;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    if (!tr->mt_pal) return BIH_ERR_INVALID;   // no materials: bih_tree_set_materials first
+    DirectJob dj;
+    merge_light_set(ls, f, &dj.lights);
+    dj.planes = bih_direct{planes->lit, nullptr, planes->rgba};
+    dj.indirect = true;
+    dj.bounce = bih_bounce{1.0f, 0.0f};
+    dj.ind = five;
+    dj.ind.irradiance = nullptr;
+    dj.n_bounces = n_bounces;
+    dj.rgb = true;
+    memcpy(dj.sky, sky, sizeof dj.sky);
+    dj.radiance = planes->radiance;
+    if (!host) return direct_locked(tr, f, dj, stream);
+    const size_t P = f.pixels(), S = (size_t)f.samples(), B = n_bounces;
+    Stage<5> sg{{planes->lit, planes->bounces, planes->lits, planes->radiance, planes->rgba},
+                {S * 8, B * S * sizeof(bih_hit), B * S * 8, P * 12, P * 4}};
+    rc = sg.place(tr, &tr->pc_stage, &tr->pc_stage_cap);
+    if (rc) return rc;
+    dj.planes.lit = static_cast<uint64_t *>(sg.dev(0));
+    dj.ind.bounce = static_cast<bih_hit *>(sg.dev(1));
+    dj.ind.lit2 = static_cast<uint64_t *>(sg.dev(2));
+    dj.radiance = static_cast<float *>(sg.dev(3));
+    dj.planes.rgba = static_cast<uint32_t *>(sg.dev(4));
+    return sg.finish(tr, direct_locked(tr, f, dj, nullptr));
+}
+
+int bih_render_path_rgb_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                               uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
+                               const float sky[3], uint32_t n_bounces, const bih_path_rgb *d_planes, void *stream) {
+    return render_path_rgb(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, sky, n_bounces, d_planes, stream,
+                           false);
+}
+
+int bih_render_path_rgb(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                        uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
+                        const float sky[3], uint32_t n_bounces, const bih_path_rgb *host_planes) {
+    return render_path_rgb(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, sky, n_bounces, host_planes, nullptr,
+                           true);
 }
 
 int bih_path_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s, uint32_t level,

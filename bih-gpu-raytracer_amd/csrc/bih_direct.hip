@@ -739,14 +739,64 @@ __device__ __forceinline__ bool pray_write(const PArgs &pa, const ClosestScene &
     return stopped;
 }
 
+// ---- Colour paths (bih_render_path_rgb*) ----
+// The paths above with a material per triangle: the sample's sum and its
+// throughput are RGB and per sample, one 16-byte record each ({R, G, B, -}: a
+// lane moves its sample's three channels with one load or store), touched by
+// list-driven kernels and the walk's writer only.  Levels, rays, lists, lit
+// words and e_k are the grey call's: every kernel that steers a path runs
+// unchanged.  A hit's material comes from its file-order triangle, which the
+// generation's tri_idx gives from the sorted position: ids follow a rebuild.
+struct CArgs {
+    PArgs p;                    // (p.acc, p.thr, p.sky: unused)
+    float4 *acc3;               // [P*spp] the sample's RGB sum so far
+    float4 *thr3;               // [P*spp] the sample's RGB throughput
+    const float4 *pal;          // two per material: {albedo, -}, {emission, -} (bih_material)
+    const uint32_t *ids;        // file-order triangle -> material, or null: material 0
+    float *radiance;            // [3P] or null
+    float sky[3];
+};
+
+__device__ __forceinline__ const PArgs &path_args(const PArgs &pa) { return pa; }
+__device__ __forceinline__ const PArgs &path_args(const CArgs &ca) { return ca.p; }
+
+// pray_write for a colour path: a stopped ray collects thr_{k-1} * emission(m_k)
+// and its throughput takes albedo(m_k); an escaped one collects thr_{k-1} * sky.
+__device__ __forceinline__ bool pray_write(const CArgs &ca, const ClosestScene &s, const BRay &r) {
+    const PArgs &pa = ca.p;
+    const bool stopped = r.w.bi != kNoHit;
+    float t = FLT_MAX, u = 0.0f, v = 0.0f;
+    uint32_t prim = kNoHit;
+    float4 acc = ca.acc3[r.i];
+    const float4 thr = ca.thr3[r.i];
+    if (stopped) {
+        (void)dev::mt_tuv(s.tris + 9ull * r.w.bi, r.o, r.w.d, t, u, v);
+        prim = pa.tri_idx[r.w.bi];
+        pa.rec_out[r.i] = make_uint4(__float_as_uint(r.o[0] + t * r.w.d[0]), __float_as_uint(r.o[1] + t * r.w.d[1]),
+                                     __float_as_uint(r.o[2] + t * r.w.d[2]), r.w.bi);
+        const uint32_t m = ca.ids ? ca.ids[prim] : 0u;
+        const float4 al = ca.pal[2 * m], em = ca.pal[2 * m + 1];
+        acc = make_float4(acc.x + thr.x * em.x, acc.y + thr.y * em.y, acc.z + thr.z * em.z, 0.0f);
+        ca.thr3[r.i] = make_float4(thr.x * al.x, thr.y * al.y, thr.z * al.z, 0.0f);
+    } else {
+        acc = make_float4(acc.x + thr.x * ca.sky[0], acc.y + thr.y * ca.sky[1], acc.z + thr.z * ca.sky[2], 0.0f);
+    }
+    ca.acc3[r.i] = acc;
+    if (pa.bounce) pa.bounce[r.i] = make_uint4(__float_as_uint(t), __float_as_uint(u), __float_as_uint(v), prim);
+    return stopped;
+}
+
 // A level's bounce walk, k_bounce's shape: persistent one-wave blocks; work
 // item = a sample of the level before's live list, taken from the global
 // cursor; a lane whose walk has ended takes the next item while its wave-mates
 // keep walking.  The lanes whose walks ended in one round write together, so
 // that the stopped ones take consecutive slots of the level's live list with
 // one atomic (wave_append needs the whole wave).
-template <int LDS>
-__global__ void __launch_bounds__(kDT) k_path_bounce(const PArgs pa) {
+// The walk is shared with the colour paths (k_path_rgb_bounce, section 4.5.8):
+// X is PArgs or CArgs, which differ in what the end of a walk writes.
+template <int LDS, class X>
+__device__ __forceinline__ void path_bounce_body(const X &x) {
+    const PArgs &pa = path_args(x);
     __shared__ uint32_t s_node[LDS * kDT];
     __shared__ float s_min[LDS * kDT];
     __shared__ float s_max[LDS * kDT];
@@ -791,12 +841,22 @@ __global__ void __launch_bounds__(kDT) k_path_bounce(const PArgs pa) {
             if (fin) has = false;
         }
         if (__ballot(fin)) {
-            const bool stopped = fin && pray_write(pa, sc, r);
+            const bool stopped = fin && pray_write(x, sc, r);
             const uint32_t j = wave_append(stopped, pa.n_live_out);
             if (stopped) pa.live_out[j] = r.i;
         }
         if (!__ballot(has) && !more) break;
     }
+}
+
+template <int LDS>
+__global__ void __launch_bounds__(kDT) k_path_bounce(const PArgs pa) {
+    path_bounce_body<LDS>(pa);
+}
+
+template <int LDS>
+__global__ void __launch_bounds__(kDT) k_path_rgb_bounce(const CArgs ca) {
+    path_bounce_body<LDS>(ca);
 }
 
 // A level's setup over its live samples: the facing mask at {P_k, n_k}; the
@@ -875,6 +935,64 @@ __global__ void __launch_bounds__(kDSetupT) k_path_fill(uint4 *bounces, unsigned
     if (i >= n) return;
     if (bounces) bounces[i] = make_uint4(__float_as_uint(FLT_MAX), 0u, 0u, kNoHit);
     if (lits) lits[i] = 0ull;
+}
+
+// Level 0 of a colour path over its live samples, behind k_path_setup0 (whose
+// records hold the sorted position): acc = emission(m_0), thr_0 = albedo(m_0).
+// A missed primary sample has no record here: k_path_rgb_resolve takes it as 0.
+__global__ void __launch_bounds__(kDSetupT) k_path_rgb_setup0(const CArgs ca) {
+    const PArgs &pa = ca.p;
+    const uint32_t n = *pa.n_live;
+    for (uint32_t j = blockIdx.x * kDSetupT + threadIdx.x; j < n; j += gridDim.x * kDSetupT) {
+        const uint32_t i = pa.live[j];
+        const uint32_t m = ca.ids ? ca.ids[pa.tri_idx[pa.a.d.rec[i].w]] : 0u;
+        ca.thr3[i] = ca.pal[2 * m];
+        ca.acc3[i] = ca.pal[2 * m + 1];
+    }
+}
+
+// k_path_accum per channel: acc[c] += thr_k[c] * e_k.
+__global__ void __launch_bounds__(kDSetupT) k_path_rgb_accum(const CArgs ca) {
+    __shared__ DLight s_light[kMaxLights];
+    const PArgs &pa = ca.p;
+    const DArgs &a = pa.a.d;
+    if (threadIdx.x < a.n_lights) s_light[threadIdx.x] = a.lights[threadIdx.x];
+    __syncthreads();
+    const uint32_t n = *pa.n_live;
+    for (uint32_t j = blockIdx.x * kDSetupT + threadIdx.x; j < n; j += gridDim.x * kDSetupT) {
+        const uint32_t i = pa.live[j];
+        uint32_t s;
+        const uint32_t gp = sample_pixel(a, i, &s);
+        const float e = sample_sum<kArea>(a, &pa.a, s_light, a.rec + i, a.rec[i].w, a.lit[i], gp, s);
+        const float4 acc = ca.acc3[i], thr = ca.thr3[i];
+        ca.acc3[i] = make_float4(acc.x + thr.x * e, acc.y + thr.y * e, acc.z + thr.z * e, 0.0f);
+    }
+}
+
+// Per pixel: E[c] over the samples' sums in the header's order, and the shade.
+__global__ void __launch_bounds__(kDSetupT) k_path_rgb_resolve(const CArgs ca) {
+    const PArgs &pa = ca.p;
+    const DArgs &a = pa.a.d;
+    const uint64_t P = (uint64_t)a.nrows * a.w;
+    const uint64_t lp = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
+    if (lp >= P) return;
+    float E[3] = {0.0f, 0.0f, 0.0f};
+    bool any = false;
+    for (uint32_t s = 0; s < a.spp; ++s) {
+        const uint64_t i = lp * a.spp + s;
+        const bool hit = pa.hit0[i] != 0;
+        any = any || hit;
+        const float4 q = hit ? ca.acc3[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const float e[3] = {q.x, q.y, q.z};
+        for (int c = 0; c < 3; ++c) E[c] = s == 0 ? e[c] : E[c] + e[c];
+    }
+    uint32_t px = 0;
+    for (int c = 0; c < 3; ++c) {
+        E[c] = E[c] / (float)a.spp;
+        if (ca.radiance) ca.radiance[3 * lp + c] = E[c];
+        px |= (uint32_t)(int)fmaxf(0.0f, fminf(255.0f, 255.0f * E[c])) << (8 * c);
+    }
+    if (a.rgba) a.rgba[lp] = any ? px : kMissShade;
 }
 
 // The argument block of a call: the frame, the tree, the lights in slot order
@@ -1058,16 +1176,28 @@ int launch_indirect(const DeviceTree &t, const RenderArgs &ra, const IndirectPla
 // ended, in stream order, before level k+1's bounce overwrites level k-1's
 // records and list, which nothing reads after level k's bounce.  The shadow
 // list (list, face, count, cursor) is free again after each level's shadow pass.
-int launch_path(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l, float albedo, float sky,
-                uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream) {
+//
+// c (a colour call, else null): the walk's and the sum's colour kernels take the
+// places of the grey ones, k_path_rgb_setup0 follows level 0's setup, and the
+// resolve is the colour one; every other launch is the grey call's.
+static int launch_path_levels(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l,
+                              float albedo, float sky, uint32_t n_bounces, const Scratch &s, const WorkArea &wa,
+                              void *stream, const PathRgb *c) {
     const hipStream_t st = (hipStream_t)stream;
     if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0) return 0;
     if (l.n_lights > kMaxLights || l.n_dir > l.n_lights) return (int)hipErrorInvalidValue;
     if (l.area.n > kMaxAreaLights || l.area.n > l.n_lights - l.n_dir) return (int)hipErrorInvalidValue;
     if (n_bounces == 0 || n_bounces > kMaxBounces) return (int)hipErrorInvalidValue;
-    static_assert(sizeof(PArgs) <= 4096, "kernel arguments");
-    PArgs pa;
+    static_assert(sizeof(CArgs) <= 4096, "kernel arguments");
+    CArgs ca;
+    PArgs &pa = ca.p;
     fill_args(pa.a, t, ra, l, p, s, wa);
+    ca.acc3 = c ? reinterpret_cast<float4 *>(c->acc3) : nullptr;
+    ca.thr3 = c ? reinterpret_cast<float4 *>(c->thr3) : nullptr;
+    ca.pal = c ? reinterpret_cast<const float4 *>(c->palette) : nullptr;
+    ca.ids = c ? c->ids : nullptr;
+    ca.radiance = c ? c->radiance : nullptr;
+    for (int k = 0; k < 3; ++k) ca.sky[k] = c ? c->sky[k] : 0.0f;
     uint4 *const recs[2] = {reinterpret_cast<uint4 *>(s.rec), reinterpret_cast<uint4 *>(s.rec2)};
     uint32_t *const lists[2] = {s.blist, s.blist2};
     uint32_t *const counts[2] = {wa.word(kCurBounce), wa.word(kCurBounce2)};
@@ -1098,7 +1228,13 @@ int launch_path(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, 
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_path_setup0, sgrid, dim3(kDSetupT), 0, st, pa);
     e = hipGetLastError();
-    float thr = 1.0f;   // thr_k
+    if (c && e == hipSuccess) {
+        pa.live = lists[0];
+        pa.n_live = counts[0];
+        hipLaunchKernelGGL(k_path_rgb_setup0, lgrid, dim3(kDSetupT), 0, st, ca);
+        e = hipGetLastError();
+    }
+    float thr = 1.0f;   // thr_k (the grey call's)
     for (uint32_t k = 0;; ++k) {
         // level k's shadow pass and sum over its live samples (pa.a.d.rec, lit: the level's)
         pa.live = lists[k & 1];
@@ -1106,7 +1242,8 @@ int launch_path(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, 
         pa.thr = thr;
         if (e == hipSuccess && l.n_lights) e = launch_shadow(pa.a, l.area.n, n, wa.lds_slots, wa.max_blocks, st);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k_path_accum, lgrid, dim3(kDSetupT), 0, st, pa);
+        if (c) hipLaunchKernelGGL(k_path_rgb_accum, lgrid, dim3(kDSetupT), 0, st, ca);
+        else hipLaunchKernelGGL(k_path_accum, lgrid, dim3(kDSetupT), 0, st, pa);
         e = hipGetLastError();
         if (k == n_bounces) break;
         // level k+1: the walk from level k's records into the other buffer, then its setup
@@ -1121,7 +1258,10 @@ int launch_path(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, 
         {
             const uint64_t need = (n + kDT - 1) / kDT;
             const dim3 grid((uint32_t)(need < wa.max_blocks ? need : wa.max_blocks)), block(kDT);
-            if (wa.lds_slots == (uint32_t)kTraceLdsTest) hipLaunchKernelGGL((k_path_bounce<kTraceLdsTest>), grid, block, 0, st, pa);
+            const bool small = wa.lds_slots == (uint32_t)kTraceLdsTest;
+            if (c && small) hipLaunchKernelGGL((k_path_rgb_bounce<kTraceLdsTest>), grid, block, 0, st, ca);
+            else if (c) hipLaunchKernelGGL((k_path_rgb_bounce<kTraceLds>), grid, block, 0, st, ca);
+            else if (small) hipLaunchKernelGGL((k_path_bounce<kTraceLdsTest>), grid, block, 0, st, pa);
             else hipLaunchKernelGGL((k_path_bounce<kTraceLds>), grid, block, 0, st, pa);
             e = hipGetLastError();
         }
@@ -1136,12 +1276,24 @@ int launch_path(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, 
         e = hipGetLastError();
     }
     if (e != hipSuccess) return (int)e;
-    if (p.irradiance || p.rgba) {
+    if (c ? (c->radiance || p.rgba) : (p.irradiance || p.rgba)) {
         const dim3 rgrid((uint32_t)((P + kDSetupT - 1) / kDSetupT));
-        hipLaunchKernelGGL(k_path_resolve, rgrid, dim3(kDSetupT), 0, st, pa);
+        if (c) hipLaunchKernelGGL(k_path_rgb_resolve, rgrid, dim3(kDSetupT), 0, st, ca);
+        else hipLaunchKernelGGL(k_path_resolve, rgrid, dim3(kDSetupT), 0, st, pa);
         e = hipGetLastError();
     }
     return (int)e;
+}
+
+int launch_path(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l, float albedo, float sky,
+                uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream) {
+    return launch_path_levels(t, ra, p, l, albedo, sky, n_bounces, s, wa, stream, nullptr);
+}
+
+int launch_path_rgb(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l, const PathRgb &c,
+                    uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream) {
+    if (!c.palette || !c.acc3 || !c.thr3) return (int)hipErrorInvalidValue;
+    return launch_path_levels(t, ra, p, l, 1.0f, 0.0f, n_bounces, s, wa, stream, &c);
 }
 
 }  // namespace bih

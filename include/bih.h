@@ -40,7 +40,9 @@ extern "C" {
                                (4, added since: bih_trace*, bih_render_gbuffer*, BIH_PARAM_GBUFFER_MASK,
                                 bih_render_direct*, BIH_QUERY_T_HI and bih_ray.t_hi, bih_render_lights*,
                                 bih_render_area_lights*, bih_area_light_sample, bih_render_indirect*,
-                                bih_bounce_sample, bih_render_path*, bih_path_sample, BIH_MAX_BOUNCES) */
+                                bih_bounce_sample, bih_render_path*, bih_path_sample, BIH_MAX_BOUNCES,
+                                bih_tree_set_materials, bih_material, BIH_MAX_MATERIALS,
+                                bih_render_path_rgb*, bih_path_rgb) */
 
 /* error codes */
 #define BIH_OK               0
@@ -805,6 +807,95 @@ int bih_render_path(const bih_tree *tree, const bih_camera *camera, uint32_t w, 
  * spp, level == 0 or level > BIH_MAX_BOUNCES -> BIH_ERR_INVALID. */
 int bih_path_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s,
                     uint32_t level, const float n[3], float d[3]);
+
+/* Colour paths: bih_render_path with a material per triangle -- a diffuse
+ * reflectance and an emitted radiance, R G B -- and an RGB sky (DESIGN.md
+ * section 4.5.8).  Surfaces have a colour, lamps glow, light that bounces off a
+ * red wall is red.  Lights stay scalar (white).  No new walk rule.
+ *
+ * Materials belong to the tree.  bih_tree_set_materials copies a palette of
+ * n_materials records and, per triangle in FILE order (bih_hit.prim's index),
+ * the index of its material; tri_material == NULL: every triangle uses
+ * material 0.  Both are host memory, copied by the call, which is synchronous
+ * and orders after the tree's work in flight: renders issued after it see the
+ * new set.  A second call replaces the first; n_materials == 0 (materials and
+ * tri_material NULL) removes the tree's materials.  Ids are by file position:
+ * they stay valid across bih_rebuild (which keeps n_tris), also the rebuild of a
+ * bih_build_device tree whose soup changed.  The device copies are counted in
+ * bih_tree_info.device_bytes and device_allocs.  Non-finite and negative
+ * values are legal: the arithmetic below decides the result.
+ * Errors, in this order: tree NULL; n_materials > BIH_MAX_MATERIALS;
+ * (materials == NULL) != (n_materials == 0); n_materials == 0 with tri_material
+ * != NULL; an id >= n_materials among the tree's n_tris entries -- all
+ * BIH_ERR_INVALID, and the tree's earlier materials stay unchanged.
+ *
+ * bih_render_path_rgb*.  Any plane may be NULL (not written); all five NULL ->
+ * BIH_ERR_INVALID.  P, i, and the level-major `bounces` and `lits` as bih_path.
+ * Semantics.  Every f32 operation is one separately rounded IEEE operation; c is
+ * a channel 0..2; m_k = tri_material[prim_k] of level k's hit (prim in file
+ * order, bih_hit's; 0 with a NULL tri_material).
+ *  - Paths: levels, rays, hash slots, bounce records, lit words and the
+ *    per-level sums e_k are exactly bih_render_path's.  Materials and sky never
+ *    steer a path: lit, bounces and lits are byte-identical to bih_render_path's
+ *    for the same light set and n_bounces, whatever the materials and sky hold.
+ *  - A hit at level 0: acc[c] = emission(m_0)[c]; thr_0[c] = albedo(m_0)[c];
+ *    acc[c] = acc[c] + thr_0[c] * e_0.
+ *  - A hit at level k >= 1, in this order:
+ *      acc[c] = acc[c] + thr_{k-1}[c] * emission(m_k)[c]
+ *      thr_k[c] = thr_{k-1}[c] * albedo(m_k)[c]
+ *      acc[c] = acc[c] + thr_k[c] * e_k
+ *  - An escape at level k: acc[c] = acc[c] + thr_{k-1}[c] * sky[c]; the path ends.
+ *  - A hit at level n_bounces ends the path after its three steps.
+ *  - A missed primary sample: acc = (0, 0, 0).
+ *  - Pixel: E[c] = (((acc_0[c] + acc_1[c]) + ..) + acc_{spp-1}[c]) / (float)spp,
+ *    written to radiance[3p + c].
+ *  - rgba: g_c = (int)fmaxf(0, fminf(255, 255.0f * E[c])) (NaN gives 255); the
+ *    pixel is g_0 | g_1 << 8 | g_2 << 16.  A pixel none of whose samples hit
+ *    gets bih_render_direct's miss shade 0x00281414.
+ * Emission is collected wherever a path lands, with no weighting against the
+ * light set: a lamp modelled both as emissive triangles and as an area light
+ * counts twice at levels >= 1.  Use one or the other for bounce light.  An
+ * accepted triangle faces the ray (one-sided triangles), so emission is
+ * one-sided as well.
+ * Identity: with the one material {albedo (1,1,1), emission (0,0,0)} and sky =
+ * (s,s,s) every channel of radiance is byte-identical to bih_render_path's
+ * irradiance with bounce = {1.0f, s}, and rgba equals its rgba (1.0f * x is x,
+ * x + 0.0f is x for the values that occur, e_k and acc start from +0).
+ * Errors: bih_render_path's, in its order, with sky == NULL in the place of
+ * bounce == NULL; then n_bounces == 0 or > BIH_MAX_BOUNCES; the alignment
+ * checks are lit and lits (8 bytes) and bounces (16 bytes), radiance needs 4
+ * bytes only -- all BIH_ERR_INVALID.  nrows == 0 -> BIH_OK, nothing launched,
+ * the tree never dereferenced.  After that, the first check that touches the
+ * tree: a tree without materials -> BIH_ERR_INVALID.
+ * RNG accounting, ordering (the ev_trace chain, rebuilds), memory and the
+ * asynchrony of the device entry are bih_render_path's.  Scratch: next to
+ * bih_render_path's per sample 32 bytes more, two 16-byte records {R, G, B, -}
+ * (the RGB sum and the RGB throughput, in place of the scalar sum, which stays
+ * allocated and unused).  All of it is counted in bih_tree_info.device_bytes.
+ * After the first call of a shape, light set, choice of planes and n_bounces
+ * further calls allocate nothing. */
+#define BIH_MAX_MATERIALS 65536
+typedef struct bih_material {
+    float albedo[3];   float reserved0;    /* diffuse reflectance, R G B */
+    float emission[3]; float reserved1;    /* emitted radiance,   R G B */
+} bih_material;                                                     /* 32 B */
+int bih_tree_set_materials(bih_tree *tree, const bih_material *materials, uint32_t n_materials,
+                           const uint32_t *tri_material);            /* synchronous, host memory */
+typedef struct bih_path_rgb {
+    uint64_t *lit;         /* as bih_path */
+    bih_hit  *bounces;     /* as bih_path */
+    uint64_t *lits;        /* as bih_path */
+    float    *radiance;    /* f32[3*P], pixel p's R, G, B at 3p, 3p+1, 3p+2 */
+    uint32_t *rgba;        /* u32[P] 0x00BBGGRR */
+} bih_path_rgb;
+int bih_render_path_rgb_device(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                               uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                               const bih_light_set *lights, const float sky[3], uint32_t n_bounces,
+                               const bih_path_rgb *d_planes, void *stream);  /* async; bih_sync waits */
+int bih_render_path_rgb(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                        uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                        const bih_light_set *lights, const float sky[3], uint32_t n_bounces,
+                        const bih_path_rgb *host_planes);                    /* synchronous, host memory */
 
 /* The drop-in host loop (bih_render into a caller's framebuffer) ends in a
  * device-to-host copy of w*h*4 bytes.  Into pageable memory the runtime
