@@ -22,7 +22,7 @@ from . import scenes  # noqa: F401
 from ._lib import (PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_ITEM_TILES, PARAM_PAIR_CAP, PARAM_STATIC_SOUP,
                    PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS, PARAM_GBUFFER_MASK,
                    AREA_LIGHT_DTYPE, MAX_AREA_LIGHTS, AreaLight, LightSet, BOUNCE_SLOT, Bounce, Indirect,
-                   MAX_BOUNCES, Path, MATERIAL_DTYPE, MAX_MATERIALS, Material, PathRgb,
+                   MAX_BOUNCES, Path, MATERIAL_DTYPE, MAX_MATERIALS, Material, PathRgb, MAT_DIFFUSE, MAT_MIRROR,
                    NO_HIT, LIGHT_DTYPE, POINT_LIGHT_DTYPE, MAX_LIGHTS, SHADOW_T_LO, QUERY_CLOSEST, QUERY_OCCLUDED,
                    QUERY_T_HI, QUERY_CLOSEST_WITHIN, QUERY_OCCLUDED_WITHIN, PointLight, Direct, GBuffer, Hit, Light, Ray, TRAVERSE_ANYHIT,
                    TRAVERSE_REFERENCE, BihError, Camera, Framebuffer, Rows, Scene, TreeInfo, check, load)
@@ -133,12 +133,16 @@ def pack_area_lights(lights) -> np.ndarray:
 
 def pack_materials(materials) -> np.ndarray:
     """(k,) MATERIAL_DTYPE array (bih_material records) of such an array or of
-    (k, 6) rows {albedo R G B, emission R G B}."""
+    (k, 6) rows {albedo R G B, emission R G B}, or (k, 7) rows with the kind
+    (MAT_DIFFUSE, MAT_MIRROR) as the seventh value."""
     a = np.asarray(materials)
     if a.dtype != MATERIAL_DTYPE:
-        rows = np.ascontiguousarray(a, np.float32).reshape(-1, 6)
+        rows = np.ascontiguousarray(a, np.float32)
+        rows = rows.reshape(-1, 7 if rows.ndim == 2 and rows.shape[1] == 7 else 6)
         a = np.zeros(rows.shape[0], MATERIAL_DTYPE)
         a["albedo"], a["emission"] = rows[:, 0:3], rows[:, 3:6]
+        if rows.shape[1] == 7:
+            a["kind"] = rows[:, 6].astype(np.uint32)
     return np.ascontiguousarray(a).reshape(-1)
 
 
@@ -229,7 +233,8 @@ class GPUArrayManager:
 
     def set_materials(self, materials, tri_material=None):
         """bih_tree_set_materials (synchronous; host arrays, copied): the tree's
-        palette -- MATERIAL_DTYPE records or (k, 6) rows {albedo, emission} -- and
+        palette -- MATERIAL_DTYPE records or (k, 6) rows {albedo, emission} (or (k, 7)
+        with the kind, which render_path_spec alone honours) -- and
         per triangle in file order the index of its material (None: every
         triangle uses material 0).  materials None or empty: the tree's
         materials are removed.  Ids stay valid across rebuild()."""
@@ -676,6 +681,42 @@ class Renderer:
               "bih_render_path_rgb_device")
         del keep
 
+    def render_path_spec(self, dir_lights, point_lights, area_lights, sky, n_bounces: int, frame: int | None = None,
+                         rows: Rows | None = None, planes=PATH_RGB) -> dict:
+        """render_path_rgb honouring the materials' kinds: a path that lands on a
+        MAT_MIRROR material goes on along the reflection and gathers no light
+        there (bih_render_path_spec; synchronous).  The planes are
+        render_path_rgb's."""
+        f = self.frame if frame is None else frame
+        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
+        nrows = rows.nrows if rows is not None else self.h
+        S = nrows * self.w * self.spp
+        out, pp = {}, PathRgb()
+        for name in planes:
+            dt, k = PATH_RGB_PLANES[name]
+            shape = ((nrows, self.w) if k == 1 else (nrows, self.w, k)) if k > 0 else ((n_bounces, S) if k < 0 else S)
+            out[name] = np.zeros(shape, dt)
+            setattr(pp, name, out[name].ctypes.data)
+        check(load().bih_render_path_spec(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
+                                          self.seed, _rows_ref(rows), C.byref(ls), self._sky3(sky), n_bounces,
+                                          C.byref(pp)),
+              "bih_render_path_spec")
+        del keep
+        self.frame = f + 1
+        return out
+
+    def render_path_spec_device(self, ptrs: dict, dir_lights, point_lights, area_lights, sky, n_bounces: int,
+                                frame: int, rows: Rows | None = None, stream: int | None = None):
+        """Asynchronous render_path_spec into device memory
+        (bih_render_path_spec_device), as render_path_rgb_device."""
+        pp = _device_planes(PathRgb(), PATH_RGB_PLANES, ptrs)
+        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
+        check(load().bih_render_path_spec_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
+                                                 frame, self.seed, _rows_ref(rows), C.byref(ls), self._sky3(sky),
+                                                 n_bounces, C.byref(pp), C.c_void_p(stream or 0)),
+              "bih_render_path_spec_device")
+        del keep
+
     def whitted_work(self) -> dict:
         """Per bounce d = 0..8 of the last Whitted render (run with
         PARAM_WHITTED_COUNTERS on): rays traced, BIH nodes entered, triangles
@@ -777,4 +818,5 @@ __all__ = ["GPUArrayManager", "Renderer", "Model", "load_obj", "host_register", 
            "pack_point_lights", "AreaLight", "LightSet", "AREA_LIGHT_DTYPE", "MAX_AREA_LIGHTS",
            "pack_area_lights", "area_light_sample", "Bounce", "Indirect", "INDIRECT", "INDIRECT_PLANES",
            "BOUNCE_SLOT", "bounce_sample", "Path", "PATH", "PATH_PLANES", "MAX_BOUNCES", "path_sample",
-           "MATERIAL_DTYPE", "Material", "PathRgb", "PATH_RGB", "PATH_RGB_PLANES", "MAX_MATERIALS", "pack_materials"]
+           "MATERIAL_DTYPE", "Material", "PathRgb", "PATH_RGB", "PATH_RGB_PLANES", "MAX_MATERIALS", "pack_materials",
+           "MAT_DIFFUSE", "MAT_MIRROR"]

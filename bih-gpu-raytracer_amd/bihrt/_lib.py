@@ -41,8 +41,12 @@ SHADOW_T_LO = 1e-4        # BIH_SHADOW_T_LO
 BOUNCE_SLOT = 0x80000000  # BIH_BOUNCE_SLOT: the hash slot of the bounce direction
 MAX_BOUNCES = 8           # BIH_MAX_BOUNCES: levels of a path (bih_render_path*)
 MAX_MATERIALS = 65536     # BIH_MAX_MATERIALS: records of a tree's palette (bih_tree_set_materials)
-MATERIAL_DTYPE = np.dtype([("albedo", np.float32, 3), ("reserved0", np.float32),       # numpy view of a
-                           ("emission", np.float32, 3), ("reserved1", np.float32)])    # bih_material array
+MAT_DIFFUSE = 0           # BIH_MAT_DIFFUSE: a Lambertian surface (the bits of reserved0 = +0.0)
+MAT_MIRROR = 1            # BIH_MAT_MIRROR: a mirror tinted by albedo (bih_render_path_spec*)
+# numpy view of a bih_material array; "kind" (uint32) overlaps "reserved0": one word, two names
+MATERIAL_DTYPE = np.dtype({"names": ["albedo", "reserved0", "emission", "reserved1", "kind"],
+                           "formats": [(np.float32, 3), np.float32, (np.float32, 3), np.float32, np.uint32],
+                           "offsets": [0, 12, 16, 28, 12], "itemsize": 32})
 MAX_AREA_LIGHTS = 16      # bih_render_area_lights*: area lights of one call
 AREA_LIGHT_DTYPE = np.dtype([("corner", np.float32, 3), ("weight", np.float32),       # numpy view of a
                              ("edge_u", np.float32, 3), ("reserved0", np.float32),    # bih_area_light array
@@ -158,9 +162,15 @@ class Path(C.Structure):
                 ("rgba", C.c_void_p)]
 
 
+class _MaterialWord(C.Union):
+    _fields_ = [("reserved0", C.c_float), ("kind", C.c_uint32)]
+
+
 class Material(C.Structure):
-    """bih_material: diffuse reflectance and emitted radiance, R G B (32 bytes)."""
-    _fields_ = [("albedo", C.c_float * 3), ("reserved0", C.c_float), ("emission", C.c_float * 3),
+    """bih_material: diffuse reflectance and emitted radiance, R G B, and the
+    kind (MAT_*; one word with reserved0) (32 bytes)."""
+    _anonymous_ = ("word",)
+    _fields_ = [("albedo", C.c_float * 3), ("word", _MaterialWord), ("emission", C.c_float * 3),
                 ("reserved1", C.c_float)]
 
 
@@ -281,6 +291,8 @@ def load():
                                              C.POINTER(LightSet), C.POINTER(C.c_float), u32, C.POINTER(PathRgb), vp]
     L.bih_render_path_rgb.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, u32, u64, C.POINTER(Rows),
                                       C.POINTER(LightSet), C.POINTER(C.c_float), u32, C.POINTER(PathRgb)]
+    L.bih_render_path_spec_device.argtypes = L.bih_render_path_rgb_device.argtypes
+    L.bih_render_path_spec.argtypes = L.bih_render_path_rgb.argtypes
     for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
@@ -291,7 +303,8 @@ def load():
                  "bih_render_lights_device", "bih_render_lights", "bih_render_area_lights_device",
                  "bih_render_area_lights", "bih_area_light_sample", "bih_render_indirect_device",
                  "bih_render_indirect", "bih_bounce_sample", "bih_render_path_device", "bih_render_path",
-                 "bih_path_sample", "bih_tree_set_materials", "bih_render_path_rgb_device", "bih_render_path_rgb"):
+                 "bih_path_sample", "bih_tree_set_materials", "bih_render_path_rgb_device", "bih_render_path_rgb",
+                 "bih_render_path_spec_device", "bih_render_path_spec"):
         getattr(L, name).restype = i32
     _lib = L
     return L

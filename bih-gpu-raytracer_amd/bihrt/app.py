@@ -21,6 +21,7 @@ usage:  python -m bihrt --mesh sponza --resources path/to/resources --frames 10 
                      [--bounce ALBEDO[,SKY]]          (one bounce of indirect light and a sky term; alone: sky only)
                      [--bounces N]                    (with --bounce: paths of N = 1..8 bounces)
                      [--colour]                       (with --bounces, --scene cornell: its materials, RGB)
+                     [--mirror]                       (with --colour: the back wall and the tall block are mirrors)
         python -m bihrt --obj file.obj ...     (explicit path)
         python -m bihrt --scene cornell|torus|soup[:N] ...   (built-in scenes)
 """
@@ -78,7 +79,7 @@ class App:
 
     def run(self, frames: int, out_pattern: str | None = None, rebuild: bool = True,
             every: int = 1, gbuffer_pattern: str | None = None, direct_pattern: str | None = None,
-            lights=None, lamps=None, panels=None, bounce=None, bounces=None, materials=None):
+            lights=None, lamps=None, panels=None, bounce=None, bounces=None, materials=None, mirror=False):
         """App::Run for a fixed number of frames: Renderer::Render each frame
         (BIH rebuild + render), optional PPM output; returns the frames.
         gbuffer_pattern: one .npz of the frame's G-buffer planes
@@ -93,7 +94,8 @@ class App:
         paths of that many bounces (Renderer.render_path).  materials: with
         bounces, a (palette, tri_material) pair: colour paths under a sky
         (s, s, s), s = bounce's sky (Renderer.render_path_rgb); bounce's albedo
-        is not used."""
+        is not used.  mirror: with materials, their kinds are honoured
+        (Renderer.render_path_spec)."""
         assert self.renderer is not None, "load_models first"
         if materials is not None:
             self.arrays.set_materials(*materials)
@@ -127,8 +129,8 @@ class App:
                 if d:
                     os.makedirs(d, exist_ok=True)
                 if bounce is not None and bounces is not None and materials is not None:
-                    shade = self.renderer.render_path_rgb(lights, lamps, panels, (bounce[1],) * 3, bounces, f,
-                                                          planes=("rgba",))["rgba"]
+                    call = self.renderer.render_path_spec if mirror else self.renderer.render_path_rgb
+                    shade = call(lights, lamps, panels, (bounce[1],) * 3, bounces, f, planes=("rgba",))["rgba"]
                 elif bounce is not None and bounces is not None:
                     shade = self.renderer.render_path(lights, lamps, panels, bounce, bounces, f,
                                                       planes=("rgba",))["rgba"]
@@ -181,6 +183,9 @@ def main(argv=None) -> int:
                          "built-in materials (red and green walls, the lamp quad emissive) under a sky (SKY, SKY, "
                          "SKY); ALBEDO is not used, and there is no light but the lamp's emission unless --sky K, "
                          "--sun, --lamp or --panel add one")
+    ap.add_argument("--mirror", action="store_true",
+                    help="--colour: the back wall and the tall block are mirrors (albedo 0.9), which reflect a path "
+                         "and gather no light themselves")
     ap.add_argument("--every", type=int, default=1, help="write every k-th frame")
     ap.add_argument("--no-rebuild", action="store_true",
                     help="build once (the reference rebuilds every frame)")
@@ -188,6 +193,8 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.colour and a.bounces is None:
         ap.error("--colour belongs to --bounces")
+    if a.mirror and not a.colour:
+        ap.error("--mirror belongs to --colour")
     if a.colour and a.scene != "cornell":
         ap.error("--colour needs a scene with built-in materials (--scene cornell)")
     if a.mesh:
@@ -269,5 +276,6 @@ def main(argv=None) -> int:
     app.load_models(scene)
     app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every, gbuffer_pattern=a.gbuffer,
             direct_pattern=a.direct, lights=lights, lamps=lamps, panels=panels, bounce=bounce,
-            bounces=a.bounces, materials=scenes.cornell_materials() if a.colour else None)
+            bounces=a.bounces, materials=(scenes.cornell_mirror_materials() if a.mirror else scenes.cornell_materials()) if a.colour
+            else None, mirror=a.mirror)
     return 0

@@ -306,3 +306,16 @@ def cornell_materials():
     ids = np.zeros(32, np.uint32)
     ids[6:8], ids[8:10], ids[30:32] = 1, 2, 3
     return pal, ids
+
+
+def cornell_mirror_materials():
+    """cornell_materials() with a fifth material, a mirror (albedo (.9, .9, .9),
+    no emission, bihrt.MAT_MIRROR), on the back wall (triangles 0 and 1) and the
+    tall block (10 .. 19), for Renderer.render_path_spec; (5,)
+    bihrt.MATERIAL_DTYPE and the (32,) uint32 ids."""
+    from . import MAT_MIRROR, MATERIAL_DTYPE, pack_materials
+    base, ids = cornell_materials()
+    pal = np.zeros(5, MATERIAL_DTYPE)       # (np.concatenate would repack the overlapping fields)
+    pal[:4], pal[4:] = base, pack_materials([(0.9, 0.9, 0.9, 0, 0, 0, MAT_MIRROR)])
+    ids[0:2], ids[10:20] = 4, 4
+    return pal, ids

@@ -49,6 +49,7 @@ constexpr size_t kDirectSampleBytes = 16 + 8 + 4;       // dr_mem per sample: re
 constexpr size_t kIndirectSampleBytes = 16 + 4;         // in_mem per sample: bounce record, hit-list entry
 constexpr size_t kPathSampleBytes = 4 + 4 + 1;          // pt_mem per sample: sum, second live-list entry, primary-hit flag
 constexpr size_t kPathRgbSampleBytes = 16 + 16;         // pc_mem per sample: RGB sum record, RGB throughput record
+constexpr size_t kPathSpecSampleBytes = 16;             // ps_mem per sample: {D, kind} of the latest hit
 
 // Per-camera structures (bih_render.hip / bih_bins.hip): primary-ray records,
 // frustum bins and the tile queue of one camera.  A tree keeps kCamSets of
@@ -356,6 +357,12 @@ struct bih_tree {
     bih_material *mt_pal = nullptr;  // the palette; null: the tree has no materials
     uint32_t *mt_ids = nullptr;      // [t.n] material of a file-order triangle; null: material 0
     size_t mt_bytes = 0;             // of both
+    // Mirror path renders (bih_render_path_spec*) are a colour path render with
+    // one more record per sample (ps_mem, next to pc_mem); the host entry
+    // stages through pc_stage.  Same users, same waits.
+    char *ps_mem = nullptr;
+    size_t ps_cap = 0;               // samples (kPathSpecSampleBytes each)
+    bool mt_kinds_ok = true;         // every kind of the palette is BIH_MAT_DIFFUSE or BIH_MAT_MIRROR
 };
 
 namespace {
@@ -854,6 +861,7 @@ void bih_free(bih_tree *tr) {
     if (tr->pt_stage) (void)hipFree(tr->pt_stage);
     if (tr->pc_mem) (void)hipFree(tr->pc_mem);
     if (tr->pc_stage) (void)hipFree(tr->pc_stage);
+    if (tr->ps_mem) (void)hipFree(tr->ps_mem);
     if (tr->mt_pal) (void)hipFree(tr->mt_pal);
     if (tr->mt_ids) (void)hipFree(tr->mt_ids);
     if (tr->ev_trace) (void)hipEventDestroy(tr->ev_trace);
@@ -920,7 +928,8 @@ int bih_tree_get_info(const bih_tree *tr, bih_tree_info *info) {
                          tr->dr_cap * kDirectSampleBytes + tr->dr_lit_cap * 8 + tr->dr_stage_cap +
                          tr->in_cap * kIndirectSampleBytes + tr->in_lit2_cap * 8 + tr->in_stage_cap +
                          tr->pt_cap * kPathSampleBytes + tr->pt_stage_cap +
-                         tr->pc_cap * kPathRgbSampleBytes + tr->pc_stage_cap + tr->mt_bytes;
+                         tr->pc_cap * kPathRgbSampleBytes + tr->pc_stage_cap + tr->mt_bytes +
+                         tr->ps_cap * kPathSpecSampleBytes;
     info->build_ms = tr->build_ms;
     info->device_allocs = tr->allocs + tr->t.allocs + tr->back[0].allocs + tr->back[1].allocs;
     return BIH_OK;
@@ -2325,6 +2334,8 @@ struct DirectJob {
     uint32_t n_bounces = 0;
     // bih_render_path_rgb*: rgb set (with n_bounces; bounce is unused, planes.irradiance null)
     bool rgb = false;
+    // bih_render_path_spec*: spec set (with rgb)
+    bool spec = false;
     float sky[3] = {0.0f, 0.0f, 0.0f};
     float *radiance = nullptr;
 };
@@ -2393,7 +2404,12 @@ static int gbuffer_locked(bih_tree *tr, const Frame &f, const bih_gbuffer &pl, v
                 c.thr3 = tr->pc_mem + 16 * tr->pc_cap;
                 c.radiance = dj->radiance;
                 memcpy(c.sky, dj->sky, sizeof c.sky);
-                rc = bih::launch_path_rgb(tr->t, a, pp, dj->lights, c, dj->n_bounces, sc, wa, st);
+                if (dj->spec) {
+                    c.dk = tr->ps_mem;
+                    rc = bih::launch_path_spec(tr->t, a, pp, dj->lights, c, dj->n_bounces, sc, wa, st);
+                } else {
+                    rc = bih::launch_path_rgb(tr->t, a, pp, dj->lights, c, dj->n_bounces, sc, wa, st);
+                }
             } else {
                 rc = bih::launch_path(tr->t, a, pp, dj->lights, dj->bounce.albedo, dj->bounce.sky, dj->n_bounces, sc,
                                       wa, st);
@@ -2522,7 +2538,8 @@ static int direct_locked(bih_tree *tr, const Frame &f, const DirectJob &dj, void
     const bool own_in = dj.indirect && tr->in_cap < S;
     const bool own_pt = dj.n_bounces && tr->pt_cap < S;
     const bool own_pc = dj.rgb && tr->pc_cap < S;
-    if ((tr->dr_cap < S || own_lit || own_lit2 || own_in || own_pt || own_pc) && tr->trace_used) {
+    const bool own_ps = dj.spec && tr->ps_cap < S;
+    if ((tr->dr_cap < S || own_lit || own_lit2 || own_in || own_pt || own_pc || own_ps) && tr->trace_used) {
         // (the users of both buffers are direct-lighting launches: each ends before its ev_trace record)
         const hipError_t e = hipEventSynchronize(tr->ev_trace);
         if (e != hipSuccess) return map_hip((int)e);
@@ -2533,6 +2550,7 @@ static int direct_locked(bih_tree *tr, const Frame &f, const DirectJob &dj, void
     if (rc == BIH_OK && own_in) rc = grow(tr, &tr->in_mem, &tr->in_cap, S, S * kIndirectSampleBytes);
     if (rc == BIH_OK && own_pt) rc = grow(tr, &tr->pt_mem, &tr->pt_cap, S, S * kPathSampleBytes);
     if (rc == BIH_OK && own_pc) rc = grow(tr, &tr->pc_mem, &tr->pc_cap, S, S * kPathRgbSampleBytes);
+    if (rc == BIH_OK && own_ps) rc = grow(tr, &tr->ps_mem, &tr->ps_cap, S, S * kPathSpecSampleBytes);
     if (rc) return rc;
     bih_gbuffer g = {};
     g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
@@ -2751,12 +2769,17 @@ int bih_tree_set_materials(bih_tree *tr, const bih_material *materials, uint32_t
     tr->mt_pal = pal;
     tr->mt_ids = ids;
     tr->mt_bytes = pal_bytes + ids_bytes;
+    tr->mt_kinds_ok = true;
+    for (uint32_t k = 0; k < n_materials; ++k)
+        if (materials[k].kind != BIH_MAT_DIFFUSE && materials[k].kind != BIH_MAT_MIRROR) tr->mt_kinds_ok = false;
     return BIH_OK;
 }
 
-// The body of the two colour path entries, as render_path.
+// The body of the two colour path entries, as render_path; spec: of the two
+// mirror path entries.
 static int render_path_rgb(const bih_tree *ctr, Frame f, const bih_rows *rows_in, const bih_light_set *ls_in,
-                           const float *sky, uint32_t n_bounces, const bih_path_rgb *planes, void *stream, bool host) {
+                           const float *sky, uint32_t n_bounces, const bih_path_rgb *planes, void *stream, bool host,
+                           bool spec = false) {
     static const bih_light_set no_lights = {nullptr, 0, nullptr, 0, nullptr, 0};
     const bih_light_set *ls = ls_in ? ls_in : &no_lights;
     bih_direct three = {};    // (radiance in the place of irradiance: "all planes NULL" counts it)
@@ -2775,6 +2798,7 @@ static int render_path_rgb(const bih_tree *ctr, Frame f, const bih_rows *rows_in
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
     if (!tr->mt_pal) return BIH_ERR_INVALID;   // no materials: bih_tree_set_materials first
+    if (spec && !tr->mt_kinds_ok) return BIH_ERR_INVALID;
     DirectJob dj;
     merge_light_set(ls, f, &dj.lights);
     dj.planes = bih_direct{planes->lit, nullptr, planes->rgba};
@@ -2784,6 +2808,7 @@ static int render_path_rgb(const bih_tree *ctr, Frame f, const bih_rows *rows_in
     dj.ind.irradiance = nullptr;
     dj.n_bounces = n_bounces;
     dj.rgb = true;
+    dj.spec = spec;
     memcpy(dj.sky, sky, sizeof dj.sky);
     dj.radiance = planes->radiance;
     if (!host) return direct_locked(tr, f, dj, stream);
@@ -2812,6 +2837,20 @@ int bih_render_path_rgb(const bih_tree *tr, const bih_camera *cam, uint32_t w, u
                         const float sky[3], uint32_t n_bounces, const bih_path_rgb *host_planes) {
     return render_path_rgb(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, sky, n_bounces, host_planes, nullptr,
                            true);
+}
+
+int bih_render_path_spec_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                                uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
+                                const float sky[3], uint32_t n_bounces, const bih_path_rgb *d_planes, void *stream) {
+    return render_path_rgb(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, sky, n_bounces, d_planes, stream,
+                           false, true);
+}
+
+int bih_render_path_spec(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                         uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
+                         const float sky[3], uint32_t n_bounces, const bih_path_rgb *host_planes) {
+    return render_path_rgb(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, sky, n_bounces, host_planes, nullptr,
+                           true, true);
 }
 
 int bih_path_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s, uint32_t level,

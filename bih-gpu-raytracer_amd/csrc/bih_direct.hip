@@ -55,6 +55,7 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stddef.h>
+#include <type_traits>
 
 #include "bih_area.h"
 #include "bih_bounce.h"
@@ -680,10 +681,15 @@ struct PArgs {
 };
 
 constexpr uint32_t kPListBlocks = 2048;   // the list-driven kernels' grid cap (they stride)
+constexpr uint32_t kMatMirror = 1u;       // BIH_MAT_MIRROR (bih_render_path_spec*, section 4.5.9)
 
 // Level 0's setup over every sample of the call: k_indirect_setup's, which
 // also starts the sample's sum and notes whether it hit.
-__global__ void __launch_bounds__(kDSetupT) k_path_setup0(const PArgs pa) {
+// Shared with the mirror paths (k_path_spec_setup0, section 4.5.9), which pass
+// their argument block as `sa`: a mirror hit faces no light, and the sample's
+// record of incoming direction and kind starts here.
+template <class S>
+__device__ __forceinline__ void path_setup0_body(const PArgs &pa, const S *sa) {
     const DArgs &a = pa.a.d;
     const uint64_t P = (uint64_t)a.nrows * a.w;
     const uint64_t n = P * a.spp;
@@ -703,7 +709,13 @@ __global__ void __launch_bounds__(kDSetupT) k_path_setup0(const PArgs pa) {
             const float t = __uint_as_float(h.x);
             for (int k = 0; k < 3; ++k) pt[k] = a.cam[k] + t * d[k];
             dev::tri_normal(a.tris + 9ull * bi, nrm);
-            face = facing_mask<kArea>(a, &pa.a, nrm, pt, y * a.w + x, s);
+            if constexpr (std::is_same<S, void>::value) {
+                face = facing_mask<kArea>(a, &pa.a, nrm, pt, y * a.w + x, s);
+            } else {
+                const uint32_t kind = spec_kind(*sa, pa.tri_idx[bi]);
+                if (kind != kMatMirror) face = facing_mask<kArea>(a, &pa.a, nrm, pt, y * a.w + x, s);
+                sa->dk[i] = make_uint4(__float_as_uint(d[0]), __float_as_uint(d[1]), __float_as_uint(d[2]), kind);
+            }
             a.rec[i] = make_uint4(__float_as_uint(pt[0]), __float_as_uint(pt[1]), __float_as_uint(pt[2]), bi);
         }
         a.lit[i] = 0ull;
@@ -717,6 +729,10 @@ __global__ void __launch_bounds__(kDSetupT) k_path_setup0(const PArgs pa) {
         a.list[j] = (uint32_t)i;
         a.face[j] = face;
     }
+}
+
+__global__ void __launch_bounds__(kDSetupT) k_path_setup0(const PArgs pa) {
+    path_setup0_body<void>(pa, nullptr);
 }
 
 // The end of a level's walk for the lane's sample: a stopped ray leaves {P_k,
@@ -762,7 +778,11 @@ __device__ __forceinline__ const PArgs &path_args(const CArgs &ca) { return ca.p
 
 // pray_write for a colour path: a stopped ray collects thr_{k-1} * emission(m_k)
 // and its throughput takes albedo(m_k); an escaped one collects thr_{k-1} * sky.
-__device__ __forceinline__ bool pray_write(const CArgs &ca, const ClosestScene &s, const BRay &r) {
+// dk (mirror paths, section 4.5.9; else null and SPEC false): the sample's
+// record of the ray that found this hit and of the hit's kind, the material's
+// fourth word, which came with its albedo.
+template <bool SPEC>
+__device__ __forceinline__ bool pray_write_rgb(const CArgs &ca, uint4 *dk, const ClosestScene &s, const BRay &r) {
     const PArgs &pa = ca.p;
     const bool stopped = r.w.bi != kNoHit;
     float t = FLT_MAX, u = 0.0f, v = 0.0f;
@@ -778,6 +798,9 @@ __device__ __forceinline__ bool pray_write(const CArgs &ca, const ClosestScene &
         const float4 al = ca.pal[2 * m], em = ca.pal[2 * m + 1];
         acc = make_float4(acc.x + thr.x * em.x, acc.y + thr.y * em.y, acc.z + thr.z * em.z, 0.0f);
         ca.thr3[r.i] = make_float4(thr.x * al.x, thr.y * al.y, thr.z * al.z, 0.0f);
+        if constexpr (SPEC)
+            dk[r.i] = make_uint4(__float_as_uint(r.w.d[0]), __float_as_uint(r.w.d[1]), __float_as_uint(r.w.d[2]),
+                                 __float_as_uint(al.w));
     } else {
         acc = make_float4(acc.x + thr.x * ca.sky[0], acc.y + thr.y * ca.sky[1], acc.z + thr.z * ca.sky[2], 0.0f);
     }
@@ -786,14 +809,66 @@ __device__ __forceinline__ bool pray_write(const CArgs &ca, const ClosestScene &
     return stopped;
 }
 
+__device__ __forceinline__ bool pray_write(const CArgs &ca, const ClosestScene &s, const BRay &r) {
+    return pray_write_rgb<false>(ca, nullptr, s, r);
+}
+
+// ---- Mirror paths (bih_render_path_spec*) ----
+// The colour paths with a material kind that steers: a sample whose latest hit
+// is a mirror goes on along the reflection of the ray that found it, not along
+// the hashed lobe, and no light is gathered there (the setups give it no list
+// entry: its lit word stays 0 and k_path_rgb_accum adds thr * +0).  One 16-byte
+// record per sample, {D, kind} of its latest hit, carries what that takes from
+// the writer of one level (level 0: the setup) to the next level's ray
+// generation and to the level's setup.  The sums are the colour kernels'.
+struct SArgs {
+    CArgs c;
+    uint4 *dk;                  // [P*spp] {D_k.x, D_k.y, D_k.z, kind_k} of the sample's latest hit
+};
+
+__device__ __forceinline__ const PArgs &path_args(const SArgs &sa) { return sa.c.p; }
+
+// kind(m) of the file-order triangle prim.
+__device__ __forceinline__ uint32_t spec_kind(const SArgs &sa, uint32_t prim) {
+    const uint32_t m = sa.c.ids ? sa.c.ids[prim] : 0u;
+    return __float_as_uint(sa.c.pal[2 * m].w);
+}
+
+__device__ __forceinline__ bool pray_write(const SArgs &sa, const ClosestScene &s, const BRay &r) {
+    return pray_write_rgb<true>(sa.c, sa.dk, s, r);
+}
+
+// The direction of the level's ray from the lane's sample i, whose latest hit
+// has the normal nrm: the level's hashed lobe; behind a mirror hit (SArgs
+// only) the reflection of the ray that found it.
+template <class X>
+__device__ __forceinline__ void path_ray_dir(const X &x, const PArgs &pa, uint32_t i, const float *nrm, float *d) {
+    const DArgs &a = pa.a.d;
+    if constexpr (std::is_same<X, SArgs>::value) {
+        const uint4 q = x.dk[i];
+        if (q.w == kMatMirror) {
+            const float D[3] = {__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z)};
+            const float dn = (D[0] * nrm[0] + D[1] * nrm[1]) + D[2] * nrm[2];
+            const float k2 = 2.0f * dn;
+            for (int c = 0; c < 3; ++c) d[c] = D[c] - k2 * nrm[c];
+            return;
+        }
+    }
+    uint32_t s;
+    const uint32_t gp = sample_pixel(a, i, &s);
+    bounce_dir(pa.a.hseed, gp, pa.a.fs0 + s, pa.slot, nrm, d);
+}
+
 // A level's bounce walk, k_bounce's shape: persistent one-wave blocks; work
 // item = a sample of the level before's live list, taken from the global
 // cursor; a lane whose walk has ended takes the next item while its wave-mates
 // keep walking.  The lanes whose walks ended in one round write together, so
 // that the stopped ones take consecutive slots of the level's live list with
 // one atomic (wave_append needs the whole wave).
-// The walk is shared with the colour paths (k_path_rgb_bounce, section 4.5.8):
-// X is PArgs or CArgs, which differ in what the end of a walk writes.
+// The walk is shared with the colour paths (k_path_rgb_bounce, section 4.5.8)
+// and the mirror paths (k_path_spec_bounce, section 4.5.9): X is PArgs, CArgs or
+// SArgs, which differ in what the end of a walk writes, SArgs also in the
+// direction a new ray takes (outside the walk loop).
 template <int LDS, class X>
 __device__ __forceinline__ void path_bounce_body(const X &x) {
     const PArgs &pa = path_args(x);
@@ -827,9 +902,7 @@ __device__ __forceinline__ void path_bounce_body(const X &x) {
                     r.o[0] = __uint_as_float(q.x); r.o[1] = __uint_as_float(q.y); r.o[2] = __uint_as_float(q.z);
                     float nrm[3];
                     dev::tri_normal(a.tris + 9ull * q.w, nrm);
-                    uint32_t s;
-                    const uint32_t gp = sample_pixel(a, r.i, &s);
-                    bounce_dir(pa.a.hseed, gp, pa.a.fs0 + s, pa.slot, nrm, r.w.d);
+                    path_ray_dir(x, pa, r.i, nrm, r.w.d);
                     has = dev::closest_start<dev::kWalkClosest>(sc, r.w, r.o, kShadowTLo);
                     fin = !has;   // missed the box / one-leaf tree: final
                 }
@@ -859,9 +932,22 @@ __global__ void __launch_bounds__(kDT) k_path_rgb_bounce(const CArgs ca) {
     path_bounce_body<LDS>(ca);
 }
 
+template <int LDS>
+__global__ void __launch_bounds__(kDT) k_path_spec_bounce(const SArgs sa) {
+    path_bounce_body<LDS>(sa);
+}
+
+// Level 0's setup of a mirror path: k_path_setup0's, see there.
+__global__ void __launch_bounds__(kDSetupT) k_path_spec_setup0(const SArgs sa) {
+    path_setup0_body(sa.c.p, &sa);
+}
+
 // A level's setup over its live samples: the facing mask at {P_k, n_k}; the
 // samples a light faces go to the shadow list; the level's lit word starts at 0.
-__global__ void __launch_bounds__(kDSetupT) k_path_setup(const PArgs pa) {
+// dk (mirror paths, k_path_spec_setup; else null and SPEC false): a mirror hit
+// faces no light.
+template <bool SPEC>
+__device__ __forceinline__ void path_setup_body(const PArgs &pa, const uint4 *dk) {
     const DArgs &a = pa.a.d;
     const uint32_t n = *pa.n_live;
     // (the trip count is the block's: wave_append needs the whole wave)
@@ -871,7 +957,9 @@ __global__ void __launch_bounds__(kDSetupT) k_path_setup(const PArgs pa) {
         uint32_t i = 0;
         if (j0 < n) {
             i = pa.live[j0];
-            if (a.n_lights) {
+            bool lights = a.n_lights != 0;
+            if constexpr (SPEC) lights = lights && dk[i].w != kMatMirror;
+            if (lights) {
                 const uint4 h = a.rec[i];
                 const float pt[3] = {__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(h.z)};
                 float nrm[3];
@@ -888,6 +976,14 @@ __global__ void __launch_bounds__(kDSetupT) k_path_setup(const PArgs pa) {
             a.face[j] = face;
         }
     }
+}
+
+__global__ void __launch_bounds__(kDSetupT) k_path_setup(const PArgs pa) {
+    path_setup_body<false>(pa, nullptr);
+}
+
+__global__ void __launch_bounds__(kDSetupT) k_path_spec_setup(const SArgs sa) {
+    path_setup_body<true>(sa.c.p, sa.dk);
 }
 
 // A level's sum over its live samples, behind its shadow pass: acc += thr_k * e_k.
@@ -1180,6 +1276,9 @@ int launch_indirect(const DeviceTree &t, const RenderArgs &ra, const IndirectPla
 // c (a colour call, else null): the walk's and the sum's colour kernels take the
 // places of the grey ones, k_path_rgb_setup0 follows level 0's setup, and the
 // resolve is the colour one; every other launch is the grey call's.
+// c->dk (a mirror call, else null): the mirror paths' setups and walk take the
+// places of the grey setups and the colour walk; every other launch is the
+// colour call's.
 static int launch_path_levels(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l,
                               float albedo, float sky, uint32_t n_bounces, const Scratch &s, const WorkArea &wa,
                               void *stream, const PathRgb *c) {
@@ -1188,9 +1287,12 @@ static int launch_path_levels(const DeviceTree &t, const RenderArgs &ra, const P
     if (l.n_lights > kMaxLights || l.n_dir > l.n_lights) return (int)hipErrorInvalidValue;
     if (l.area.n > kMaxAreaLights || l.area.n > l.n_lights - l.n_dir) return (int)hipErrorInvalidValue;
     if (n_bounces == 0 || n_bounces > kMaxBounces) return (int)hipErrorInvalidValue;
-    static_assert(sizeof(CArgs) <= 4096, "kernel arguments");
-    CArgs ca;
+    static_assert(sizeof(SArgs) <= 4096, "kernel arguments");
+    SArgs sa;
+    CArgs &ca = sa.c;
     PArgs &pa = ca.p;
+    sa.dk = c ? reinterpret_cast<uint4 *>(c->dk) : nullptr;
+    const bool spec = sa.dk != nullptr;
     fill_args(pa.a, t, ra, l, p, s, wa);
     ca.acc3 = c ? reinterpret_cast<float4 *>(c->acc3) : nullptr;
     ca.thr3 = c ? reinterpret_cast<float4 *>(c->thr3) : nullptr;
@@ -1226,7 +1328,8 @@ static int launch_path_levels(const DeviceTree &t, const RenderArgs &ra, const P
     if (e == hipSuccess) e = reset_counts(pa.a.d, st);
     if (e == hipSuccess) e = hipMemsetAsync(counts[0], 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_path_setup0, sgrid, dim3(kDSetupT), 0, st, pa);
+    if (spec) hipLaunchKernelGGL(k_path_spec_setup0, sgrid, dim3(kDSetupT), 0, st, sa);
+    else hipLaunchKernelGGL(k_path_setup0, sgrid, dim3(kDSetupT), 0, st, pa);
     e = hipGetLastError();
     if (c && e == hipSuccess) {
         pa.live = lists[0];
@@ -1259,7 +1362,9 @@ static int launch_path_levels(const DeviceTree &t, const RenderArgs &ra, const P
             const uint64_t need = (n + kDT - 1) / kDT;
             const dim3 grid((uint32_t)(need < wa.max_blocks ? need : wa.max_blocks)), block(kDT);
             const bool small = wa.lds_slots == (uint32_t)kTraceLdsTest;
-            if (c && small) hipLaunchKernelGGL((k_path_rgb_bounce<kTraceLdsTest>), grid, block, 0, st, ca);
+            if (spec && small) hipLaunchKernelGGL((k_path_spec_bounce<kTraceLdsTest>), grid, block, 0, st, sa);
+            else if (spec) hipLaunchKernelGGL((k_path_spec_bounce<kTraceLds>), grid, block, 0, st, sa);
+            else if (c && small) hipLaunchKernelGGL((k_path_rgb_bounce<kTraceLdsTest>), grid, block, 0, st, ca);
             else if (c) hipLaunchKernelGGL((k_path_rgb_bounce<kTraceLds>), grid, block, 0, st, ca);
             else if (small) hipLaunchKernelGGL((k_path_bounce<kTraceLdsTest>), grid, block, 0, st, pa);
             else hipLaunchKernelGGL((k_path_bounce<kTraceLds>), grid, block, 0, st, pa);
@@ -1272,7 +1377,8 @@ static int launch_path_levels(const DeviceTree &t, const RenderArgs &ra, const P
         pa.n_live = pa.n_live_out;
         if (e == hipSuccess) e = hipMemsetAsync(pa.a.d.cursor, 0, sizeof(unsigned long long), st);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k_path_setup, lgrid, dim3(kDSetupT), 0, st, pa);
+        if (spec) hipLaunchKernelGGL(k_path_spec_setup, lgrid, dim3(kDSetupT), 0, st, sa);
+        else hipLaunchKernelGGL(k_path_setup, lgrid, dim3(kDSetupT), 0, st, pa);
         e = hipGetLastError();
     }
     if (e != hipSuccess) return (int)e;
@@ -1292,7 +1398,13 @@ int launch_path(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, 
 
 int launch_path_rgb(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l, const PathRgb &c,
                     uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream) {
-    if (!c.palette || !c.acc3 || !c.thr3) return (int)hipErrorInvalidValue;
+    if (!c.palette || !c.acc3 || !c.thr3 || c.dk) return (int)hipErrorInvalidValue;
+    return launch_path_levels(t, ra, p, l, 1.0f, 0.0f, n_bounces, s, wa, stream, &c);
+}
+
+int launch_path_spec(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l, const PathRgb &c,
+                     uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream) {
+    if (!c.palette || !c.acc3 || !c.thr3 || !c.dk) return (int)hipErrorInvalidValue;
     return launch_path_levels(t, ra, p, l, 1.0f, 0.0f, n_bounces, s, wa, stream, &c);
 }
 

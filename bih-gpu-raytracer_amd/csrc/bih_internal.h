@@ -501,16 +501,23 @@ int launch_path(const DeviceTree &t, const RenderArgs &a, const PathPlanes &p, c
 // material per triangle.  palette: two float4 per material (bih_material); ids:
 // u32 per file-order triangle, or null (material 0); acc3, thr3: 16 bytes per
 // sample each; radiance: f32[3P] or null (p.irradiance is not written).
+// Mirror paths (bih_render_path_spec*): launch_path_spec, the same with dk, 16
+// bytes per sample ({D, kind} of the sample's latest hit); the palette's kinds
+// are BIH_MAT_DIFFUSE or BIH_MAT_MIRROR (the caller's check).  launch_path_rgb
+// takes dk == null only and never reads a kind.
 struct PathRgb {
     const void *palette = nullptr;
     const uint32_t *ids = nullptr;
     void *acc3 = nullptr;
     void *thr3 = nullptr;
+    void *dk = nullptr;
     float *radiance = nullptr;
     float sky[3] = {0.0f, 0.0f, 0.0f};
 };
 int launch_path_rgb(const DeviceTree &t, const RenderArgs &a, const PathPlanes &p, const Lights &l, const PathRgb &c,
                     uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream);
+int launch_path_spec(const DeviceTree &t, const RenderArgs &a, const PathPlanes &p, const Lights &l, const PathRgb &c,
+                     uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream);
 int launch_rng_init(uint32_t *rng, uint32_t w, uint32_t row0, uint32_t nrows, uint32_t band_h,
                     uint32_t band_step, uint64_t seed, uint64_t skip, int device, void *stream);
 // dst = src's per-pixel state advanced by `steps` draws (planes of `pixels`; dst may be src)

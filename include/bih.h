@@ -42,7 +42,8 @@ extern "C" {
                                 bih_render_area_lights*, bih_area_light_sample, bih_render_indirect*,
                                 bih_bounce_sample, bih_render_path*, bih_path_sample, BIH_MAX_BOUNCES,
                                 bih_tree_set_materials, bih_material, BIH_MAX_MATERIALS,
-                                bih_render_path_rgb*, bih_path_rgb) */
+                                bih_render_path_rgb*, bih_path_rgb, bih_material.kind, BIH_MAT_DIFFUSE,
+                                BIH_MAT_MIRROR, bih_render_path_spec*) */
 
 /* error codes */
 #define BIH_OK               0
@@ -875,8 +876,22 @@ int bih_path_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp,
  * After the first call of a shape, light set, choice of planes and n_bounces
  * further calls allocate nothing. */
 #define BIH_MAX_MATERIALS 65536
+#define BIH_MAT_DIFFUSE 0u   /* a Lambertian surface: the one kind bih_render_path_rgb* knows */
+#define BIH_MAT_MIRROR  1u   /* a perfect mirror tinted by albedo (bih_render_path_spec* only) */
+/* The fourth word: `reserved0` to bih_render_path_rgb*, which never reads it;
+ * `kind` to bih_render_path_spec* (one member, two names, as bih_ray's last
+ * float).  Positional initialisers written before `kind` existed, such as
+ * {{1, 1, 1}, 0, {0, 0, 0}, 0}, go on meaning what they meant: brace elision
+ * reaches the union's first member.  C compilers that know -Wmissing-braces
+ * (part of -Wall there) warn about exactly that elision, so for C translation
+ * units the header turns that one warning off from here on; define
+ * BIH_KEEP_MISSING_BRACES_WARNING before including it to keep the warning and
+ * write {{1, 1, 1}, {0}, {0, 0, 0}, 0}. */
+#if defined(__GNUC__) && !defined(__cplusplus) && !defined(BIH_KEEP_MISSING_BRACES_WARNING)
+#pragma GCC diagnostic ignored "-Wmissing-braces"
+#endif
 typedef struct bih_material {
-    float albedo[3];   float reserved0;    /* diffuse reflectance, R G B */
+    float albedo[3];   union { float reserved0; uint32_t kind; };  /* BIH_MAT_*; +0.0f's bits are DIFFUSE */
     float emission[3]; float reserved1;    /* emitted radiance,   R G B */
 } bih_material;                                                     /* 32 B */
 int bih_tree_set_materials(bih_tree *tree, const bih_material *materials, uint32_t n_materials,
@@ -896,6 +911,64 @@ int bih_render_path_rgb(const bih_tree *tree, const bih_camera *camera, uint32_t
                         uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
                         const bih_light_set *lights, const float sky[3], uint32_t n_bounces,
                         const bih_path_rgb *host_planes);                    /* synchronous, host memory */
+
+/* Mirror materials: bih_render_path_rgb with a material kind that steers the
+ * path.  A material whose `kind` is BIH_MAT_MIRROR
+ * reflects the ray that found it; BIH_MAT_DIFFUSE (the bits of +0.0f, so every
+ * palette written for bih_render_path_rgb is all diffuse) bounces as before.  A
+ * call of its own: bih_render_path_rgb* goes on ignoring the word.  One-sided
+ * triangles rule out glass; there are no glossy lobes.  No new walk rule.
+ * bih_tree_set_materials accepts what it accepts and notes, on the host,
+ * whether every kind of the palette is BIH_MAT_DIFFUSE or BIH_MAT_MIRROR.
+ *
+ * Planes, P, i, level-major `bounces` and `lits`: bih_path_rgb's.
+ * Semantics, as a delta on bih_render_path_rgb.  Every f32 operation is one
+ * separately rounded IEEE operation.  kind_k = kind(m_k) of a sample alive at
+ * level k (level 0: the primary hit).
+ *  - Incoming direction D_k, the direction of the ray that found level k's hit:
+ *    D_0 is the primary d, bit for bit the G-buffer's; D_k, k >= 1, is the
+ *    direction of level k's ray below.
+ *  - The ray of level k+1 from a sample alive at level k is {o = P_k, t_lo =
+ *    BIH_SHADOW_T_LO, d}.  kind_k == BIH_MAT_DIFFUSE: d = B_{k+1}, exactly
+ *    bih_render_path's, hash slot BIH_BOUNCE_SLOT + k.  kind_k == BIH_MAT_MIRROR:
+ *      dn = (D_k.x*n_k.x + D_k.y*n_k.y) + D_k.z*n_k.z
+ *      k2 = 2.0f*dn
+ *      d[c] = D_k[c] - k2*n_k[c]        (one multiply, one subtract)
+ *    with n_k the `normal` formula's unit normal; the level's hash slot is not
+ *    used (slots are counter-based: nothing shifts).
+ *  - bounces[k*P*spp + i] is the BIH_QUERY_CLOSEST record of that ray, as in
+ *    bih_render_path.  An accepted triangle faces its ray, so dn < 0 in exact
+ *    arithmetic and d leaves the surface; the originating triangle cannot stop
+ *    its own ray, for the reason given for bounce rays.
+ *  - Light at a hit of level k: a diffuse hit has bih_render_path's lit word and
+ *    e_k.  A mirror hit has lit word 0 and e_k = +0.0f; no shadow ray is traced
+ *    for it.  At level 0 too: `lit` is byte-identical to
+ *    bih_render_area_lights' only on samples whose primary hit is diffuse.
+ *  - Sums: exactly bih_render_path_rgb's steps in its order with those e_k --
+ *    the emission of m_k, thr_k = thr_{k-1} * albedo(m_k), acc += thr_k * e_k
+ *    (performed as written at a mirror hit, with e_k = +0: one rule, also for
+ *    -0 and NaN).  A mirror's albedo tints what it reflects.
+ *  - The escape, radiance, rgba, miss shade, ended-path fill and n_bounces
+ *    rules are unchanged.
+ * Identity: with every kind BIH_MAT_DIFFUSE all five planes are byte-identical
+ * to bih_render_path_rgb's.
+ * Errors: bih_render_path_rgb's, in its order; then, right after "a tree
+ * without materials", a palette holding a kind other than BIH_MAT_DIFFUSE and
+ * BIH_MAT_MIRROR -> BIH_ERR_INVALID.  nrows == 0, RNG accounting, ordering (the
+ * ev_trace chain, rebuilds) and the asynchrony of the device entry are
+ * bih_render_path_rgb's.  Scratch: next to bih_render_path_rgb's per sample 16
+ * bytes more, one record {D.x, D.y, D.z, kind} of the sample's latest hit;
+ * counted in bih_tree_info.device_bytes.  The host entry stages through the
+ * colour call's device planes.  After the first call of a shape, light set,
+ * choice of planes and n_bounces further calls allocate nothing. */
+int bih_render_path_spec_device(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                                uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                                const bih_light_set *lights, const float sky[3], uint32_t n_bounces,
+                                const bih_path_rgb *d_planes, void *stream);  /* async; bih_sync waits */
+int bih_render_path_spec(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                         uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
+                         const bih_light_set *lights, const float sky[3], uint32_t n_bounces,
+                         const bih_path_rgb *host_planes);                    /* synchronous, host memory */
 
 /* The drop-in host loop (bih_render into a caller's framebuffer) ends in a
  * device-to-host copy of w*h*4 bytes.  Into pageable memory the runtime
