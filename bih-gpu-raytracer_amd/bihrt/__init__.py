@@ -23,6 +23,8 @@ from ._lib import (PARAM_BINS_CAP, PARAM_FORCE_FALLBACK, PARAM_ITEM_TILES, PARAM
                    PARAM_TEST_ALLOC_FAIL, PARAM_TRACE_LDS_SLOTS, PARAM_WHITTED_COUNTERS, PARAM_GBUFFER_MASK,
                    AREA_LIGHT_DTYPE, MAX_AREA_LIGHTS, AreaLight, LightSet, BOUNCE_SLOT, Bounce, Indirect,
                    MAX_BOUNCES, Path, MATERIAL_DTYPE, MAX_MATERIALS, Material, PathRgb, MAT_DIFFUSE, MAT_MIRROR,
+                   DENOISE_PARAMS, DENOISE_DEFAULTS, DENOISE_MAX_PASSES, DENOISE_MAX_SQUARINGS, DENOISE_MAX_PIXELS,
+                   DenoiseParams,
                    NO_HIT, LIGHT_DTYPE, POINT_LIGHT_DTYPE, MAX_LIGHTS, SHADOW_T_LO, QUERY_CLOSEST, QUERY_OCCLUDED,
                    QUERY_T_HI, QUERY_CLOSEST_WITHIN, QUERY_OCCLUDED_WITHIN, PointLight, Direct, GBuffer, Hit, Light, Ray, TRAVERSE_ANYHIT,
                    TRAVERSE_REFERENCE, BihError, Camera, Framebuffer, Rows, Scene, TreeInfo, check, load)
@@ -85,6 +87,21 @@ PATH = tuple(PATH_PLANES)
 PATH_RGB_PLANES = {"lit": (np.uint64, 0), "bounces": (HIT_DTYPE, -1), "lits": (np.uint64, -1),
                    "radiance": (np.float32, 3), "rgba": (np.uint32, 1)}
 PATH_RGB = tuple(PATH_RGB_PLANES)
+
+
+# the outputs of a denoise call (bih_denoise*): name -> (dtype, values per pixel)
+DENOISE_PLANES = {"radiance": (np.float32, 3), "rgba": (np.uint32, 1)}
+
+
+def denoise_params(params=None) -> DenoiseParams:
+    """A bih_denoise_params from None (DENOISE_DEFAULTS: 3 passes, 5 normal
+    squarings, sigma_colour 2.0, sigma_plane 0.05), a DenoiseParams, or a
+    sequence (passes[, normal_squarings[, sigma_colour[, sigma_plane]]])."""
+    if isinstance(params, DenoiseParams):
+        return params
+    v = list(params) if params is not None else []
+    v += list(DENOISE_DEFAULTS[len(v):])
+    return DenoiseParams(int(v[0]), int(v[1]), float(v[2]), float(v[3]))
 
 
 def _rows_ref(rows: Rows | None):
@@ -717,6 +734,48 @@ class Renderer:
               "bih_render_path_spec_device")
         del keep
 
+    def denoise(self, radiance, depth, normal, params=None, planes=("radiance", "rgba")) -> dict:
+        """The edge-avoiding a-trous filter over a whole frame's host planes
+        (bih_denoise; synchronous): `radiance` (h, w, 3) float32 as
+        render_path_rgb's or render_path_spec's, `depth` (h, w) and `normal`
+        (h, w, 3) as render_gbuffer's under this renderer's camera.  params: see
+        denoise_params (default 3 passes, 5 normal squarings, sigma_colour 2.0,
+        sigma_plane 0.05; sigma_plane is in scene units, the distance of a tap from
+        the centre's tangent plane at which its weight reaches 0).  Returns a
+        dict of the planes asked for (DENOISE_PLANES): "radiance" (h, w, 3)
+        float32, "rgba" (h, w) uint32.  Pixels the G-buffer missed pass through."""
+        prm = denoise_params(params)
+        src = [np.ascontiguousarray(a, np.float32) for a in (radiance, depth, normal)]
+        for a, k in zip(src, (3, 1, 3)):
+            if a.size != self.h * self.w * k:
+                raise ValueError(f"a plane of {a.size} values for a {self.w} x {self.h} frame")
+        out, ptr = {}, {"radiance": None, "rgba": None}
+        for name in planes:
+            dt, k = DENOISE_PLANES[name]
+            out[name] = np.zeros((self.h, self.w) + ((k,) if k > 1 else ()), dt)
+            ptr[name] = out[name].ctypes.data
+        check(load().bih_denoise(self.arrays.handle, C.byref(self.camera), self.w, self.h, C.byref(prm),
+                                 src[0].ctypes.data, src[1].ctypes.data, src[2].ctypes.data, ptr["radiance"],
+                                 ptr["rgba"]), "bih_denoise")
+        return out
+
+    def denoise_device(self, ptrs: dict, radiance_ptr: int, depth_ptr: int, normal_ptr: int, params=None,
+                       stream: int | None = None):
+        """Asynchronous denoise of device planes (bih_denoise_device): ptrs maps
+        "radiance" and "rgba" (DENOISE_PLANES) to the output device pointers, an
+        output left out is not written; ptrs["radiance"] may be radiance_ptr (in
+        place).  The call runs on `stream` and is not ordered after renders on
+        other streams: that is the caller's."""
+        for name in ptrs:
+            if name not in DENOISE_PLANES:
+                raise KeyError(name)
+        prm = denoise_params(params)
+        check(load().bih_denoise_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, C.byref(prm),
+                                        C.c_void_p(radiance_ptr or 0), C.c_void_p(depth_ptr or 0),
+                                        C.c_void_p(normal_ptr or 0), C.c_void_p(ptrs.get("radiance") or 0),
+                                        C.c_void_p(ptrs.get("rgba") or 0), C.c_void_p(stream or 0)),
+              "bih_denoise_device")
+
     def whitted_work(self) -> dict:
         """Per bounce d = 0..8 of the last Whitted render (run with
         PARAM_WHITTED_COUNTERS on): rays traced, BIH nodes entered, triangles
@@ -819,4 +878,5 @@ __all__ = ["GPUArrayManager", "Renderer", "Model", "load_obj", "host_register", 
            "pack_area_lights", "area_light_sample", "Bounce", "Indirect", "INDIRECT", "INDIRECT_PLANES",
            "BOUNCE_SLOT", "bounce_sample", "Path", "PATH", "PATH_PLANES", "MAX_BOUNCES", "path_sample",
            "MATERIAL_DTYPE", "Material", "PathRgb", "PATH_RGB", "PATH_RGB_PLANES", "MAX_MATERIALS", "pack_materials",
-           "MAT_DIFFUSE", "MAT_MIRROR"]
+           "MAT_DIFFUSE", "MAT_MIRROR", "DENOISE_PARAMS", "DenoiseParams", "DENOISE_DEFAULTS", "DENOISE_PLANES",
+           "DENOISE_MAX_PASSES", "DENOISE_MAX_SQUARINGS", "DENOISE_MAX_PIXELS", "denoise_params"]

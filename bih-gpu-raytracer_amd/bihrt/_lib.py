@@ -47,6 +47,9 @@ MAT_MIRROR = 1            # BIH_MAT_MIRROR: a mirror tinted by albedo (bih_rende
 MATERIAL_DTYPE = np.dtype({"names": ["albedo", "reserved0", "emission", "reserved1", "kind"],
                            "formats": [(np.float32, 3), np.float32, (np.float32, 3), np.float32, np.uint32],
                            "offsets": [0, 12, 16, 28, 12], "itemsize": 32})
+DENOISE_MAX_PASSES = 8        # BIH_DENOISE_MAX_PASSES
+DENOISE_MAX_SQUARINGS = 8     # BIH_DENOISE_MAX_SQUARINGS
+DENOISE_MAX_PIXELS = 1 << 28  # BIH_DENOISE_MAX_PIXELS
 MAX_AREA_LIGHTS = 16      # bih_render_area_lights*: area lights of one call
 AREA_LIGHT_DTYPE = np.dtype([("corner", np.float32, 3), ("weight", np.float32),       # numpy view of a
                              ("edge_u", np.float32, 3), ("reserved0", np.float32),    # bih_area_light array
@@ -181,6 +184,18 @@ class PathRgb(C.Structure):
                 ("rgba", C.c_void_p)]
 
 
+class DenoiseParams(C.Structure):
+    """bih_denoise_params (16 bytes): passes 1..8 (pass i uses step 1 << i),
+    normal_squarings 0..8, sigma_colour (pass 0's colour support; halves every
+    pass), sigma_plane (scene units: distance from the centre's tangent plane)."""
+    _fields_ = [("passes", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_colour", C.c_float),
+                ("sigma_plane", C.c_float)]
+
+
+DENOISE_PARAMS = DenoiseParams          # the ctypes mirror of bih_denoise_params
+DENOISE_DEFAULTS = (3, 5, 2.0, 0.05)    # passes, normal_squarings, sigma_colour, sigma_plane
+
+
 class BinsStats(C.Structure):
     _fields_ = [("usable", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
                 ("list_entries", C.c_uint64), ("global_entries", C.c_uint32)]
@@ -293,6 +308,8 @@ def load():
                                       C.POINTER(LightSet), C.POINTER(C.c_float), u32, C.POINTER(PathRgb)]
     L.bih_render_path_spec_device.argtypes = L.bih_render_path_rgb_device.argtypes
     L.bih_render_path_spec.argtypes = L.bih_render_path_rgb.argtypes
+    L.bih_denoise_device.argtypes = [vp, C.POINTER(Camera), u32, u32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp]
+    L.bih_denoise.argtypes = [vp, C.POINTER(Camera), u32, u32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp]
     for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
@@ -304,7 +321,7 @@ def load():
                  "bih_render_area_lights", "bih_area_light_sample", "bih_render_indirect_device",
                  "bih_render_indirect", "bih_bounce_sample", "bih_render_path_device", "bih_render_path",
                  "bih_path_sample", "bih_tree_set_materials", "bih_render_path_rgb_device", "bih_render_path_rgb",
-                 "bih_render_path_spec_device", "bih_render_path_spec"):
+                 "bih_render_path_spec_device", "bih_render_path_spec", "bih_denoise_device", "bih_denoise"):
         getattr(L, name).restype = i32
     _lib = L
     return L

@@ -22,6 +22,7 @@ usage:  python -m bihrt --mesh sponza --resources path/to/resources --frames 10 
                      [--bounces N]                    (with --bounce: paths of N = 1..8 bounces)
                      [--colour]                       (with --bounces, --scene cornell: its materials, RGB)
                      [--mirror]                       (with --colour: the back wall and the tall block are mirrors)
+                     [--denoise [PASSES[,SC[,SP]]]]   (with --colour: the PPM is the a-trous filtered frame)
         python -m bihrt --obj file.obj ...     (explicit path)
         python -m bihrt --scene cornell|torus|soup[:N] ...   (built-in scenes)
 """
@@ -34,7 +35,7 @@ import time
 
 import numpy as np
 
-from . import (MAX_BOUNCES, RAYS_PER_PIXEL, SCREEN_HEIGHT, SCREEN_WIDTH, SEED, GPUArrayManager, Renderer,
+from . import (DENOISE_DEFAULTS, DENOISE_MAX_PASSES, MAX_BOUNCES, RAYS_PER_PIXEL, SCREEN_HEIGHT, SCREEN_WIDTH, SEED, GPUArrayManager, Renderer,
                load_obj, scenes, write_ppm)
 
 
@@ -79,7 +80,8 @@ class App:
 
     def run(self, frames: int, out_pattern: str | None = None, rebuild: bool = True,
             every: int = 1, gbuffer_pattern: str | None = None, direct_pattern: str | None = None,
-            lights=None, lamps=None, panels=None, bounce=None, bounces=None, materials=None, mirror=False):
+            lights=None, lamps=None, panels=None, bounce=None, bounces=None, materials=None, mirror=False,
+            denoise=None):
         """App::Run for a fixed number of frames: Renderer::Render each frame
         (BIH rebuild + render), optional PPM output; returns the frames.
         gbuffer_pattern: one .npz of the frame's G-buffer planes
@@ -95,7 +97,9 @@ class App:
         bounces, a (palette, tri_material) pair: colour paths under a sky
         (s, s, s), s = bounce's sky (Renderer.render_path_rgb); bounce's albedo
         is not used.  mirror: with materials, their kinds are honoured
-        (Renderer.render_path_spec)."""
+        (Renderer.render_path_spec).  denoise: with materials, the params of
+        Renderer.denoise: the PPM is the rgba of the frame's radiance filtered
+        under render_gbuffer's depth and normal."""
         assert self.renderer is not None, "load_models first"
         if materials is not None:
             self.arrays.set_materials(*materials)
@@ -130,7 +134,12 @@ class App:
                     os.makedirs(d, exist_ok=True)
                 if bounce is not None and bounces is not None and materials is not None:
                     call = self.renderer.render_path_spec if mirror else self.renderer.render_path_rgb
-                    shade = call(lights, lamps, panels, (bounce[1],) * 3, bounces, f, planes=("rgba",))["rgba"]
+                    if denoise is not None:
+                        rad = call(lights, lamps, panels, (bounce[1],) * 3, bounces, f, planes=("radiance",))["radiance"]
+                        gb = self.renderer.render_gbuffer(f, planes=("depth", "normal"))
+                        shade = self.renderer.denoise(rad, gb["depth"], gb["normal"], denoise, planes=("rgba",))["rgba"]
+                    else:
+                        shade = call(lights, lamps, panels, (bounce[1],) * 3, bounces, f, planes=("rgba",))["rgba"]
                 elif bounce is not None and bounces is not None:
                     shade = self.renderer.render_path(lights, lamps, panels, bounce, bounces, f,
                                                       planes=("rgba",))["rgba"]
@@ -186,6 +195,11 @@ def main(argv=None) -> int:
     ap.add_argument("--mirror", action="store_true",
                     help="--colour: the back wall and the tall block are mirrors (albedo 0.9), which reflect a path "
                          "and gather no light themselves")
+    ap.add_argument("--denoise", nargs="?", const="", default=None, metavar="PASSES[,SC[,SP]]",
+                    help="--colour: the --direct PPM is the frame's radiance after the edge-avoiding a-trous filter "
+                         "(PASSES 1..%d passes, default %d; colour support SC, default %g; tangent-plane support SP "
+                         "in scene units, default %g), guided by the frame's G-buffer depth and normal"
+                         % ((DENOISE_MAX_PASSES,) + DENOISE_DEFAULTS[:1] + DENOISE_DEFAULTS[2:]))
     ap.add_argument("--every", type=int, default=1, help="write every k-th frame")
     ap.add_argument("--no-rebuild", action="store_true",
                     help="build once (the reference rebuilds every frame)")
@@ -195,6 +209,18 @@ def main(argv=None) -> int:
         ap.error("--colour belongs to --bounces")
     if a.mirror and not a.colour:
         ap.error("--mirror belongs to --colour")
+    denoise = None
+    if a.denoise is not None:
+        if not a.colour:
+            ap.error("--denoise belongs to --colour")
+        try:
+            v = [float(x) for x in a.denoise.split(",")] if a.denoise else []
+        except ValueError:
+            v = None
+        if v is None or len(v) > 3 or (v and not (v[0] == int(v[0]) and 1 <= v[0] <= DENOISE_MAX_PASSES)):
+            ap.error("--denoise takes [PASSES[,SC[,SP]]], PASSES = 1..%d" % DENOISE_MAX_PASSES)
+        denoise = (int(v[0]) if v else DENOISE_DEFAULTS[0], DENOISE_DEFAULTS[1],
+                   v[1] if len(v) > 1 else DENOISE_DEFAULTS[2], v[2] if len(v) > 2 else DENOISE_DEFAULTS[3])
     if a.colour and a.scene != "cornell":
         ap.error("--colour needs a scene with built-in materials (--scene cornell)")
     if a.mesh:
@@ -277,5 +303,5 @@ def main(argv=None) -> int:
     app.run(a.frames, a.out, rebuild=not a.no_rebuild, every=a.every, gbuffer_pattern=a.gbuffer,
             direct_pattern=a.direct, lights=lights, lamps=lamps, panels=panels, bounce=bounce,
             bounces=a.bounces, materials=(scenes.cornell_mirror_materials() if a.mirror else scenes.cornell_materials()) if a.colour
-            else None, mirror=a.mirror)
+            else None, mirror=a.mirror, denoise=denoise)
     return 0

@@ -363,6 +363,17 @@ struct bih_tree {
     char *ps_mem = nullptr;
     size_t ps_cap = 0;               // samples (kPathSpecSampleBytes each)
     bool mt_kinds_ok = true;         // every kind of the palette is BIH_MAT_DIFFUSE or BIH_MAT_MIRROR
+    // Denoise calls (bih_denoise.hip) read no tree buffer and no RNG state and
+    // take no render slot: nothing above orders against them.  Their record
+    // planes are shared, so a denoise orders after the one before it
+    // (ev_denoise, an event of its own: a denoise may overlap the next frame's
+    // walks, which chain on ev_trace); the host entry's device planes.
+    char *dn_mem = nullptr;
+    size_t dn_cap = 0;               // pixels (kDenoisePixelBytes each)
+    hipEvent_t ev_denoise = nullptr; // after the last denoise; the first one creates it
+    bool denoise_used = false;
+    char *dn_stage = nullptr;
+    size_t dn_stage_cap = 0;         // bytes
 };
 
 namespace {
@@ -821,6 +832,7 @@ void bih_free(bih_tree *tr) {
     for (CamSet &c : tr->cs)
         if (c.bins_pending) (void)hipEventSynchronize(c.ev_bins);
     if (tr->trace_used) (void)hipEventSynchronize(tr->ev_trace);
+    if (tr->denoise_used) (void)hipEventSynchronize(tr->ev_denoise);
     if (tr->bstream) (void)hipStreamSynchronize(tr->bstream);
     bih::free_tree_device(tr->t);
     bih::free_tree_device(tr->back[0]);   // (the soup is freed by whichever buffer owns it)
@@ -862,9 +874,12 @@ void bih_free(bih_tree *tr) {
     if (tr->pc_mem) (void)hipFree(tr->pc_mem);
     if (tr->pc_stage) (void)hipFree(tr->pc_stage);
     if (tr->ps_mem) (void)hipFree(tr->ps_mem);
+    if (tr->dn_mem) (void)hipFree(tr->dn_mem);
+    if (tr->dn_stage) (void)hipFree(tr->dn_stage);
     if (tr->mt_pal) (void)hipFree(tr->mt_pal);
     if (tr->mt_ids) (void)hipFree(tr->mt_ids);
     if (tr->ev_trace) (void)hipEventDestroy(tr->ev_trace);
+    if (tr->ev_denoise) (void)hipEventDestroy(tr->ev_denoise);
     for (int k = 0; k < kSlots; ++k) {
         if (tr->ev0[k]) (void)hipEventDestroy(tr->ev0[k]);
         if (tr->evd[k]) (void)hipEventDestroy(tr->evd[k]);
@@ -929,7 +944,8 @@ int bih_tree_get_info(const bih_tree *tr, bih_tree_info *info) {
                          tr->in_cap * kIndirectSampleBytes + tr->in_lit2_cap * 8 + tr->in_stage_cap +
                          tr->pt_cap * kPathSampleBytes + tr->pt_stage_cap +
                          tr->pc_cap * kPathRgbSampleBytes + tr->pc_stage_cap + tr->mt_bytes +
-                         tr->ps_cap * kPathSpecSampleBytes;
+                         tr->ps_cap * kPathSpecSampleBytes +
+                         tr->dn_cap * bih::kDenoisePixelBytes + tr->dn_stage_cap;
     info->build_ms = tr->build_ms;
     info->device_allocs = tr->allocs + tr->t.allocs + tr->back[0].allocs + tr->back[1].allocs;
     return BIH_OK;
@@ -2851,6 +2867,106 @@ int bih_render_path_spec(const bih_tree *tr, const bih_camera *cam, uint32_t w, 
                          const float sky[3], uint32_t n_bounces, const bih_path_rgb *host_planes) {
     return render_path_rgb(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, sky, n_bounces, host_planes, nullptr,
                            true, true);
+}
+
+// Argument checks of both denoise entries, in the header's order; none
+// touches the tree or a device.
+static int denoise_check(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h,
+                         const bih_denoise_params *prm, const float *radiance, const float *depth,
+                         const float *normal, const float *radiance_out, const uint32_t *rgba_out) {
+    if (!tr || !cam || !prm) return BIH_ERR_INVALID;
+    if (w == 0 || h == 0) return BIH_ERR_INVALID;
+    if (prm->passes == 0 || prm->passes > BIH_DENOISE_MAX_PASSES) return BIH_ERR_INVALID;
+    if (prm->normal_squarings > BIH_DENOISE_MAX_SQUARINGS) return BIH_ERR_INVALID;
+    if ((uint64_t)w * h > BIH_DENOISE_MAX_PIXELS) return BIH_ERR_TOO_LARGE;
+    if (!radiance || !depth || !normal) return BIH_ERR_INVALID;
+    if (!radiance_out && !rgba_out) return BIH_ERR_INVALID;
+    return BIH_OK;
+}
+
+// bih_denoise_device under the tree's lock, arguments checked.
+static int denoise_locked(bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h,
+                          const bih_denoise_params *prm, const float *d_radiance, const float *d_depth,
+                          const float *d_normal, float *d_radiance_out, uint32_t *d_rgba_out, hipStream_t st) {
+    static_assert(BIH_DENOISE_MAX_PASSES == bih::kDenoiseMaxPasses, "BIH_DENOISE_MAX_PASSES / kDenoiseMaxPasses");
+    const size_t P = (size_t)w * h;
+    // (a tree that never denoises creates, waits for and frees nothing of this call's)
+    if (!tr->ev_denoise) {
+        const hipError_t e = hipEventCreateWithFlags(&tr->ev_denoise, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            tr->ev_denoise = nullptr;
+            return map_hip((int)e);
+        }
+    }
+    if (tr->dn_cap < P && tr->denoise_used) {
+        // (the record planes' only users are denoise launches: each ends before its ev_denoise record)
+        const hipError_t e = hipEventSynchronize(tr->ev_denoise);
+        if (e != hipSuccess) return map_hip((int)e);
+    }
+    int rc = grow(tr, &tr->dn_mem, &tr->dn_cap, P, P * bih::kDenoisePixelBytes);
+    if (rc) return rc;
+    // the record planes are shared: after the denoise before this one
+    if (tr->denoise_used && hipEventQuery(tr->ev_denoise) != hipSuccess) {
+        rc = map_hip((int)hipStreamWaitEvent(st, tr->ev_denoise, 0));
+        if (rc) return rc;
+    }
+    bih::DenoiseArgs a;
+    memcpy(a.cam, cam, sizeof a.cam);
+    a.w = w;
+    a.h = h;
+    a.passes = prm->passes;
+    a.squarings = prm->normal_squarings;
+    a.sigma_colour = prm->sigma_colour;
+    a.sigma_plane = prm->sigma_plane;
+    a.radiance = d_radiance;
+    a.depth = d_depth;
+    a.normal = d_normal;
+    a.radiance_out = d_radiance_out;
+    a.rgba_out = d_rgba_out;
+    rc = map_hip(bih::launch_denoise(a, tr->dn_mem, st));
+    // (a failed launch may have left work on st that uses the planes: the event covers it)
+    const hipError_t e = hipEventRecord(tr->ev_denoise, st);
+    if (e == hipSuccess) tr->denoise_used = true;
+    if (rc) return rc;
+    return map_hip((int)e);
+}
+
+int bih_denoise_device(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h,
+                       const bih_denoise_params *prm, const float *d_radiance, const float *d_depth,
+                       const float *d_normal, float *d_radiance_out, uint32_t *d_rgba_out, void *stream) {
+    const int rc = denoise_check(ctr, cam, w, h, prm, d_radiance, d_depth, d_normal, d_radiance_out, d_rgba_out);
+    if (rc) return rc;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    return denoise_locked(tr, cam, w, h, prm, d_radiance, d_depth, d_normal, d_radiance_out, d_rgba_out,
+                          stream ? (hipStream_t)stream : tr->stream);
+}
+
+int bih_denoise(const bih_tree *ctr, const bih_camera *cam, uint32_t w, uint32_t h, const bih_denoise_params *prm,
+                const float *radiance, const float *depth, const float *normal, float *radiance_out,
+                uint32_t *rgba_out) {
+    int rc = denoise_check(ctr, cam, w, h, prm, radiance, depth, normal, radiance_out, rgba_out);
+    if (rc) return rc;
+    bih_tree *tr = const_cast<bih_tree *>(ctr);
+    DeviceGuard g(tr->t.device);
+    std::lock_guard<std::mutex> lk(tr->mu);
+    // the three inputs go up (regions 0..2), the outputs asked for come back (3, 4)
+    const size_t P = (size_t)w * h;
+    Stage<5> sg{{const_cast<float *>(radiance), const_cast<float *>(depth), const_cast<float *>(normal), radiance_out,
+                 rgba_out},
+                {P * 12, P * 4, P * 12, P * 12, P * 4}};
+    rc = sg.place(tr, &tr->dn_stage, &tr->dn_stage_cap);
+    if (rc) return rc;
+    for (int k = 0; k < 3; ++k) {
+        const hipError_t e = hipMemcpyAsync(sg.dev(k), sg.host[k], sg.size[k], hipMemcpyHostToDevice, tr->stream);
+        if (e != hipSuccess) return map_hip((int)e);
+    }
+    return sg.finish(tr,
+                     denoise_locked(tr, cam, w, h, prm, static_cast<float *>(sg.dev(0)),
+                                    static_cast<float *>(sg.dev(1)), static_cast<float *>(sg.dev(2)),
+                                    static_cast<float *>(sg.dev(3)), static_cast<uint32_t *>(sg.dev(4)), tr->stream),
+                     3);
 }
 
 int bih_path_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s, uint32_t level,

@@ -518,6 +518,24 @@ int launch_path_rgb(const DeviceTree &t, const RenderArgs &a, const PathPlanes &
                     uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream);
 int launch_path_spec(const DeviceTree &t, const RenderArgs &a, const PathPlanes &p, const Lights &l, const PathRgb &c,
                      uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream);
+// Denoiser (bih_denoise.hip; bih_denoise*): the edge-avoiding a-trous filter of
+// a whole w x h frame.  scratch: kDenoisePixelBytes per pixel, four planes of
+// 16-byte records -- {Pos, valid}, {n, 0} and two colour records (pass i reads
+// plane i & 1 and writes the other; pass 0 reads k_denoise_setup's copy, so
+// radiance_out may be radiance).  The last pass writes radiance_out and
+// rgba_out (either may be null) and no record.
+constexpr size_t kDenoisePixelBytes = 64;
+constexpr uint32_t kDenoiseMaxPasses = 8;      // BIH_DENOISE_MAX_PASSES
+struct DenoiseArgs {
+    float cam[12];              // origin, lower_left, horizontal, vertical
+    uint32_t w, h;
+    uint32_t passes, squarings;
+    float sigma_colour, sigma_plane;
+    const float *radiance, *depth, *normal;
+    float *radiance_out;
+    uint32_t *rgba_out;
+};
+int launch_denoise(const DenoiseArgs &a, void *scratch, void *stream);
 int launch_rng_init(uint32_t *rng, uint32_t w, uint32_t row0, uint32_t nrows, uint32_t band_h,
                     uint32_t band_step, uint64_t seed, uint64_t skip, int device, void *stream);
 // dst = src's per-pixel state advanced by `steps` draws (planes of `pixels`; dst may be src)

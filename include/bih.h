@@ -43,7 +43,8 @@ extern "C" {
                                 bih_bounce_sample, bih_render_path*, bih_path_sample, BIH_MAX_BOUNCES,
                                 bih_tree_set_materials, bih_material, BIH_MAX_MATERIALS,
                                 bih_render_path_rgb*, bih_path_rgb, bih_material.kind, BIH_MAT_DIFFUSE,
-                                BIH_MAT_MIRROR, bih_render_path_spec*) */
+                                BIH_MAT_MIRROR, bih_render_path_spec*, bih_denoise*, bih_denoise_params,
+                                BIH_DENOISE_MAX_PASSES, BIH_DENOISE_MAX_SQUARINGS, BIH_DENOISE_MAX_PIXELS) */
 
 /* error codes */
 #define BIH_OK               0
@@ -969,6 +970,96 @@ int bih_render_path_spec(const bih_tree *tree, const bih_camera *camera, uint32_
                          uint32_t spp, uint32_t frame, uint64_t seed, const bih_rows *rows,
                          const bih_light_set *lights, const float sky[3], uint32_t n_bounces,
                          const bih_path_rgb *host_planes);                    /* synchronous, host memory */
+
+/* Denoiser: the edge-avoiding a-trous wavelet filter (Dammertz et al. 2010; the
+ * spatial filter of SVGF) over a colour render's `radiance`, guided by the
+ * G-buffer's `depth` and `normal`.  A few passes of
+ * a 5 x 5 B3-spline stencil with holes; each tap is weighted by how well its
+ * normal, its position on the centre's tangent plane and its colour agree with
+ * the centre's.  An image filter: it walks no tree and draws no random number.
+ *
+ * The frame is always whole: P = w*h pixels, pixel p = y*w + x, row 0 at the
+ * bottom (a frame rendered in bands is denoised after it is assembled).
+ * radiance: f32[3P], bih_path_rgb.radiance's layout; depth: f32[P] and normal:
+ * f32[3P], bih_gbuffer's planes; `camera`: the camera they were rendered under.
+ * Either output may be NULL (not written): radiance_out f32[3P], rgba_out
+ * u32[P].  radiance_out may equal radiance exactly (in place); any other
+ * overlap of an output with an input or with the other output is undefined.
+ *
+ * Semantics.  Every f32 operation is one separately rounded IEEE operation;
+ * dots are (x+y)+z; fmaxf returns the non-NaN operand; a is an axis and c a
+ * channel, 0..2.
+ *  - Pixel p is valid exactly when depth[p] < FLT_MAX (one f32 compare): the
+ *    G-buffer's miss value, inf and NaN are all invalid.
+ *  - An invalid pixel's radiance passes through every pass unchanged, it never
+ *    contributes to another pixel, and its rgba_out is the miss shade 0x00281414.
+ *  - Position of a valid pixel (x, y), the G-buffer's ray formula at the pixel
+ *    centre: u = ((float)x + 0.5f) / (float)w; v = ((float)y + 0.5f) / (float)h;
+ *    d[a] = ((lower_left[a] + u*horizontal[a]) + v*vertical[a]) - origin[a];
+ *    Pos[a] = origin[a] + depth*d[a].
+ *  - Pass i = 0 .. passes-1 has the step s = 1 << i, the input C_i (C_0 = the
+ *    caller's radiance) and the output C_{i+1}.
+ *  - A valid pixel p = (x, y) visits its taps with dy = -2..2 as the outer and
+ *    dx = -2..2 as the inner loop, both ascending: q = (x + dx*s, y + dy*s).  A
+ *    tap outside the image or on an invalid pixel is skipped.
+ *      k = K[|dx|] * K[|dy|], K = {0.375f, 0.25f, 0.0625f} (exact).
+ *    The centre tap (dx = dy = 0) has the weight w = k.  Any other tap:
+ *      dn = n_p . n_q; m = fmaxf(0.0f, dn); m = m*m, normal_squarings times; wn = m
+ *      e[a] = Pos_q[a] - Pos_p[a]; pd = n_p . e; wp = g(fabsf(pd) / sigma_plane)
+ *      dc[c] = C_i[q][c] - C_i[p][c]; d2 = (dc0*dc0 + dc1*dc1) + dc2*dc2
+ *      sc = sigma_colour * 2^-i (an exact scaling); wc = g(d2 / (sc*sc))
+ *      g(x) = t*t with t = fmaxf(0.0f, 1.0f - x)
+ *      w = ((k * wn) * wp) * wc
+ *    (g has compact support: no expf, which differs between host and device,
+ *    and an edge stops the filter hard.)  A tap contributes exactly when
+ *    w > 0.0f: sum[c] = sum[c] + w * C_i[q][c] (a multiply, then an add), wsum =
+ *    wsum + w, both from +0.0f.  C_{i+1}[p][c] = sum[c] / wsum.
+ *  - radiance_out = C_passes.  rgba_out follows bih_render_path_rgb's rgba rule
+ *    on C_passes for valid pixels.
+ * Non-finite values are legal and decided by the arithmetic above.  A NaN or
+ * inf colour gets the weight 0 at every other pixel through g, so a firefly
+ * never spreads, and the pixel keeps its own non-finite value (the centre tap:
+ * (k*C)/k).  Non-finite guides are decided likewise: a NaN anywhere in a tap's
+ * terms gives it the weight 0, while +inf in a normal can give a tap the weight
+ * +inf and the pixels whose stencil reaches it NaN (inf/inf).  sigma_colour = +inf or sigma_plane = +inf switches that term off
+ * (g(0) = 1); a sigma of 0 leaves the centre tap alone.  sigma_plane is in scene
+ * units.
+ * Errors, checked in this order before a device is touched: NULL tree, camera
+ * or params -> BIH_ERR_INVALID; w or h == 0 -> BIH_ERR_INVALID; passes == 0 or
+ * > BIH_DENOISE_MAX_PASSES -> BIH_ERR_INVALID; normal_squarings >
+ * BIH_DENOISE_MAX_SQUARINGS -> BIH_ERR_INVALID; w*h > BIH_DENOISE_MAX_PIXELS ->
+ * BIH_ERR_TOO_LARGE; radiance, depth or normal NULL -> BIH_ERR_INVALID; both
+ * outputs NULL -> BIH_ERR_INVALID.
+ * Ordering: the call reads nothing of the tree's geometry and no RNG state, so
+ * builds, rebuilds, renders and traces are not ordered against it.  It runs on
+ * `stream` (NULL: the tree's); the caller orders it after the renders that
+ * wrote its inputs, by using the same stream or events of its own.  Two denoise
+ * calls of one tree order after each other, whatever their streams, through an
+ * event of their own -- not the ray queries': a denoise may overlap the next
+ * frame's walks.  bih_free waits for it.
+ * Memory: the tree owns the scratch, 64 bytes per pixel -- a position record
+ * {Pos, valid}, a normal record and two ping-pong colour records of 16 bytes
+ * each (pass 0 reads a copy, so in place is safe) -- counted in
+ * bih_tree_info.device_bytes and device_allocs; after the first call of a
+ * shape further calls allocate nothing.  The host entry stages its five planes
+ * through device planes of the tree's, counted likewise. */
+#define BIH_DENOISE_MAX_PASSES 8
+#define BIH_DENOISE_MAX_SQUARINGS 8
+#define BIH_DENOISE_MAX_PIXELS (1u << 28)
+typedef struct bih_denoise_params {
+    uint32_t passes;            /* 1..8; pass i = 0.. uses step 1<<i            */
+    uint32_t normal_squarings;  /* 0..8; normal weight = max(0, n.n')^(2^this)  */
+    float    sigma_colour;      /* colour support of pass 0; halves every pass  */
+    float    sigma_plane;       /* scene units: distance from the centre's tangent plane */
+} bih_denoise_params;
+int bih_denoise_device(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                       const bih_denoise_params *params,
+                       const float *d_radiance, const float *d_depth, const float *d_normal,
+                       float *d_radiance_out, uint32_t *d_rgba_out, void *stream);  /* async; bih_sync waits */
+int bih_denoise(const bih_tree *tree, const bih_camera *camera, uint32_t w, uint32_t h,
+                const bih_denoise_params *params,
+                const float *radiance, const float *depth, const float *normal,
+                float *radiance_out, uint32_t *rgba_out);                           /* synchronous, host memory */
 
 /* The drop-in host loop (bih_render into a caller's framebuffer) ends in a
  * device-to-host copy of w*h*4 bytes.  Into pageable memory the runtime
