@@ -240,6 +240,7 @@ def load():
     L.bih_strerror.restype = C.c_char_p
     L.bih_camera_reference.argtypes = [u32, u32, C.POINTER(Camera)]
     L.bih_camera_ray_bound.argtypes = [C.POINTER(Camera), C.POINTER(C.c_float)]
+    L.bih_pixel_divide.argtypes = [u32, vp, C.c_size_t, vp, C.POINTER(u32)]
     L.bih_scene_load_obj.argtypes = [C.c_char_p, C.POINTER(Scene), C.POINTER(u32)]
     L.bih_scene_free.argtypes = [C.POINTER(Scene)]
     L.bih_scene_free.restype = None
@@ -310,7 +311,7 @@ def load():
     L.bih_render_path_spec.argtypes = L.bih_render_path_rgb.argtypes
     L.bih_denoise_device.argtypes = [vp, C.POINTER(Camera), u32, u32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp]
     L.bih_denoise.argtypes = [vp, C.POINTER(Camera), u32, u32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp]
-    for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
+    for name in ("bih_camera_reference", "bih_camera_ray_bound", "bih_pixel_divide", "bih_scene_load_obj", "bih_build", "bih_build_device", "bih_rebuild",
                  "bih_tree_get_info", "bih_tree_export", "bih_render", "bih_render_rows",
                  "bih_render_device", "bih_sync", "bih_last_render_ms", "bih_last_render_times", "bih_set_timing",
                  "bih_render_whitted_device", "bih_render_whitted", "bih_render_device_frames",

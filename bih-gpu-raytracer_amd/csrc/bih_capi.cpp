@@ -28,6 +28,7 @@
 #include "bih_area.h"
 #include "bih_bounce.h"
 #include "bih_internal.h"
+#include "bih_pixdiv.h"
 
 // Up to kSlots renders through one tree may be in flight together (issued
 // on as many streams): each launch takes one of kSlots {tile queue, spill
@@ -759,6 +760,16 @@ int bih_camera_ray_bound(const bih_camera *cam, float dmax[3]) {
                            std::fabs(cam->vertical[c])) + std::fabs(cam->origin[c]);
         dmax[c] = (mx * 1.001f + 1e-6f) + std::ldexp(mag, -21);
     }
+    return BIH_OK;
+}
+
+int bih_pixel_divide(uint32_t size, const float *n, size_t count, float *out, uint32_t *reciprocal) {
+    if (!size || (count && (!n || !out))) return BIH_ERR_INVALID;
+    const float d = (float)size;
+    const bool recip = size <= bih::kPixelDivideMax;
+    const float y = 1.0f / d;
+    for (size_t i = 0; i < count; ++i) out[i] = recip ? bih::pixel_divide(n[i], d, y) : n[i] / d;
+    if (reciprocal) *reciprocal = recip ? 1u : 0u;
     return BIH_OK;
 }
 

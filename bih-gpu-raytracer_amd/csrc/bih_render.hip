@@ -39,6 +39,7 @@
 
 #include "bih_internal.h"
 #include "bih_bound.h"
+#include "bih_pixdiv.h"
 #include "bih_packet_asm.h"
 #include "bih_device.h"
 
@@ -1826,6 +1827,52 @@ __device__ __forceinline__ void frame_draws(uint32_t rs[5], uint32_t s, uint32_t
     }
 }
 
+// The same at 4 spp, where a quad of lanes (lane = pix * 4 + s) is one pixel:
+// its four lanes hold the same state and share the work of the 8 steps.
+// With o_1..o_8 the frame's outputs and rs = (o_-4..o_0), a step is
+//   o_n = A(o_{n-1}) ^ B(o_{n-5}),  A(v) = v ^ (v << 4),
+//   B(x) = t ^ (t << 1) with t = x ^ (x >> 2)            (dev::xorwow_raw).
+// The A chain is sequential and every lane computes it: each needs o_4..o_8
+// as the next state and its own two draws.  The eight B terms do not depend
+// on the chain, except that B_6..B_8 take o_1..o_3, which every lane has by
+// then: lane s computes B_{s+1} = B(rs[s]) and B_{s+5} = B(o_s), and step n
+// takes its term from lane (n - 1) & 3 of its quad (a quad-permute DPP
+// operand).  XOR is associative: the words are the same bits.
+// `own` is rs[s], which the caller reads from the lane's LDS column.
+// Every lane of a quad must be active: a DPP operand from an inactive lane
+// reads 0.  The caller's `valid` is a property of the pixel (x < w and
+// lr < nrows, in cut tiles and row bands alike), so a quad's four lanes enter
+// together or not at all.
+template <uint32_t K>
+__device__ __forceinline__ uint32_t quad_lane(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, (int)(K * 0x55u), 0xf, 0xf, true);
+}
+__device__ __forceinline__ uint32_t xorwow_b(uint32_t x) {
+    const uint32_t t = x ^ (x >> 2);
+    return t ^ (t << 1);
+}
+__device__ __forceinline__ uint32_t xorwow_a(uint32_t v) { return v ^ (v << 4); }
+__device__ __forceinline__ void frame_draws_quad(uint32_t rs[5], uint32_t own, uint32_t s, uint32_t &xu,
+                                                 uint32_t &xv) {
+    const bool b0 = (s & 1u) != 0u, b1 = (s & 2u) != 0u;
+    const uint32_t lo = xorwow_b(own);                       // B_{s+1}
+    const uint32_t o1 = xorwow_a(rs[4]) ^ quad_lane<0>(lo);
+    const uint32_t o2 = xorwow_a(o1) ^ quad_lane<1>(lo);
+    const uint32_t o3 = xorwow_a(o2) ^ quad_lane<2>(lo);
+    const uint32_t o4 = xorwow_a(o3) ^ quad_lane<3>(lo);
+    const uint32_t hl = b0 ? o1 : rs[4], hh = b0 ? o3 : o2;
+    const uint32_t hi = xorwow_b(b1 ? hh : hl);              // B_{s+5}
+    const uint32_t o5 = xorwow_a(o4) ^ quad_lane<0>(hi);
+    const uint32_t o6 = xorwow_a(o5) ^ quad_lane<1>(hi);
+    const uint32_t o7 = xorwow_a(o6) ^ quad_lane<2>(hi);
+    const uint32_t o8 = xorwow_a(o7) ^ quad_lane<3>(hi);
+    rs[0] = o4; rs[1] = o5; rs[2] = o6; rs[3] = o7; rs[4] = o8;
+    const uint32_t ul = b0 ? o3 : o1, uh = b0 ? o7 : o5;
+    const uint32_t vl = b0 ? o4 : o2, vh = b0 ? o8 : o6;
+    xu = b1 ? uh : ul;
+    xv = b1 ? vh : vl;
+}
+
 // A plan's 1-2 critical comparisons (meta & 3 of them) on its values v
 __device__ __forceinline__ bool plan_values_check(uint32_t meta, const float4 v, float ix, float iy, float iz,
                                                   float tMin, float tMax) {
@@ -2042,6 +2089,9 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
     const cprim_t *prims = (const cprim_t *)(const void *)a.tri_prim;
     const uint32_t tiles_x = (a.w + TW - 1) / TW;
     const float fw = (float)a.w, fh = (float)a.h;
+    // the image's reciprocals, correctly rounded, once per wave (pixel_divide)
+    const float yw = 1.0f / fw, yh = 1.0f / fh;
+    const bool recip = a.w <= kPixelDivideMax && a.h <= kPixelDivideMax;
     const uint32_t pix = lane >> LOG2SPP;
     const uint32_t misspix = pixel_from_hits(0u, SPP), solidpix = pixel_from_hits(SPP, SPP);
     // the bins' status word (k_bin_status wrote it before this launch, nothing
@@ -2299,7 +2349,13 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
                 uint32_t rs[5];
 #pragma unroll
                 for (int i = 0; i < 5; ++i) rs[i] = s_rs[i][tid];
-                frame_draws<SPP>(rs, s, xu, xv);
+                if constexpr (SPP == 4u) {
+                    // (a quad is one pixel: ray_coords' lane = pix * SPP + s)
+                    static_assert(LOG2SPP == 2 && kThreads % 64 == 0, "a quad of lanes is one pixel");
+                    frame_draws_quad(rs, s_rs[s][tid], s, xu, xv);
+                } else {
+                    frame_draws<SPP>(rs, s, xu, xv);
+                }
                 xu += dfr + wo;
                 xv += dfr + wo + kWeyl;
                 const float ru = dev::xorwow_to_uniform(xu), rv = dev::xorwow_to_uniform(xv);
@@ -2317,8 +2373,15 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bins(const RenderArgs a)
 #pragma unroll
                     for (int i = 0; i < 5; ++i) dst[(uint64_t)i * P + lp] = rs[i];
                 }
-                uf = ((float)x + ru) / fw;       // CUDAKernels.cu:414-415
-                vf = ((float)y + rv) / fh;
+                // CUDAKernels.cu:414-415; the same quotients through the
+                // image's reciprocals (bih_pixdiv.h) at the sizes its proof covers
+                if (recip) {
+                    uf = pixel_divide((float)x + ru, fw, yw);
+                    vf = pixel_divide((float)y + rv, fh, yh);
+                } else {
+                    uf = ((float)x + ru) / fw;
+                    vf = ((float)y + rv) / fh;
+                }
                 camera_dir(a, uf, vf, dx, dy, dz);
             }
             // Ray::Ray (Ray.cu:3-10) + scene-AABB slab test (CUDAKernels.cu:237-262)

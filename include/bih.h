@@ -147,6 +147,12 @@ int bih_camera_reference(uint32_t w, uint32_t h, bih_camera *out);
  * in f32 for u, v in [0, 1] (Camera.cu:18-20).  The any-hit walk's miss-proof
  * boxes are sized with it. */
 int bih_camera_ray_bound(const bih_camera *camera, float dmax[3]);
+/* Host only: out[i] = the quotient n[i] / (float)size as the primary render's
+ * kernel forms a pixel coordinate (x + ru) / w, (y + rv) / h: through the
+ * image side's reciprocal and two fma up to a side of 65536, where that is
+ * proved to be the IEEE quotient, by the division
+ * itself above it.  *reciprocal (may be NULL) is set to 1 or 0 accordingly. */
+int bih_pixel_divide(uint32_t size, const float *n, size_t count, float *out, uint32_t *reciprocal);
 
 /* Scene ingestion (host only, no device): a Wavefront OBJ file flattened to a
  * triangle soup in file order, replacing Model::LoadModel's assimp import
