@@ -455,16 +455,20 @@ class Renderer:
                                                frame, self.seed, _rows_ref(rows),
                                                C.byref(gb), C.c_void_p(stream or 0)), "bih_render_gbuffer_device")
 
-    def _host_direct(self, rows, planes):
-        """Zeroed host arrays of the DIRECT_PLANES asked for, by name, and the
-        bih_direct that points at them."""
+    def _host_planes(self, st, table, planes, rows, n_bounces: int = 0):
+        """Zeroed host arrays of the planes asked for, by name, shaped as their
+        *_PLANES table says (values per pixel k > 0: (nrows, w) or (nrows, w, k);
+        0: one per sample; -1: (n_bounces, samples)), and the plane struct `st`
+        (Direct, Indirect, Path, PathRgb) pointing at them."""
         nrows = rows.nrows if rows is not None else self.h
-        out, dp = {}, Direct()
+        S = nrows * self.w * self.spp
+        out = {}
         for name in planes:
-            dt, k = DIRECT_PLANES[name]
-            out[name] = np.zeros((nrows, self.w) if k else nrows * self.w * self.spp, dt)
-            setattr(dp, name, out[name].ctypes.data)
-        return out, dp
+            dt, k = table[name]
+            shape = (nrows, self.w) + ((k,) if k > 1 else ()) if k > 0 else ((n_bounces, S) if k < 0 else S)
+            out[name] = np.zeros(shape, dt)
+            setattr(st, name, out[name].ctypes.data)
+        return out, st
 
     def render_direct(self, lights, frame: int | None = None, rows: Rows | None = None,
                       planes=("lit", "irradiance", "rgba")) -> dict:
@@ -476,7 +480,7 @@ class Renderer:
         "irradiance" (nrows, w) float32; "rgba" (nrows, w) uint32 grey."""
         f = self.frame if frame is None else frame
         lt = pack_lights(lights)
-        out, dp = self._host_direct(rows, planes)
+        out, dp = self._host_planes(Direct(), DIRECT_PLANES, planes, rows)
         check(load().bih_render_direct(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
                                        self.seed, _rows_ref(rows),
                                        C.c_void_p(lt.ctypes.data), lt.shape[0], C.byref(dp)), "bih_render_direct")
@@ -512,7 +516,7 @@ class Renderer:
         + j point light j, which a triangle behind it does not shadow."""
         f = self.frame if frame is None else frame
         dl, pl, dptr, nd, pptr, npt = self._lights_args(dir_lights, point_lights)
-        out, dp = self._host_direct(rows, planes)
+        out, dp = self._host_planes(Direct(), DIRECT_PLANES, planes, rows)
         check(load().bih_render_lights(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
                                        self.seed, _rows_ref(rows),
                                        dptr, nd, pptr, npt, C.byref(dp)), "bih_render_lights")
@@ -537,6 +541,27 @@ class Renderer:
         ls = LightSet(dptr, nd, pptr, npt, C.c_void_p(al.ctypes.data if al.shape[0] else 0), al.shape[0])
         return (dl, pl, al), ls   # (the arrays stay alive as long as the first element does)
 
+    def _host_call(self, fn: str, st, table, planes, lights, extra, frame, rows, n_bounces: int = 0) -> dict:
+        """A host entry that takes a bih_light_set: `fn` names the C function, `st`
+        and `table` are its plane struct and *_PLANES, `lights` the three light
+        arrays, `extra` its arguments between the light set and the planes."""
+        f = self.frame if frame is None else frame
+        keep, ls = self._light_set(*lights)
+        out, st = self._host_planes(st, table, planes, rows, n_bounces)
+        check(getattr(load(), fn)(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f, self.seed,
+                                  _rows_ref(rows), C.byref(ls), *extra, C.byref(st)), fn)
+        del keep
+        self.frame = f + 1
+        return out
+
+    def _device_call(self, fn: str, st, table, ptrs: dict, lights, extra, frame, rows, stream):
+        """The device entry next to _host_call's: ptrs maps plane names to device pointers."""
+        st = _device_planes(st, table, ptrs)
+        keep, ls = self._light_set(*lights)
+        check(getattr(load(), fn)(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, frame, self.seed,
+                                  _rows_ref(rows), C.byref(ls), *extra, C.byref(st), C.c_void_p(stream or 0)), fn)
+        del keep
+
     def render_area_lights(self, dir_lights, point_lights, area_lights, frame: int | None = None,
                            rows: Rows | None = None, planes=("lit", "irradiance", "rgba")) -> dict:
         """render_lights with area lights (soft shadows) next to the others
@@ -546,28 +571,16 @@ class Renderer:
         or empty, together 1 .. MAX_LIGHTS.  Bit len(dir_lights) +
         len(point_lights) + j of "lit" is area light j: per sample one shadow
         ray to a point of the panel (area_light_sample)."""
-        f = self.frame if frame is None else frame
-        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        out, dp = self._host_direct(rows, planes)
-        check(load().bih_render_area_lights(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
-                                            self.seed, _rows_ref(rows),
-                                            C.byref(ls), C.byref(dp)), "bih_render_area_lights")
-        del keep
-        self.frame = f + 1
-        return out
+        return self._host_call("bih_render_area_lights", Direct(), DIRECT_PLANES, planes,
+                               (dir_lights, point_lights, area_lights), (), frame, rows)
 
     def render_area_lights_device(self, ptrs: dict, dir_lights, point_lights, area_lights, frame: int,
                                   rows: Rows | None = None, stream: int | None = None):
         """Asynchronous render_area_lights into device memory
         (bih_render_area_lights_device); ptrs as render_direct_device's.  The
         light arrays are host memory, copied by the call."""
-        dp = _device_planes(Direct(), DIRECT_PLANES, ptrs)
-        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        check(load().bih_render_area_lights_device(self.arrays.handle, C.byref(self.camera), self.w, self.h,
-                                                   self.spp, frame, self.seed, _rows_ref(rows),
-                                                   C.byref(ls), C.byref(dp), C.c_void_p(stream or 0)),
-              "bih_render_area_lights_device")
-        del keep
+        self._device_call("bih_render_area_lights_device", Direct(), DIRECT_PLANES, ptrs,
+                          (dir_lights, point_lights, area_lights), (), frame, rows, stream)
 
     @staticmethod
     def _bounce(bounce) -> Bounce:
@@ -583,21 +596,8 @@ class Renderer:
         (INDIRECT_PLANES): "lit" and "lit2" (nrows*w*spp,) uint64 of the primary
         and the bounce hit, "bounce" (nrows*w*spp,) HIT_DTYPE, the bounce ray's
         closest hit, "irradiance" (nrows, w) float32, "rgba" (nrows, w) uint32."""
-        f = self.frame if frame is None else frame
-        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        nrows = rows.nrows if rows is not None else self.h
-        out, ip = {}, Indirect()
-        for name in planes:
-            dt, k = INDIRECT_PLANES[name]
-            out[name] = np.zeros((nrows, self.w) if k else nrows * self.w * self.spp, dt)
-            setattr(ip, name, out[name].ctypes.data)
-        bn = self._bounce(bounce)
-        check(load().bih_render_indirect(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
-                                         self.seed, _rows_ref(rows), C.byref(ls), C.byref(bn), C.byref(ip)),
-              "bih_render_indirect")
-        del keep
-        self.frame = f + 1
-        return out
+        return self._host_call("bih_render_indirect", Indirect(), INDIRECT_PLANES, planes,
+                               (dir_lights, point_lights, area_lights), (C.byref(self._bounce(bounce)),), frame, rows)
 
     def render_indirect_device(self, ptrs: dict, dir_lights, point_lights, area_lights, bounce, frame: int,
                                rows: Rows | None = None, stream: int | None = None):
@@ -605,14 +605,9 @@ class Renderer:
         (bih_render_indirect_device): ptrs maps plane names (INDIRECT_PLANES) to
         device pointers; planes left out are not written.  The light arrays and
         bounce are host memory, copied by the call."""
-        ip = _device_planes(Indirect(), INDIRECT_PLANES, ptrs)
-        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        bn = self._bounce(bounce)
-        check(load().bih_render_indirect_device(self.arrays.handle, C.byref(self.camera), self.w, self.h,
-                                                self.spp, frame, self.seed, _rows_ref(rows),
-                                                C.byref(ls), C.byref(bn), C.byref(ip), C.c_void_p(stream or 0)),
-              "bih_render_indirect_device")
-        del keep
+        self._device_call("bih_render_indirect_device", Indirect(), INDIRECT_PLANES, ptrs,
+                          (dir_lights, point_lights, area_lights),
+                          (C.byref(self._bounce(bounce)),), frame, rows, stream)
 
     def render_path(self, dir_lights, point_lights, area_lights, bounce, n_bounces: int, frame: int | None = None,
                     rows: Rows | None = None, planes=PATH) -> dict:
@@ -624,22 +619,9 @@ class Renderer:
         (n_bounces, nrows*w*spp) uint64, row k-1 level k's bounce records and
         lit words, "irradiance" (nrows, w) float32, "rgba" (nrows, w) uint32.
         With n_bounces = 1 they are render_indirect's planes."""
-        f = self.frame if frame is None else frame
-        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        nrows = rows.nrows if rows is not None else self.h
-        S = nrows * self.w * self.spp
-        out, pp = {}, Path()
-        for name in planes:
-            dt, k = PATH_PLANES[name]
-            out[name] = np.zeros((nrows, self.w) if k > 0 else ((n_bounces, S) if k < 0 else S), dt)
-            setattr(pp, name, out[name].ctypes.data)
-        bn = self._bounce(bounce)
-        check(load().bih_render_path(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
-                                     self.seed, _rows_ref(rows), C.byref(ls), C.byref(bn), n_bounces, C.byref(pp)),
-              "bih_render_path")
-        del keep
-        self.frame = f + 1
-        return out
+        return self._host_call("bih_render_path", Path(), PATH_PLANES, planes,
+                               (dir_lights, point_lights, area_lights),
+                               (C.byref(self._bounce(bounce)), n_bounces), frame, rows, n_bounces)
 
     def render_path_device(self, ptrs: dict, dir_lights, point_lights, area_lights, bounce, n_bounces: int,
                            frame: int, rows: Rows | None = None, stream: int | None = None):
@@ -647,14 +629,9 @@ class Renderer:
         ptrs maps plane names (PATH_PLANES) to device pointers; planes left out
         are not written.  The light arrays and bounce are host memory, copied by
         the call."""
-        pp = _device_planes(Path(), PATH_PLANES, ptrs)
-        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        bn = self._bounce(bounce)
-        check(load().bih_render_path_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
-                                            frame, self.seed, _rows_ref(rows), C.byref(ls), C.byref(bn), n_bounces,
-                                            C.byref(pp), C.c_void_p(stream or 0)),
-              "bih_render_path_device")
-        del keep
+        self._device_call("bih_render_path_device", Path(), PATH_PLANES, ptrs,
+                          (dir_lights, point_lights, area_lights),
+                          (C.byref(self._bounce(bounce)), n_bounces), frame, rows, stream)
 
     @staticmethod
     def _sky3(sky):
@@ -666,23 +643,9 @@ class Renderer:
         and an RGB sky, a 3-vector (bih_render_path_rgb; synchronous).  Returns
         a dict of the planes asked for (PATH_RGB_PLANES): "lit", "bounces",
         "lits" and "rgba" as render_path's, "radiance" (nrows, w, 3) float32."""
-        f = self.frame if frame is None else frame
-        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        nrows = rows.nrows if rows is not None else self.h
-        S = nrows * self.w * self.spp
-        out, pp = {}, PathRgb()
-        for name in planes:
-            dt, k = PATH_RGB_PLANES[name]
-            shape = ((nrows, self.w) if k == 1 else (nrows, self.w, k)) if k > 0 else ((n_bounces, S) if k < 0 else S)
-            out[name] = np.zeros(shape, dt)
-            setattr(pp, name, out[name].ctypes.data)
-        check(load().bih_render_path_rgb(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
-                                         self.seed, _rows_ref(rows), C.byref(ls), self._sky3(sky), n_bounces,
-                                         C.byref(pp)),
-              "bih_render_path_rgb")
-        del keep
-        self.frame = f + 1
-        return out
+        return self._host_call("bih_render_path_rgb", PathRgb(), PATH_RGB_PLANES, planes,
+                               (dir_lights, point_lights, area_lights),
+                               (self._sky3(sky), n_bounces), frame, rows, n_bounces)
 
     def render_path_rgb_device(self, ptrs: dict, dir_lights, point_lights, area_lights, sky, n_bounces: int,
                                frame: int, rows: Rows | None = None, stream: int | None = None):
@@ -690,13 +653,8 @@ class Renderer:
         (bih_render_path_rgb_device): ptrs maps plane names (PATH_RGB_PLANES) to
         device pointers; planes left out are not written.  The light arrays and
         sky are host memory, copied by the call."""
-        pp = _device_planes(PathRgb(), PATH_RGB_PLANES, ptrs)
-        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        check(load().bih_render_path_rgb_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
-                                                frame, self.seed, _rows_ref(rows), C.byref(ls), self._sky3(sky),
-                                                n_bounces, C.byref(pp), C.c_void_p(stream or 0)),
-              "bih_render_path_rgb_device")
-        del keep
+        self._device_call("bih_render_path_rgb_device", PathRgb(), PATH_RGB_PLANES, ptrs,
+                          (dir_lights, point_lights, area_lights), (self._sky3(sky), n_bounces), frame, rows, stream)
 
     def render_path_spec(self, dir_lights, point_lights, area_lights, sky, n_bounces: int, frame: int | None = None,
                          rows: Rows | None = None, planes=PATH_RGB) -> dict:
@@ -704,35 +662,16 @@ class Renderer:
         MAT_MIRROR material goes on along the reflection and gathers no light
         there (bih_render_path_spec; synchronous).  The planes are
         render_path_rgb's."""
-        f = self.frame if frame is None else frame
-        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        nrows = rows.nrows if rows is not None else self.h
-        S = nrows * self.w * self.spp
-        out, pp = {}, PathRgb()
-        for name in planes:
-            dt, k = PATH_RGB_PLANES[name]
-            shape = ((nrows, self.w) if k == 1 else (nrows, self.w, k)) if k > 0 else ((n_bounces, S) if k < 0 else S)
-            out[name] = np.zeros(shape, dt)
-            setattr(pp, name, out[name].ctypes.data)
-        check(load().bih_render_path_spec(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp, f,
-                                          self.seed, _rows_ref(rows), C.byref(ls), self._sky3(sky), n_bounces,
-                                          C.byref(pp)),
-              "bih_render_path_spec")
-        del keep
-        self.frame = f + 1
-        return out
+        return self._host_call("bih_render_path_spec", PathRgb(), PATH_RGB_PLANES, planes,
+                               (dir_lights, point_lights, area_lights),
+                               (self._sky3(sky), n_bounces), frame, rows, n_bounces)
 
     def render_path_spec_device(self, ptrs: dict, dir_lights, point_lights, area_lights, sky, n_bounces: int,
                                 frame: int, rows: Rows | None = None, stream: int | None = None):
         """Asynchronous render_path_spec into device memory
         (bih_render_path_spec_device), as render_path_rgb_device."""
-        pp = _device_planes(PathRgb(), PATH_RGB_PLANES, ptrs)
-        keep, ls = self._light_set(dir_lights, point_lights, area_lights)
-        check(load().bih_render_path_spec_device(self.arrays.handle, C.byref(self.camera), self.w, self.h, self.spp,
-                                                 frame, self.seed, _rows_ref(rows), C.byref(ls), self._sky3(sky),
-                                                 n_bounces, C.byref(pp), C.c_void_p(stream or 0)),
-              "bih_render_path_spec_device")
-        del keep
+        self._device_call("bih_render_path_spec_device", PathRgb(), PATH_RGB_PLANES, ptrs,
+                          (dir_lights, point_lights, area_lights), (self._sky3(sky), n_bounces), frame, rows, stream)
 
     def denoise(self, radiance, depth, normal, params=None, planes=("radiance", "rgba")) -> dict:
         """The edge-avoiding a-trous filter over a whole frame's host planes

@@ -1,6 +1,6 @@
 // bih_bounce.h -- the bounce direction of a primary-hit sample
 // (bih_render_indirect*, include/bih.h): ONE
-// expression for k_bounce and k_indirect_setup2 of bih_direct.hip and for
+// expression for the bounce walk of bih_direct.hip (k_path_bounce) and for
 // bih_bounce_sample on the host, as bih_area.h is for the panels.  The
 // direction comes from the area lights' counter-based hash with the slot
 // kBounceSlot, which no light index takes: no XORWOW draw of any frame moves.

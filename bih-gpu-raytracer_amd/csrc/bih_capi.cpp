@@ -11,8 +11,8 @@
 // the last rebuild), Frame (what every render entry is asked for), resolve_rows
 // (the row rule), begin_slot / slot_args / finish_slot (a render slot taken
 // outside the camera sets: Whitted and G-buffer launches), mask_prepass (their
-// any-hit pass through the frustum bins), and light_set_check /
-// render_light_set (the one path of the six direct-lighting entries).
+// any-hit pass through the frustum bins), and LightJob / render_lighting (the
+// one path of every lighting entry, direct to mirror paths).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -47,7 +47,7 @@ constexpr bool kShareOneFrame = BIH_SHARE_ONE_FRAME != 0;
 constexpr size_t kEntryBytes = 16 * bih::kBinEntryF4;   // frustum-bin list entry
 using bih::kTraceCursorBytes;                           // the work area's cursor block (bih::WorkArea)
 constexpr size_t kDirectSampleBytes = 16 + 8 + 4;       // dr_mem per sample: record, facing mask, list entry
-constexpr size_t kIndirectSampleBytes = 16 + 4;         // in_mem per sample: bounce record, hit-list entry
+constexpr size_t kIndirectSampleBytes = 16 + 4;         // in_mem per sample: second record buffer, live-list entry
 constexpr size_t kPathSampleBytes = 4 + 4 + 1;          // pt_mem per sample: sum, second live-list entry, primary-hit flag
 constexpr size_t kPathRgbSampleBytes = 16 + 16;         // pc_mem per sample: RGB sum record, RGB throughput record
 constexpr size_t kPathSpecSampleBytes = 16;             // ps_mem per sample: {D, kind} of the latest hit
@@ -339,9 +339,10 @@ struct bih_tree {
     char *in_stage = nullptr;
     size_t in_stage_cap = 0;         // bytes
     // Path renders (bih_render_path*) are an indirect-lighting render with more
-    // levels: next to dr_mem, in_mem and (for calls without `lits`) in_lit2 per
-    // sample its sum, the second live list's entry and the primary-hit flag;
-    // the host entry's device planes.  Same users, same waits.
+    // levels (an indirect-lighting render is a path render of one): next to
+    // dr_mem, in_mem and (for calls without `lits`) in_lit2 per sample its sum,
+    // the second live list's entry and the primary-hit flag, which both kinds
+    // of call size; the host entry's device planes.  Same users, same waits.
     char *pt_mem = nullptr;
     size_t pt_cap = 0;               // samples (kPathSampleBytes each)
     char *pt_stage = nullptr;
@@ -2346,32 +2347,86 @@ static int gbuffer_check(const bih_tree *tr, Frame *f, const bih_rows *rows_in, 
     return BIH_OK;
 }
 
-// What a direct-lighting call adds to its G-buffer launch: its light set
-// merged into the kernels' slot order (merge_light_set) and the planes to
-// write (device memory).  The launch's hits go to dr_mem.
-struct DirectJob {
-    bih::Lights lights;
-    bih_direct planes;
-    // bih_render_indirect*: the second level (planes then holds lit, irradiance, rgba of `ind`)
-    bool indirect = false;
-    bih_bounce bounce;
-    bih_indirect ind;
-    // bih_render_path*: n_bounces > 0 (with indirect set; ind.bounce and ind.lit2 then hold
-    // the level planes `bounces` and `lits`)
-    uint32_t n_bounces = 0;
-    // bih_render_path_rgb*: rgb set (with n_bounces; bounce is unused, planes.irradiance null)
-    bool rgb = false;
-    // bih_render_path_spec*: spec set (with rgb)
-    bool spec = false;
-    float sky[3] = {0.0f, 0.0f, 0.0f};
-    float *radiance = nullptr;
+// What a lighting call adds to its G-buffer launch, whose hits go to dr_mem.
+enum class Lighting {
+    kDirect,    // bih_render_direct*, _lights*, _area_lights*: the primary level only
+    kGrey,      // bih_render_indirect* (one level), bih_render_path*: levels with a grey albedo and sky
+    kColour,    // bih_render_path_rgb*: levels with the tree's materials and an RGB sky
+    kMirror,    // bih_render_path_spec*: kColour whose materials have kinds
+};
+// The planes of a lighting call, S = P*spp; any may be null.  An entry's: as its
+// caller gave them (host or device memory); a job's: device memory.
+struct LightPlanes {
+    bool given;                 // the entry's planes argument was not NULL
+    uint64_t *lit;              // [S] level 0's lit words
+    bih_hit *bounces;           // [n_bounces*S] the levels' bounce records (bih_indirect: bounce)
+    uint64_t *lits;             // [n_bounces*S] the levels' lit words (bih_indirect: lit2)
+    float *sum;                 // [P] irradiance, sum_bytes 4, or [3P] radiance, 12
+    size_t sum_bytes;           // of `sum` per pixel
+    uint32_t *rgba;             // [P]
+};
+static LightPlanes planes_of(const bih_direct *p) {
+    return p ? LightPlanes{true, p->lit, nullptr, nullptr, p->irradiance, 4, p->rgba} : LightPlanes{};
+}
+static LightPlanes planes_of(const bih_indirect *p) {
+    return p ? LightPlanes{true, p->lit, p->bounce, p->lit2, p->irradiance, 4, p->rgba} : LightPlanes{};
+}
+static LightPlanes planes_of(const bih_path *p) {
+    return p ? LightPlanes{true, p->lit, p->bounces, p->lits, p->irradiance, 4, p->rgba} : LightPlanes{};
+}
+static LightPlanes planes_of(const bih_path_rgb *p) {
+    return p ? LightPlanes{true, p->lit, p->bounces, p->lits, p->radiance, 12, p->rgba} : LightPlanes{};
+}
+struct LightJob {
+    bih::Lights lights;         // the call's light set in the kernels' slot order (merge_light_set)
+    Lighting kind;
+    uint32_t n_bounces;         // levels past the primary one; 0: direct light only (kDirect)
+    float albedo, sky;          // kGrey
+    float sky3[3];              // kColour, kMirror
+    LightPlanes pl;
 };
 
+// The lighting launch of job dj behind its G-buffer launch of the frame `a`, on
+// the same stream: the per-sample scratch, carved from the tree's buffers
+// (direct_locked sized them), and the one launch_direct or launch_path.
+static int launch_lighting(bih_tree *tr, const bih::RenderArgs &a, const LightJob &dj, const bih::WorkArea &wa,
+                           hipStream_t st) {
+    // dr_mem: records, facing masks, list (each at a multiple of 8 bytes); in_mem: second
+    // record buffer, live list; pt_mem: sums, second live list, primary-hit flags
+    const size_t S = tr->dr_cap;
+    char *rec = tr->dr_mem, *face = rec + 16 * S, *list = face + 8 * S;
+    char *rec2 = tr->in_mem, *blist = rec2 + 16 * tr->in_cap;
+    char *acc = tr->pt_mem, *blist2 = acc + 4 * tr->pt_cap, *hit0 = blist2 + 4 * tr->pt_cap;
+    const bih::Scratch sc = {rec, reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
+                             rec2, reinterpret_cast<uint32_t *>(blist), reinterpret_cast<uint32_t *>(blist2),
+                             reinterpret_cast<float *>(acc), reinterpret_cast<uint8_t *>(hit0)};
+    const bool colour = dj.kind == Lighting::kColour || dj.kind == Lighting::kMirror;
+    bih::PathPlanes pp;
+    pp.lit = dj.pl.lit ? reinterpret_cast<unsigned long long *>(dj.pl.lit) : tr->dr_lit;
+    pp.irradiance = colour ? nullptr : dj.pl.sum;
+    pp.rgba = dj.pl.rgba;
+    if (dj.kind == Lighting::kDirect) return bih::launch_direct(tr->t, a, pp, dj.lights, sc, wa, st);
+    pp.bounces = dj.pl.bounces;
+    pp.lits = reinterpret_cast<unsigned long long *>(dj.pl.lits);
+    pp.lit_scratch = tr->in_lit2;
+    if (!colour)
+        return bih::launch_path(tr->t, a, pp, dj.lights, dj.albedo, dj.sky, dj.n_bounces, sc, wa, st, nullptr);
+    bih::PathRgb c;
+    c.palette = tr->mt_pal;
+    c.ids = tr->mt_ids;
+    c.acc3 = tr->pc_mem;
+    c.thr3 = tr->pc_mem + 16 * tr->pc_cap;
+    if (dj.kind == Lighting::kMirror) c.dk = tr->ps_mem;
+    c.radiance = dj.pl.sum;
+    memcpy(c.sky, dj.sky3, sizeof c.sky);
+    return bih::launch_path(tr->t, a, pp, dj.lights, 1.0f, 0.0f, dj.n_bounces, sc, wa, st, &c);
+}
+
 // bih_render_gbuffer_device under the tree's lock, arguments checked, nrows > 0.
-// dj: the call is bih_render_direct_device's (pl.hits = dr_mem, sized for it):
-// the records carry sorted positions and the direct-lighting kernels follow.
+// dj: the call is a lighting entry's (pl.hits = dr_mem, sized for it): the
+// records carry sorted positions and the job's lighting launch follows.
 static int gbuffer_locked(bih_tree *tr, const Frame &f, const bih_gbuffer &pl, void *stream,
-                          const DirectJob *dj = nullptr) {
+                          const LightJob *dj = nullptr) {
     if (!tr->t.hdr) return BIH_ERR_INVALID;   // no tree was ever built into this buffer
     hipStream_t st = stream ? (hipStream_t)stream : tr->stream;
     int rc = ensure_trace(tr);
@@ -2403,52 +2458,7 @@ static int gbuffer_locked(bih_tree *tr, const Frame &f, const bih_gbuffer &pl, v
     if (e != hipSuccess) return map_hip((int)e);
     const bih::WorkArea wa = work_area(tr);
     rc = bih::launch_gbuffer(tr->t, a, p, mask, wa, st, dj != nullptr);
-    if (rc == 0 && dj) {
-        // dr_mem: records, facing masks, list (each at a multiple of 8 bytes);
-        // in_mem: bounce records, hit list; pt_mem: sums, second live list, primary-hit flags
-        const size_t S = tr->dr_cap;
-        char *rec = tr->dr_mem, *face = rec + 16 * S, *list = face + 8 * S;
-        char *rec2 = tr->in_mem, *blist = rec2 + 16 * tr->in_cap;
-        char *acc = tr->pt_mem, *blist2 = acc + 4 * tr->pt_cap, *hit0 = blist2 + 4 * tr->pt_cap;
-        const bih::Scratch sc = {rec, reinterpret_cast<uint32_t *>(list), reinterpret_cast<unsigned long long *>(face),
-                                 rec2, reinterpret_cast<uint32_t *>(blist), reinterpret_cast<uint32_t *>(blist2),
-                                 reinterpret_cast<float *>(acc), reinterpret_cast<uint8_t *>(hit0)};
-        bih::IndirectPlanes ip;
-        ip.lit = dj->planes.lit ? reinterpret_cast<unsigned long long *>(dj->planes.lit) : tr->dr_lit;
-        ip.irradiance = dj->planes.irradiance;
-        ip.rgba = dj->planes.rgba;
-        if (dj->n_bounces) {
-            bih::PathPlanes pp;
-            static_cast<bih::DirectPlanes &>(pp) = ip;
-            pp.bounces = dj->ind.bounce;
-            pp.lits = reinterpret_cast<unsigned long long *>(dj->ind.lit2);
-            pp.lit_scratch = tr->in_lit2;
-            if (dj->rgb) {
-                bih::PathRgb c;
-                c.palette = tr->mt_pal;
-                c.ids = tr->mt_ids;
-                c.acc3 = tr->pc_mem;
-                c.thr3 = tr->pc_mem + 16 * tr->pc_cap;
-                c.radiance = dj->radiance;
-                memcpy(c.sky, dj->sky, sizeof c.sky);
-                if (dj->spec) {
-                    c.dk = tr->ps_mem;
-                    rc = bih::launch_path_spec(tr->t, a, pp, dj->lights, c, dj->n_bounces, sc, wa, st);
-                } else {
-                    rc = bih::launch_path_rgb(tr->t, a, pp, dj->lights, c, dj->n_bounces, sc, wa, st);
-                }
-            } else {
-                rc = bih::launch_path(tr->t, a, pp, dj->lights, dj->bounce.albedo, dj->bounce.sky, dj->n_bounces, sc,
-                                      wa, st);
-            }
-        } else if (dj->indirect) {
-            ip.bounce = dj->ind.bounce;
-            ip.lit2 = dj->ind.lit2 ? reinterpret_cast<unsigned long long *>(dj->ind.lit2) : tr->in_lit2;
-            rc = bih::launch_indirect(tr->t, a, ip, dj->lights, dj->bounce.albedo, dj->bounce.sky, sc, wa, st);
-        } else {
-            rc = bih::launch_direct(tr->t, a, ip, dj->lights, sc, wa, st);
-        }
-    }
+    if (rc == 0 && dj) rc = launch_lighting(tr, a, *dj, wa, st);
     // (a failed launch may have left work on st that uses the cursor: the event covers it)
     e = hipEventRecord(tr->ev_trace, st);
     if (e == hipSuccess) tr->trace_used = true;
@@ -2497,28 +2507,26 @@ int bih_render_gbuffer(const bih_tree *ctr, const bih_camera *cam, uint32_t w, u
     return sg.finish(tr, gbuffer_locked(tr, f, d, nullptr));
 }
 
-// Argument checks of the six direct-lighting entries (bih_render_direct*,
-// bih_render_lights*, bih_render_area_lights*), each of which states its
+// Argument checks every lighting entry starts with, each of which states its
 // lights as a bih_light_set: the G-buffer's checks, then the lights and lit's
-// alignment (BIH_ERR_INVALID all, so one order serves the three headers').
+// alignment (BIH_ERR_INVALID all, so one order serves all the headers').
 // None touches the tree or a device.  f, f->rows: as gbuffer_check.
-// ind: the planes of bih_render_indirect* (pl then holds its lit, irradiance
-// and rgba): "all planes NULL" is about the five, ls may be NULL or empty.
+// pl: the entry's planes; "all planes NULL" is about its five (a direct entry
+// has three), and only a direct entry (!levels) needs a light.
 static int light_set_check(const bih_tree *tr, Frame *f, const bih_rows *rows_in, const bih_light_set *ls,
-                           const bih_direct *pl, const bih_indirect *ind = nullptr) {
-    // the G-buffer's "all planes NULL" is about the three planes here
+                           const LightPlanes &pl, bool levels) {
+    // the G-buffer's "all planes NULL" is about the job's planes here
     static float some_plane;
     bih_gbuffer g = {};
-    if (pl && (pl->lit || pl->irradiance || pl->rgba)) g.depth = &some_plane;
-    if (ind && (ind->bounce || ind->lit2)) g.depth = &some_plane;
-    const int rc = gbuffer_check(tr, f, rows_in, pl ? &g : nullptr);
+    if (pl.lit || pl.bounces || pl.lits || pl.sum || pl.rgba) g.depth = &some_plane;
+    const int rc = gbuffer_check(tr, f, rows_in, pl.given ? &g : nullptr);
     if (rc) return rc;
     if (!ls) return BIH_ERR_INVALID;
     const uint64_t n = (uint64_t)ls->n_dir + ls->n_point + ls->n_area;
-    if ((n == 0 && !ind) || n > BIH_MAX_LIGHTS) return BIH_ERR_INVALID;
+    if ((n == 0 && !levels) || n > BIH_MAX_LIGHTS) return BIH_ERR_INVALID;
     if (ls->n_area > BIH_MAX_AREA_LIGHTS) return BIH_ERR_INVALID;
     if ((ls->n_dir && !ls->dir) || (ls->n_point && !ls->point) || (ls->n_area && !ls->area)) return BIH_ERR_INVALID;
-    if ((uintptr_t)pl->lit & 7u) return BIH_ERR_INVALID;   // the lit words take 64-bit atomics
+    if ((uintptr_t)pl.lit & 7u) return BIH_ERR_INVALID;   // the lit words take 64-bit atomics
     return BIH_OK;
 }
 
@@ -2556,56 +2564,82 @@ static void merge_light_set(const bih_light_set *ls, const Frame &f, bih::Lights
     }
 }
 
-// A direct-lighting render into dj.planes under the tree's lock, arguments
-// checked, nrows > 0.
-static int direct_locked(bih_tree *tr, const Frame &f, const DirectJob &dj, void *stream) {
+// The lighting render of job dj (device planes) under the tree's lock,
+// arguments checked, nrows > 0.
+static int direct_locked(bih_tree *tr, const Frame &f, const LightJob &dj, void *stream) {
     const size_t S = (size_t)f.samples();
-    const bool own_lit = !dj.planes.lit && tr->dr_lit_cap < S;
-    const bool own_lit2 = dj.indirect && !dj.ind.lit2 && tr->in_lit2_cap < S;
-    const bool own_in = dj.indirect && tr->in_cap < S;
-    const bool own_pt = dj.n_bounces && tr->pt_cap < S;
-    const bool own_pc = dj.rgb && tr->pc_cap < S;
-    const bool own_ps = dj.spec && tr->ps_cap < S;
-    if ((tr->dr_cap < S || own_lit || own_lit2 || own_in || own_pt || own_pc || own_ps) && tr->trace_used) {
-        // (the users of both buffers are direct-lighting launches: each ends before its ev_trace record)
+    const bool levels = dj.kind != Lighting::kDirect, mirror = dj.kind == Lighting::kMirror;
+    const bool colour = dj.kind == Lighting::kColour || mirror;
+    // the tree's per-sample buffers in the order they grow: capacity in samples, bytes per sample, the job uses it
+    const struct { void **p; size_t *cap, bytes; bool need; } bufs[] = {
+        {(void **)&tr->dr_lit, &tr->dr_lit_cap, 8, !dj.pl.lit},
+        {(void **)&tr->dr_mem, &tr->dr_cap, kDirectSampleBytes, true},
+        {(void **)&tr->in_lit2, &tr->in_lit2_cap, 8, levels && !dj.pl.lits},
+        {(void **)&tr->in_mem, &tr->in_cap, kIndirectSampleBytes, levels},
+        {(void **)&tr->pt_mem, &tr->pt_cap, kPathSampleBytes, levels},
+        {(void **)&tr->pc_mem, &tr->pc_cap, kPathRgbSampleBytes, colour},
+        {(void **)&tr->ps_mem, &tr->ps_cap, kPathSpecSampleBytes, mirror},
+    };
+    bool grows = false;
+    for (const auto &b : bufs) grows = grows || (b.need && *b.cap < S);
+    if (grows && tr->trace_used) {
+        // (the buffers' users are lighting launches: each ends before its ev_trace record)
         const hipError_t e = hipEventSynchronize(tr->ev_trace);
         if (e != hipSuccess) return map_hip((int)e);
     }
-    int rc = own_lit ? grow(tr, &tr->dr_lit, &tr->dr_lit_cap, S, S * 8) : BIH_OK;
-    if (rc == BIH_OK) rc = grow(tr, &tr->dr_mem, &tr->dr_cap, S, S * kDirectSampleBytes);
-    if (rc == BIH_OK && own_lit2) rc = grow(tr, &tr->in_lit2, &tr->in_lit2_cap, S, S * 8);
-    if (rc == BIH_OK && own_in) rc = grow(tr, &tr->in_mem, &tr->in_cap, S, S * kIndirectSampleBytes);
-    if (rc == BIH_OK && own_pt) rc = grow(tr, &tr->pt_mem, &tr->pt_cap, S, S * kPathSampleBytes);
-    if (rc == BIH_OK && own_pc) rc = grow(tr, &tr->pc_mem, &tr->pc_cap, S, S * kPathRgbSampleBytes);
-    if (rc == BIH_OK && own_ps) rc = grow(tr, &tr->ps_mem, &tr->ps_cap, S, S * kPathSpecSampleBytes);
+    int rc = BIH_OK;
+    for (const auto &b : bufs)
+        if (rc == BIH_OK && b.need) rc = grow(tr, b.p, b.cap, S, S * b.bytes);
     if (rc) return rc;
     bih_gbuffer g = {};
     g.hits = reinterpret_cast<bih_hit *>(tr->dr_mem);
     return gbuffer_locked(tr, f, g, stream, &dj);
 }
 
-// The body of the six entries: the checks, then under the tree's lock the
-// merged lights and the render -- into the caller's device planes on `stream`,
-// or (host) into device planes of dr_stage on the tree's stream, copied to the
-// caller's before the call returns.
-static int render_light_set(const bih_tree *ctr, Frame f, const bih_rows *rows_in, const bih_light_set *ls,
-                            const bih_direct *planes, void *stream, bool host) {
-    int rc = light_set_check(ctr, &f, rows_in, ls, planes);
-    if (rc || f.rows.nrows == 0) return rc;
+// The tree's stage buffers, one per family of host entries.
+struct StageBuf { char *bih_tree::*buf; size_t bih_tree::*cap; };
+constexpr StageBuf kDirectStage = {&bih_tree::dr_stage, &bih_tree::dr_stage_cap};
+constexpr StageBuf kIndirectStage = {&bih_tree::in_stage, &bih_tree::in_stage_cap};
+constexpr StageBuf kPathStage = {&bih_tree::pt_stage, &bih_tree::pt_stage_cap};
+constexpr StageBuf kColourStage = {&bih_tree::pc_stage, &bih_tree::pc_stage_cap};
+
+// The body of every lighting entry: the checks in the headers' one order, then
+// under the tree's lock the materials checks, the merged lights and the render
+// -- into the caller's device planes on `stream`, or (a host entry: `stage`)
+// into device planes of that buffer on the tree's stream, copied to the
+// caller's before the call returns.  bounce: kGrey's; sky: kColour's, kMirror's.
+static int render_lighting(const bih_tree *ctr, Frame f, const bih_rows *rows_in, const bih_light_set *ls,
+                           Lighting kind, const bih_bounce *bounce, const float *sky, uint32_t n_bounces,
+                           LightPlanes pl, void *stream, const StageBuf *stage = nullptr) {
+    static_assert(BIH_MAX_BOUNCES == bih::kMaxBounces, "BIH_MAX_BOUNCES / kMaxBounces");
+    static const bih_light_set no_lights = {nullptr, 0, nullptr, 0, nullptr, 0};
+    const bool levels = kind != Lighting::kDirect, colour = levels && kind != Lighting::kGrey;
+    if (!ls && levels) ls = &no_lights;
+    int rc = light_set_check(ctr, &f, rows_in, ls, pl, levels);
+    if (rc) return rc;
+    if (levels && (colour ? !sky : !bounce)) return BIH_ERR_INVALID;
+    if (levels && (n_bounces == 0 || n_bounces > BIH_MAX_BOUNCES)) return BIH_ERR_INVALID;
+    if (((uintptr_t)pl.lits & 7u) || ((uintptr_t)pl.bounces & 15u)) return BIH_ERR_INVALID;
+    if (f.rows.nrows == 0) return BIH_OK;
     bih_tree *tr = const_cast<bih_tree *>(ctr);
     DeviceGuard g(tr->t.device);
     std::lock_guard<std::mutex> lk(tr->mu);
-    DirectJob dj;
+    if (colour && !tr->mt_pal) return BIH_ERR_INVALID;   // no materials: bih_tree_set_materials first
+    if (kind == Lighting::kMirror && !tr->mt_kinds_ok) return BIH_ERR_INVALID;
+    LightJob dj = {{}, kind, n_bounces, bounce ? bounce->albedo : 0.0f, bounce ? bounce->sky : 0.0f, {}, pl};
+    if (sky) memcpy(dj.sky3, sky, sizeof dj.sky3);
     merge_light_set(ls, f, &dj.lights);
-    dj.planes = *planes;
-    if (!host) return direct_locked(tr, f, dj, stream);
-    const size_t P = f.pixels();
-    Stage<3> sg{{planes->lit, planes->irradiance, planes->rgba}, {P * f.spp * 8, P * 4, P * 4}};
-    rc = sg.place(tr, &tr->dr_stage, &tr->dr_stage_cap);
+    if (!stage) return direct_locked(tr, f, dj, stream);
+    const size_t P = f.pixels(), S = (size_t)f.samples(), B = n_bounces;
+    Stage<5> sg{{pl.lit, pl.bounces, pl.lits, pl.sum, pl.rgba},
+                {S * 8, B * S * sizeof(bih_hit), B * S * 8, P * pl.sum_bytes, P * 4}};
+    rc = sg.place(tr, &(tr->*stage->buf), &(tr->*stage->cap));
     if (rc) return rc;
-    dj.planes.lit = static_cast<uint64_t *>(sg.dev(0));
-    dj.planes.irradiance = static_cast<float *>(sg.dev(1));
-    dj.planes.rgba = static_cast<uint32_t *>(sg.dev(2));
+    dj.pl.lit = static_cast<uint64_t *>(sg.dev(0));
+    dj.pl.bounces = static_cast<bih_hit *>(sg.dev(1));
+    dj.pl.lits = static_cast<uint64_t *>(sg.dev(2));
+    dj.pl.sum = static_cast<float *>(sg.dev(3));
+    dj.pl.rgba = static_cast<uint32_t *>(sg.dev(4));
     return sg.finish(tr, direct_locked(tr, f, dj, nullptr));
 }
 
@@ -2613,14 +2647,16 @@ int bih_render_direct_device(const bih_tree *tr, const bih_camera *cam, uint32_t
                              uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light *lights,
                              uint32_t n_lights, const bih_direct *d_planes, void *stream) {
     const bih_light_set ls = {lights, n_lights, nullptr, 0, nullptr, 0};
-    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, d_planes, stream, false);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, Lighting::kDirect, nullptr,
+                           nullptr, 0, planes_of(d_planes), stream);
 }
 
 int bih_render_direct(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                       uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light *lights,
                       uint32_t n_lights, const bih_direct *host_planes) {
     const bih_light_set ls = {lights, n_lights, nullptr, 0, nullptr, 0};
-    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, host_planes, nullptr, true);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, Lighting::kDirect, nullptr,
+                           nullptr, 0, planes_of(host_planes), nullptr, &kDirectStage);
 }
 
 int bih_render_lights_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
@@ -2628,7 +2664,8 @@ int bih_render_lights_device(const bih_tree *tr, const bih_camera *cam, uint32_t
                              uint32_t n_dir, const bih_point_light *point_lights, uint32_t n_point,
                              const bih_direct *d_planes, void *stream) {
     const bih_light_set ls = {dir_lights, n_dir, point_lights, n_point, nullptr, 0};
-    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, d_planes, stream, false);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, Lighting::kDirect, nullptr,
+                           nullptr, 0, planes_of(d_planes), stream);
 }
 
 int bih_render_lights(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
@@ -2636,66 +2673,36 @@ int bih_render_lights(const bih_tree *tr, const bih_camera *cam, uint32_t w, uin
                       uint32_t n_dir, const bih_point_light *point_lights, uint32_t n_point,
                       const bih_direct *host_planes) {
     const bih_light_set ls = {dir_lights, n_dir, point_lights, n_point, nullptr, 0};
-    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, host_planes, nullptr, true);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, &ls, Lighting::kDirect, nullptr,
+                           nullptr, 0, planes_of(host_planes), nullptr, &kDirectStage);
 }
 
 int bih_render_area_lights_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                                   uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                                   const bih_direct *d_planes, void *stream) {
-    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, d_planes, stream, false);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, Lighting::kDirect, nullptr,
+                           nullptr, 0, planes_of(d_planes), stream);
 }
 
 int bih_render_area_lights(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                            uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                            const bih_direct *host_planes) {
-    return render_light_set(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, host_planes, nullptr, true);
-}
-
-// The body of the two indirect-lighting entries, as render_light_set.
-static int render_indirect(const bih_tree *ctr, Frame f, const bih_rows *rows_in, const bih_light_set *ls_in,
-                           const bih_bounce *bounce, const bih_indirect *planes, void *stream, bool host) {
-    static const bih_light_set no_lights = {nullptr, 0, nullptr, 0, nullptr, 0};
-    const bih_light_set *ls = ls_in ? ls_in : &no_lights;
-    bih_direct three = {};
-    if (planes) three = bih_direct{planes->lit, planes->irradiance, planes->rgba};
-    int rc = light_set_check(ctr, &f, rows_in, ls, planes ? &three : nullptr, planes);
-    if (rc) return rc;
-    if (!bounce) return BIH_ERR_INVALID;
-    if (((uintptr_t)planes->lit2 & 7u) || ((uintptr_t)planes->bounce & 15u)) return BIH_ERR_INVALID;
-    if (f.rows.nrows == 0) return BIH_OK;
-    bih_tree *tr = const_cast<bih_tree *>(ctr);
-    DeviceGuard g(tr->t.device);
-    std::lock_guard<std::mutex> lk(tr->mu);
-    DirectJob dj;
-    merge_light_set(ls, f, &dj.lights);
-    dj.planes = three;
-    dj.indirect = true;
-    dj.bounce = *bounce;
-    dj.ind = *planes;
-    if (!host) return direct_locked(tr, f, dj, stream);
-    const size_t P = f.pixels(), S = (size_t)f.samples();
-    Stage<5> sg{{planes->lit, planes->bounce, planes->lit2, planes->irradiance, planes->rgba},
-                {S * 8, S * sizeof(bih_hit), S * 8, P * 4, P * 4}};
-    rc = sg.place(tr, &tr->in_stage, &tr->in_stage_cap);
-    if (rc) return rc;
-    dj.planes.lit = static_cast<uint64_t *>(sg.dev(0));
-    dj.ind.bounce = static_cast<bih_hit *>(sg.dev(1));
-    dj.ind.lit2 = static_cast<uint64_t *>(sg.dev(2));
-    dj.planes.irradiance = static_cast<float *>(sg.dev(3));
-    dj.planes.rgba = static_cast<uint32_t *>(sg.dev(4));
-    return sg.finish(tr, direct_locked(tr, f, dj, nullptr));
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, Lighting::kDirect, nullptr,
+                           nullptr, 0, planes_of(host_planes), nullptr, &kDirectStage);
 }
 
 int bih_render_indirect_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                                uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                                const bih_bounce *bounce, const bih_indirect *d_planes, void *stream) {
-    return render_indirect(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, bounce, d_planes, stream, false);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, Lighting::kGrey, bounce, nullptr, 1,
+                           planes_of(d_planes), stream);
 }
 
 int bih_render_indirect(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                         uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                         const bih_bounce *bounce, const bih_indirect *host_planes) {
-    return render_indirect(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, bounce, host_planes, nullptr, true);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, Lighting::kGrey, bounce, nullptr, 1,
+                           planes_of(host_planes), nullptr, &kIndirectStage);
 }
 
 int bih_bounce_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t spp, uint32_t s, const float n[3],
@@ -2706,60 +2713,18 @@ int bih_bounce_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t sp
     return BIH_OK;
 }
 
-// The body of the two path entries, as render_indirect.
-static int render_path(const bih_tree *ctr, Frame f, const bih_rows *rows_in, const bih_light_set *ls_in,
-                       const bih_bounce *bounce, uint32_t n_bounces, const bih_path *planes, void *stream, bool host) {
-    static_assert(BIH_MAX_BOUNCES == bih::kMaxBounces, "BIH_MAX_BOUNCES / kMaxBounces");
-    static const bih_light_set no_lights = {nullptr, 0, nullptr, 0, nullptr, 0};
-    const bih_light_set *ls = ls_in ? ls_in : &no_lights;
-    bih_direct three = {};
-    bih_indirect five = {};   // (the level planes in the places of bih_indirect's bounce and lit2)
-    if (planes) {
-        three = bih_direct{planes->lit, planes->irradiance, planes->rgba};
-        five = bih_indirect{planes->lit, planes->bounces, planes->lits, planes->irradiance, planes->rgba};
-    }
-    int rc = light_set_check(ctr, &f, rows_in, ls, planes ? &three : nullptr, planes ? &five : nullptr);
-    if (rc) return rc;
-    if (!bounce) return BIH_ERR_INVALID;
-    if (n_bounces == 0 || n_bounces > BIH_MAX_BOUNCES) return BIH_ERR_INVALID;
-    if (((uintptr_t)planes->lits & 7u) || ((uintptr_t)planes->bounces & 15u)) return BIH_ERR_INVALID;
-    if (f.rows.nrows == 0) return BIH_OK;
-    bih_tree *tr = const_cast<bih_tree *>(ctr);
-    DeviceGuard g(tr->t.device);
-    std::lock_guard<std::mutex> lk(tr->mu);
-    DirectJob dj;
-    merge_light_set(ls, f, &dj.lights);
-    dj.planes = three;
-    dj.indirect = true;
-    dj.bounce = *bounce;
-    dj.ind = five;
-    dj.n_bounces = n_bounces;
-    if (!host) return direct_locked(tr, f, dj, stream);
-    const size_t P = f.pixels(), S = (size_t)f.samples(), B = n_bounces;
-    Stage<5> sg{{planes->lit, planes->bounces, planes->lits, planes->irradiance, planes->rgba},
-                {S * 8, B * S * sizeof(bih_hit), B * S * 8, P * 4, P * 4}};
-    rc = sg.place(tr, &tr->pt_stage, &tr->pt_stage_cap);
-    if (rc) return rc;
-    dj.planes.lit = static_cast<uint64_t *>(sg.dev(0));
-    dj.ind.bounce = static_cast<bih_hit *>(sg.dev(1));
-    dj.ind.lit2 = static_cast<uint64_t *>(sg.dev(2));
-    dj.planes.irradiance = static_cast<float *>(sg.dev(3));
-    dj.planes.rgba = static_cast<uint32_t *>(sg.dev(4));
-    return sg.finish(tr, direct_locked(tr, f, dj, nullptr));
-}
-
 int bih_render_path_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                            uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                            const bih_bounce *bounce, uint32_t n_bounces, const bih_path *d_planes, void *stream) {
-    return render_path(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, bounce, n_bounces, d_planes, stream,
-                       false);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, Lighting::kGrey, bounce, nullptr,
+                           n_bounces, planes_of(d_planes), stream);
 }
 
 int bih_render_path(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t frame,
                     uint64_t seed, const bih_rows *rows, const bih_light_set *ls, const bih_bounce *bounce,
                     uint32_t n_bounces, const bih_path *host_planes) {
-    return render_path(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, bounce, n_bounces, host_planes, nullptr,
-                       true);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, Lighting::kGrey, bounce, nullptr,
+                           n_bounces, planes_of(host_planes), nullptr, &kPathStage);
 }
 
 int bih_tree_set_materials(bih_tree *tr, const bih_material *materials, uint32_t n_materials,
@@ -2802,82 +2767,32 @@ int bih_tree_set_materials(bih_tree *tr, const bih_material *materials, uint32_t
     return BIH_OK;
 }
 
-// The body of the two colour path entries, as render_path; spec: of the two
-// mirror path entries.
-static int render_path_rgb(const bih_tree *ctr, Frame f, const bih_rows *rows_in, const bih_light_set *ls_in,
-                           const float *sky, uint32_t n_bounces, const bih_path_rgb *planes, void *stream, bool host,
-                           bool spec = false) {
-    static const bih_light_set no_lights = {nullptr, 0, nullptr, 0, nullptr, 0};
-    const bih_light_set *ls = ls_in ? ls_in : &no_lights;
-    bih_direct three = {};    // (radiance in the place of irradiance: "all planes NULL" counts it)
-    bih_indirect five = {};
-    if (planes) {
-        three = bih_direct{planes->lit, planes->radiance, planes->rgba};
-        five = bih_indirect{planes->lit, planes->bounces, planes->lits, planes->radiance, planes->rgba};
-    }
-    int rc = light_set_check(ctr, &f, rows_in, ls, planes ? &three : nullptr, planes ? &five : nullptr);
-    if (rc) return rc;
-    if (!sky) return BIH_ERR_INVALID;
-    if (n_bounces == 0 || n_bounces > BIH_MAX_BOUNCES) return BIH_ERR_INVALID;
-    if (((uintptr_t)planes->lits & 7u) || ((uintptr_t)planes->bounces & 15u)) return BIH_ERR_INVALID;
-    if (f.rows.nrows == 0) return BIH_OK;
-    bih_tree *tr = const_cast<bih_tree *>(ctr);
-    DeviceGuard g(tr->t.device);
-    std::lock_guard<std::mutex> lk(tr->mu);
-    if (!tr->mt_pal) return BIH_ERR_INVALID;   // no materials: bih_tree_set_materials first
-    if (spec && !tr->mt_kinds_ok) return BIH_ERR_INVALID;
-    DirectJob dj;
-    merge_light_set(ls, f, &dj.lights);
-    dj.planes = bih_direct{planes->lit, nullptr, planes->rgba};
-    dj.indirect = true;
-    dj.bounce = bih_bounce{1.0f, 0.0f};
-    dj.ind = five;
-    dj.ind.irradiance = nullptr;
-    dj.n_bounces = n_bounces;
-    dj.rgb = true;
-    dj.spec = spec;
-    memcpy(dj.sky, sky, sizeof dj.sky);
-    dj.radiance = planes->radiance;
-    if (!host) return direct_locked(tr, f, dj, stream);
-    const size_t P = f.pixels(), S = (size_t)f.samples(), B = n_bounces;
-    Stage<5> sg{{planes->lit, planes->bounces, planes->lits, planes->radiance, planes->rgba},
-                {S * 8, B * S * sizeof(bih_hit), B * S * 8, P * 12, P * 4}};
-    rc = sg.place(tr, &tr->pc_stage, &tr->pc_stage_cap);
-    if (rc) return rc;
-    dj.planes.lit = static_cast<uint64_t *>(sg.dev(0));
-    dj.ind.bounce = static_cast<bih_hit *>(sg.dev(1));
-    dj.ind.lit2 = static_cast<uint64_t *>(sg.dev(2));
-    dj.radiance = static_cast<float *>(sg.dev(3));
-    dj.planes.rgba = static_cast<uint32_t *>(sg.dev(4));
-    return sg.finish(tr, direct_locked(tr, f, dj, nullptr));
-}
-
 int bih_render_path_rgb_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                                uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                                const float sky[3], uint32_t n_bounces, const bih_path_rgb *d_planes, void *stream) {
-    return render_path_rgb(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, sky, n_bounces, d_planes, stream,
-                           false);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, Lighting::kColour, nullptr, sky,
+                           n_bounces, planes_of(d_planes), stream);
 }
 
 int bih_render_path_rgb(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                         uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                         const float sky[3], uint32_t n_bounces, const bih_path_rgb *host_planes) {
-    return render_path_rgb(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, sky, n_bounces, host_planes, nullptr,
-                           true);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, Lighting::kColour, nullptr, sky,
+                           n_bounces, planes_of(host_planes), nullptr, &kColourStage);
 }
 
 int bih_render_path_spec_device(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                                 uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                                 const float sky[3], uint32_t n_bounces, const bih_path_rgb *d_planes, void *stream) {
-    return render_path_rgb(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, sky, n_bounces, d_planes, stream,
-                           false, true);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, Lighting::kMirror, nullptr, sky,
+                           n_bounces, planes_of(d_planes), stream);
 }
 
 int bih_render_path_spec(const bih_tree *tr, const bih_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
                          uint32_t frame, uint64_t seed, const bih_rows *rows, const bih_light_set *ls,
                          const float sky[3], uint32_t n_bounces, const bih_path_rgb *host_planes) {
-    return render_path_rgb(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, sky, n_bounces, host_planes, nullptr,
-                           true, true);
+    return render_lighting(tr, Frame{cam, w, h, spp, frame, seed, {}}, rows, ls, Lighting::kMirror, nullptr, sky,
+                           n_bounces, planes_of(host_planes), nullptr, &kColourStage);
 }
 
 // Argument checks of both denoise entries, in the header's order; none

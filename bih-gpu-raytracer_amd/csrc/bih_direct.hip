@@ -46,12 +46,10 @@
 // pixel, frame*spp + s, light), recomputed from the item's sample index in all
 // three kernels (area_dir), so a lane's walk state stays SRay's {o, d, i, k}.
 //
-// One-bounce indirect lighting (bih_render_indirect*) runs the stages twice,
-// with the bounce walk k_bounce between the levels: see IArgs below.
-//
-// Multi-bounce paths (bih_render_path*) run them once per level, list-driven
-// past the primary level, with the walk k_path_bounce between the levels: see
-// PArgs below.
+// Multi-bounce paths (bih_render_path*) run the stages once per level,
+// list-driven past the primary level, with the walk k_path_bounce between the
+// levels: see PArgs below.  One-bounce indirect lighting (bih_render_indirect*)
+// is that pipeline with one level past the primary one.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stddef.h>
@@ -438,229 +436,21 @@ __global__ void __launch_bounds__(kDSetupT) k_area_resolve(const AArgs a) {
     direct_resolve_body<kArea>(a.d, &a, s_light);
 }
 
-// ---- One-bounce indirect lighting (bih_render_indirect*) ----
-// Two levels of the stages above.  The primary level is bih_render_area_lights'
-// (k_indirect_setup is its setup, which also turns EVERY hit sample's record
-// into {P, sorted position} and lists the hit samples); k_bounce walks one
-// hashed, cosine-distributed ray per hit sample (bih_bounce.h) to its closest
-// hit and leaves {P2, sorted position} in rec2; k_indirect_setup2 is the setup
-// on those records; the secondary shadow pass is the primary's kernel, launched
-// on rec2 / lit2 (a secondary record keeps its sample's index, so sample_pixel
-// still gives the primary's (gp, s) for an area light's Q);
-// k_indirect_resolve sums both levels.  The setup and resolve kernels are the
-// kArea bodies for every light set (n_area, the lamps or all lights may be 0).
-struct IArgs {
-    AArgs a;                    // a.d: the primary level's rec, list, face, lit, count, cursor
-    uint4 *rec2;                // [P*spp]: the bounce hit's {P2, sorted position}; kNoHit: escaped, or a missed sample
-    unsigned long long *lit2;   // [P*spp]
-    uint4 *bounce;              // [P*spp] bih_hit, prim in file order, or null
-    uint32_t *blist;            // [P*spp]: hit samples
-    uint32_t *bcount;           // hit samples (zero at launch)
-    const uint32_t *tri_idx;    // sorted position -> file order
-    float albedo, sky;
-};
-
-// The wave's lanes with `on` take consecutive slots from *count: one atomic
-// per wave (all lanes of the wave call it).
-__device__ __forceinline__ uint32_t wave_append(bool on, uint32_t *count) {
-    const unsigned long long m = __ballot(on);
-    const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    uint32_t first = 0;
-    if (m && (threadIdx.x & (dev::kLanes - 1u)) == 0) first = atomicAdd(count, (uint32_t)__popcll(m));
-    return __builtin_amdgcn_readfirstlane(first) + rk;
-}
-
-__global__ void __launch_bounds__(kDSetupT) k_indirect_setup(const IArgs ia) {
-    const DArgs &a = ia.a.d;
-    const uint64_t P = (uint64_t)a.nrows * a.w;
-    const uint64_t n = P * a.spp;
-    const uint64_t i = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
-    unsigned long long face = 0ull;
-    uint32_t bi = kNoHit;
-    if (i < n) {
-        const uint4 h = a.rec[i];
-        bi = h.w;
-        if (bi != kNoHit) {
-            const uint64_t lp = i / a.spp;
-            const uint32_t s = (uint32_t)(i - lp * a.spp);
-            const uint32_t lr = (uint32_t)(lp / a.w), x = (uint32_t)(lp - (uint64_t)lr * a.w);
-            const uint32_t y = dev::global_row(lr, a.row0, a.band_h, a.band_step);
-            float d[3], nrm[3], pt[3];
-            dev::primary_dir(a.cam, a.rng_in, P, lp, a.d_base, s, x, y, a.w, a.h, d);
-            const float t = __uint_as_float(h.x);
-            for (int k = 0; k < 3; ++k) pt[k] = a.cam[k] + t * d[k];
-            dev::tri_normal(a.tris + 9ull * bi, nrm);
-            face = facing_mask<kArea>(a, &ia.a, nrm, pt, y * a.w + x, s);
-            a.rec[i] = make_uint4(__float_as_uint(pt[0]), __float_as_uint(pt[1]), __float_as_uint(pt[2]), bi);
-        } else {   // a missed sample has no bounce: the miss record, lit2 = 0 (k_indirect_setup2)
-            ia.rec2[i] = make_uint4(0u, 0u, 0u, kNoHit);
-            if (ia.bounce) ia.bounce[i] = make_uint4(__float_as_uint(FLT_MAX), 0u, 0u, kNoHit);
-        }
-        a.lit[i] = 0ull;
-    }
-    const uint32_t jb = wave_append(bi != kNoHit, ia.bcount);
-    if (bi != kNoHit) ia.blist[jb] = (uint32_t)i;
-    const uint32_t j = wave_append(face != 0ull, a.count);
-    if (face != 0ull) {
-        a.list[j] = (uint32_t)i;
-        a.face[j] = face;
-    }
-}
-
-// A bounce ray: where it starts, whose it is, and its walk.
-struct BRay {
-    float o[3];
-    uint32_t i;                 // sample
-    ClosestRay w;
-};
-
-// The bounce's result: {P2, sorted position} for the secondary level, and the
-// caller's bih_hit (tray_write's: u, v from the accepted triangle's test once
-// more, prim in file order).
-__device__ __forceinline__ void bray_write(const IArgs &ia, const ClosestScene &s, const BRay &r) {
-    float t = FLT_MAX, u = 0.0f, v = 0.0f;
-    uint32_t prim = kNoHit;
-    uint4 q2 = make_uint4(0u, 0u, 0u, kNoHit);
-    if (r.w.bi != kNoHit) {
-        (void)dev::mt_tuv(s.tris + 9ull * r.w.bi, r.o, r.w.d, t, u, v);
-        prim = ia.tri_idx[r.w.bi];
-        q2 = make_uint4(__float_as_uint(r.o[0] + t * r.w.d[0]), __float_as_uint(r.o[1] + t * r.w.d[1]),
-                        __float_as_uint(r.o[2] + t * r.w.d[2]), r.w.bi);
-    }
-    ia.rec2[r.i] = q2;
-    if (ia.bounce) ia.bounce[r.i] = make_uint4(__float_as_uint(t), __float_as_uint(u), __float_as_uint(v), prim);
-}
-
-// The bounce walk, k_trace's shape: persistent one-wave blocks; work item = a
-// hit sample of blist, taken from the global cursor; a lane whose walk has
-// ended takes the next item while its wave-mates keep walking.  No ray goes
-// through memory: the origin is the sample's P, the direction bih_bounce.h's
-// hash about its triangle's normal.  The walk is bih_closest.h's closest walk.
-template <int LDS>
-__global__ void __launch_bounds__(kDT) k_bounce(const IArgs ia) {
-    __shared__ uint32_t s_node[LDS * kDT];
-    __shared__ float s_min[LDS * kDT];
-    __shared__ float s_max[LDS * kDT];
-    const DArgs &a = ia.a.d;
-    const uint32_t lane = threadIdx.x;
-    const dev::LaneStack<LDS> stk(s_node, s_min, s_max, a.spill);
-    const ClosestScene sc = dev::load_closest_scene(a.hdr, a.nodes, a.tris, a.dup);
-    const uint64_t n = *ia.bcount;
-    BRay r;
-    bool has = false;          // this lane walks a ray
-    bool more = true;          // (wave-uniform) the cursor may still be short of n
-    for (;;) {
-        const unsigned long long idle = __ballot(!has);
-        if (more && (__popcll(idle) >= kDRefill || idle == ~0ull)) {
-            const uint32_t cnt = (uint32_t)__popcll(idle);
-            unsigned long long first = 0;
-            if (lane == 0) first = atomicAdd(a.cursor, (unsigned long long)cnt);
-            first = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(first >> 32)) << 32) |
-                    __builtin_amdgcn_readfirstlane((uint32_t)first);
-            if (first + cnt >= n) more = false;
-            if (!has) {
-                const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
-                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                if (first + rk < n) {
-                    r.i = ia.blist[first + rk];
-                    const uint4 q = a.rec[r.i];   // {P, sorted position}: k_indirect_setup
-                    r.o[0] = __uint_as_float(q.x); r.o[1] = __uint_as_float(q.y); r.o[2] = __uint_as_float(q.z);
-                    float nrm[3];
-                    dev::tri_normal(a.tris + 9ull * q.w, nrm);
-                    uint32_t s;
-                    const uint32_t gp = sample_pixel(a, r.i, &s);
-                    bounce_dir(ia.a.hseed, gp, ia.a.fs0 + s, kBounceSlot, nrm, r.w.d);
-                    has = dev::closest_start<dev::kWalkClosest>(sc, r.w, r.o, kShadowTLo);
-                    if (!has) bray_write(ia, sc, r);   // missed the box / one-leaf tree: final
-                }
-            }
-        }
-        if (!__ballot(has)) {
-            if (!more) break;
-            continue;
-        }
-        if (has) {
-            bool fin = false;
-            for (int k = 0; k < kDSteps && !fin; ++k)
-                fin = dev::closest_step<dev::kWalkClosest>(sc, r.w, r.o, kShadowTLo, stk);
-            if (fin) {
-                bray_write(ia, sc, r);
-                has = false;
-            }
-        }
-    }
-}
-
-__global__ void __launch_bounds__(kDSetupT) k_indirect_setup2(const IArgs ia) {
-    const DArgs &a = ia.a.d;
-    const uint64_t n = (uint64_t)a.nrows * a.w * a.spp;
-    const uint64_t i = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
-    unsigned long long face = 0ull;
-    if (i < n) {
-        const uint4 h = ia.rec2[i];
-        if (h.w != kNoHit && a.n_lights) {
-            const float pt[3] = {__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(h.z)};
-            float nrm[3];
-            dev::tri_normal(a.tris + 9ull * h.w, nrm);
-            uint32_t s;
-            const uint32_t gp = sample_pixel(a, (uint32_t)i, &s);
-            face = facing_mask<kArea>(a, &ia.a, nrm, pt, gp, s);
-        }
-        ia.lit2[i] = 0ull;
-    }
-    const uint32_t j = wave_append(face != 0ull, a.count);
-    if (face != 0ull) {
-        a.list[j] = (uint32_t)i;
-        a.face[j] = face;
-    }
-}
-
-__global__ void __launch_bounds__(kDSetupT) k_indirect_resolve(const IArgs ia) {
-    __shared__ DLight s_light[kMaxLights];
-    const DArgs &a = ia.a.d;
-    if (threadIdx.x < a.n_lights) s_light[threadIdx.x] = a.lights[threadIdx.x];
-    __syncthreads();
-    const uint64_t P = (uint64_t)a.nrows * a.w;
-    const uint64_t lp = (uint64_t)blockIdx.x * kDSetupT + threadIdx.x;
-    if (lp >= P) return;
-    const uint32_t lr = (uint32_t)(lp / a.w), px = (uint32_t)(lp - (uint64_t)lr * a.w);
-    const uint32_t gp = dev::global_row(lr, a.row0, a.band_h, a.band_step) * a.w + px;
-    float E = 0.0f;
-    bool any = false;
-    for (uint32_t s = 0; s < a.spp; ++s) {
-        const uint64_t i = lp * a.spp + s;
-        const uint32_t bi = a.rec[i].w;
-        float e = 0.0f;
-        if (bi != kNoHit) {
-            any = true;
-            const float e_dir = sample_sum<kArea>(a, &ia.a, s_light, a.rec + i, bi, a.lit[i], gp, s);
-            const uint32_t bi2 = ia.rec2[i].w;
-            float e_ind = ia.sky;   // an escaped bounce
-            if (bi2 != kNoHit)
-                e_ind = ia.albedo * sample_sum<kArea>(a, &ia.a, s_light, ia.rec2 + i, bi2, ia.lit2[i], gp, s);
-            e = e_dir + e_ind;
-        }
-        E = s == 0 ? e : E + e;
-    }
-    E = E / (float)a.spp;
-    if (a.irradiance) a.irradiance[lp] = E;
-    if (a.rgba) {
-        const uint32_t g = (uint32_t)(int)fmaxf(0.0f, fminf(255.0f, 255.0f * E));
-        a.rgba[lp] = any ? (g | (g << 8) | (g << 16)) : kMissShade;
-    }
-}
-
-// ---- Multi-bounce paths (bih_render_path*) ----
+// ---- Multi-bounce paths (bih_render_path*; with one level,
+// bih_render_indirect*, 4.5.6) ----
 // The stages above once per level, list-driven past the primary one.  Level 0
-// is bih_render_indirect's primary level (k_path_setup0: every hit sample's
-// record becomes {P, sorted position}, the hit samples are level 0's live
-// list).  Level k = 1..n_bounces: k_path_bounce walks one hashed ray (slot
-// kBounceSlot + k - 1) per sample of level k-1's live list, reads its record
-// from one of two record buffers and leaves {P_k, sorted position} in the
-// other, appends the samples it stopped to level k's live list and adds an
-// escaped sample's thr_{k-1} * sky; k_path_setup lists the live samples a
-// light faces for the shadow pass, which is the kernels above on the level's
-// records and lit plane; k_path_accum adds thr_k * e_k.  The sums go forward
+// is bih_render_area_lights' primary level for every light set (n_area, the
+// lamps or all lights may be 0; k_path_setup0: every hit sample's record
+// becomes {P, sorted position}, the hit samples are level 0's live list).
+// Level k = 1..n_bounces: k_path_bounce walks one hashed, cosine-distributed
+// ray (bih_bounce.h, slot kBounceSlot + k - 1) per sample of level k-1's live
+// list to its closest hit, reads its record from one of two record buffers and
+// leaves {P_k, sorted position} in the other, appends the samples it stopped to
+// level k's live list and adds an escaped sample's thr_{k-1} * sky;
+// k_path_setup lists the live samples a light faces for the shadow pass, which
+// is the kernels above on the level's records and lit plane (a record keeps its
+// sample's index, so sample_pixel still gives the primary's (gp, s) for an area
+// light's Q); k_path_accum adds thr_k * e_k.  The sums go forward
 // into one f32 per sample (acc), so k_path_resolve needs no level's data.
 // thr_k is the same for every sample alive at level k: it travels as a scalar.
 struct PArgs {
@@ -683,8 +473,20 @@ struct PArgs {
 constexpr uint32_t kPListBlocks = 2048;   // the list-driven kernels' grid cap (they stride)
 constexpr uint32_t kMatMirror = 1u;       // BIH_MAT_MIRROR (bih_render_path_spec*, section 4.5.9)
 
-// Level 0's setup over every sample of the call: k_indirect_setup's, which
-// also starts the sample's sum and notes whether it hit.
+// The wave's lanes with `on` take consecutive slots from *count: one atomic
+// per wave (all lanes of the wave call it).
+__device__ __forceinline__ uint32_t wave_append(bool on, uint32_t *count) {
+    const unsigned long long m = __ballot(on);
+    const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    uint32_t first = 0;
+    if (m && (threadIdx.x & (dev::kLanes - 1u)) == 0) first = atomicAdd(count, (uint32_t)__popcll(m));
+    return __builtin_amdgcn_readfirstlane(first) + rk;
+}
+
+// Level 0's setup over every sample of the call: the area setup's point, normal
+// and facing mask for every light set; EVERY hit sample's record becomes {P,
+// sorted position} and joins level 0's live list, the ones a light faces also
+// the shadow list; lit = 0, the sample's sum starts and whether it hit is noted.
 // Shared with the mirror paths (k_path_spec_setup0, section 4.5.9), which pass
 // their argument block as `sa`: a mirror hit faces no light, and the sample's
 // record of incoming direction and kind starts here.
@@ -735,10 +537,18 @@ __global__ void __launch_bounds__(kDSetupT) k_path_setup0(const PArgs pa) {
     path_setup0_body<void>(pa, nullptr);
 }
 
+// A bounce ray: where it starts, whose it is, and its walk.
+struct BRay {
+    float o[3];
+    uint32_t i;                 // sample
+    ClosestRay w;
+};
+
 // The end of a level's walk for the lane's sample: a stopped ray leaves {P_k,
 // sorted position} in the level's record buffer and stays alive (returns true);
-// an escaped one collects thr_{k-1} * sky and ends.  The caller's bih_hit as
-// bray_write's.
+// an escaped one collects thr_{k-1} * sky and ends.  The caller's bih_hit is
+// bih_trace's: u, v from the accepted triangle's test once more, prim in file
+// order; the miss record for an escape.
 __device__ __forceinline__ bool pray_write(const PArgs &pa, const ClosestScene &s, const BRay &r) {
     const bool stopped = r.w.bi != kNoHit;
     float t = FLT_MAX, u = 0.0f, v = 0.0f;
@@ -859,10 +669,12 @@ __device__ __forceinline__ void path_ray_dir(const X &x, const PArgs &pa, uint32
     bounce_dir(pa.a.hseed, gp, pa.a.fs0 + s, pa.slot, nrm, d);
 }
 
-// A level's bounce walk, k_bounce's shape: persistent one-wave blocks; work
+// A level's bounce walk, k_trace's shape: persistent one-wave blocks; work
 // item = a sample of the level before's live list, taken from the global
 // cursor; a lane whose walk has ended takes the next item while its wave-mates
-// keep walking.  The lanes whose walks ended in one round write together, so
+// keep walking.  No ray goes through memory: the origin is the sample's P, the
+// direction path_ray_dir's.  The walk is bih_closest.h's closest walk.
+// The lanes whose walks ended in one round write together, so
 // that the stopped ones take consecutive slots of the level's live list with
 // one atomic (wave_append needs the whole wave).
 // The walk is shared with the colour paths (k_path_rgb_bounce, section 4.5.8)
@@ -1202,64 +1014,6 @@ int launch_direct(const DeviceTree &t, const RenderArgs &ra, const DirectPlanes 
     return (int)e;
 }
 
-// The call's passes, each behind the one before on the stream: the primary
-// setup, the primary shadow pass, the bounce walk, the secondary setup, the
-// secondary shadow pass (the primary's kernels on the secondary records; list,
-// face, count and cursor are the primary's, free again), the resolve.
-int launch_indirect(const DeviceTree &t, const RenderArgs &ra, const IndirectPlanes &p, const Lights &l, float albedo,
-                    float sky, const Scratch &s, const WorkArea &wa, void *stream) {
-    const hipStream_t st = (hipStream_t)stream;
-    if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0) return 0;
-    if (l.n_lights > kMaxLights || l.n_dir > l.n_lights) return (int)hipErrorInvalidValue;
-    if (l.area.n > kMaxAreaLights || l.area.n > l.n_lights - l.n_dir) return (int)hipErrorInvalidValue;
-    static_assert(sizeof(IArgs) <= 4096, "kernel arguments");
-    IArgs ia;
-    fill_args(ia.a, t, ra, l, p, s, wa);
-    const DArgs &a = ia.a.d;
-    ia.rec2 = reinterpret_cast<uint4 *>(s.rec2);
-    ia.lit2 = p.lit2;
-    ia.bounce = reinterpret_cast<uint4 *>(p.bounce);
-    ia.blist = s.blist;
-    ia.bcount = wa.word(kCurBounce);
-    ia.tri_idx = t.vals;
-    ia.albedo = albedo;
-    ia.sky = sky;
-    const uint64_t P = (uint64_t)ra.nrows * ra.w, n = P * ra.spp;
-    const dim3 sgrid((uint32_t)((n + kDSetupT - 1) / kDSetupT));
-    hipError_t e = reset_counts(a, st);
-    if (e == hipSuccess) e = hipMemsetAsync(ia.bcount, 0, sizeof(uint32_t), st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_indirect_setup, sgrid, dim3(kDSetupT), 0, st, ia);
-    e = hipGetLastError();
-    if (e == hipSuccess && l.n_lights) e = launch_shadow(ia.a, l.area.n, n, wa.lds_slots, wa.max_blocks, st);
-    if (e == hipSuccess) e = hipMemsetAsync(a.cursor, 0, sizeof(unsigned long long), st);
-    if (e != hipSuccess) return (int)e;
-    {
-        const uint64_t need = (n + kDT - 1) / kDT;
-        const dim3 grid((uint32_t)(need < wa.max_blocks ? need : wa.max_blocks)), block(kDT);
-        if (wa.lds_slots == (uint32_t)kTraceLdsTest) hipLaunchKernelGGL((k_bounce<kTraceLdsTest>), grid, block, 0, st, ia);
-        else hipLaunchKernelGGL((k_bounce<kTraceLds>), grid, block, 0, st, ia);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = reset_counts(a, st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_indirect_setup2, sgrid, dim3(kDSetupT), 0, st, ia);
-    e = hipGetLastError();
-    if (e == hipSuccess && l.n_lights) {
-        AArgs a2 = ia.a;       // the secondary level: its records and lit words
-        a2.d.rec = ia.rec2;
-        a2.d.lit = ia.lit2;
-        e = launch_shadow(a2, l.area.n, n, wa.lds_slots, wa.max_blocks, st);
-    }
-    if (e != hipSuccess) return (int)e;
-    if (p.irradiance || p.rgba) {
-        const dim3 rgrid((uint32_t)((P + kDSetupT - 1) / kDSetupT));
-        hipLaunchKernelGGL(k_indirect_resolve, rgrid, dim3(kDSetupT), 0, st, ia);
-        e = hipGetLastError();
-    }
-    return (int)e;
-}
-
 // The call's passes, each behind the one before on the stream: the fill of the
 // caller's level planes, level 0's setup, shadow pass and sum, then per level
 // the bounce walk, the setup, the shadow pass and the sum, and the resolve.
@@ -1279,10 +1033,10 @@ int launch_indirect(const DeviceTree &t, const RenderArgs &ra, const IndirectPla
 // c->dk (a mirror call, else null): the mirror paths' setups and walk take the
 // places of the grey setups and the colour walk; every other launch is the
 // colour call's.
-static int launch_path_levels(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l,
-                              float albedo, float sky, uint32_t n_bounces, const Scratch &s, const WorkArea &wa,
-                              void *stream, const PathRgb *c) {
+int launch_path(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l, float albedo, float sky,
+                uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream, const PathRgb *c) {
     const hipStream_t st = (hipStream_t)stream;
+    if (c && (!c->palette || !c->acc3 || !c->thr3)) return (int)hipErrorInvalidValue;
     if (ra.nrows == 0 || ra.w == 0 || ra.spp == 0) return 0;
     if (l.n_lights > kMaxLights || l.n_dir > l.n_lights) return (int)hipErrorInvalidValue;
     if (l.area.n > kMaxAreaLights || l.area.n > l.n_lights - l.n_dir) return (int)hipErrorInvalidValue;
@@ -1389,23 +1143,6 @@ static int launch_path_levels(const DeviceTree &t, const RenderArgs &ra, const P
         e = hipGetLastError();
     }
     return (int)e;
-}
-
-int launch_path(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l, float albedo, float sky,
-                uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream) {
-    return launch_path_levels(t, ra, p, l, albedo, sky, n_bounces, s, wa, stream, nullptr);
-}
-
-int launch_path_rgb(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l, const PathRgb &c,
-                    uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream) {
-    if (!c.palette || !c.acc3 || !c.thr3 || c.dk) return (int)hipErrorInvalidValue;
-    return launch_path_levels(t, ra, p, l, 1.0f, 0.0f, n_bounces, s, wa, stream, &c);
-}
-
-int launch_path_spec(const DeviceTree &t, const RenderArgs &ra, const PathPlanes &p, const Lights &l, const PathRgb &c,
-                     uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream) {
-    if (!c.palette || !c.acc3 || !c.thr3 || !c.dk) return (int)hipErrorInvalidValue;
-    return launch_path_levels(t, ra, p, l, 1.0f, 0.0f, n_bounces, s, wa, stream, &c);
 }
 
 }  // namespace bih

@@ -387,7 +387,7 @@ int whitted_work(const void *mem, uint64_t rays, uint32_t ray_counts[9], unsigne
 constexpr uint32_t kCurTaken = 0;    // u32: rays (launch_trace) / tiles (launch_gbuffer) taken
 constexpr uint32_t kCurItems = 2;    // u64: shadow / bounce items taken
 constexpr uint32_t kCurListed = 4;   // u32: listed samples
-constexpr uint32_t kCurBounce = 6;   // u32: samples whose bounce hit / a path's live samples, even levels
+constexpr uint32_t kCurBounce = 6;   // u32: a path's live samples, even levels
 constexpr uint32_t kCurBounce2 = 7;  // u32: a path's live samples, odd levels
 constexpr size_t kTraceCursorBytes = ((kCurBounce2 + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
 struct WorkArea {
@@ -453,9 +453,9 @@ struct Lights {
     AreaLights area;
 };
 // Per-sample scratch of a lighting launch (device; P*spp entries each): rec
-// (16 bytes), list (u32), face (u64); one-bounce launches also rec2 (16
-// bytes) and blist (u32) of the second level; path launches also the second
-// live list blist2 (u32), the samples' sums acc (f32) and hit0 (one byte).
+// (16 bytes), list (u32), face (u64); path launches also the second record
+// buffer rec2 (16 bytes), the two live lists blist and blist2 (u32), the
+// samples' sums acc (f32) and hit0 (one byte).
 struct Scratch {
     void *rec = nullptr;
     uint32_t *list = nullptr;
@@ -473,38 +473,28 @@ struct DirectPlanes {
 };
 int launch_direct(const DeviceTree &t, const RenderArgs &a, const DirectPlanes &p, const Lights &l, const Scratch &s,
                   const WorkArea &wa, void *stream);
-// One-bounce indirect lighting (bih_direct.hip), behind a launch_gbuffer as
-// launch_direct: the primary level as there (n_lights may be 0: sky only),
-// then per hit sample one bounce ray (bih_bounce.h; area.hseed and area.fs0
-// are read whatever area.n), its hit lit by the same lights, and the sums of
-// both levels.  lit and lit2 are never null.
-struct IndirectPlanes : DirectPlanes {
-    void *bounce = nullptr;             // bih_hit[P*spp], prim in file order, or null
-    unsigned long long *lit2 = nullptr;
-};
-int launch_indirect(const DeviceTree &t, const RenderArgs &a, const IndirectPlanes &p, const Lights &l, float albedo,
-                    float sky, const Scratch &s, const WorkArea &wa, void *stream);
-// Multi-bounce paths (bih_direct.hip), behind a launch_gbuffer as
-// launch_indirect: level 0 as there, then n_bounces (1 .. kMaxBounces) levels
-// of one bounce ray per sample still alive.  bounces and lits (either may be
-// null) hold one plane of P*spp per level 1..n_bounces; lit_scratch
-// (u64[P*spp], never null when lits is) stands in for a level's lit plane.
+// Multi-bounce paths (bih_direct.hip; bih_render_path*, and with n_bounces = 1
+// bih_render_indirect*), behind a launch_gbuffer as launch_direct: level 0 as
+// there (n_lights may be 0: sky only; lit is never null), then n_bounces (1 ..
+// kMaxBounces) levels of one bounce ray per sample still alive (bih_bounce.h;
+// area.hseed and area.fs0 are read whatever area.n), its hit lit by the same
+// lights, and the sums of all levels.  bounces (bih_hit, prim in file order) and
+// lits (either may be null) hold one plane of P*spp per level 1..n_bounces;
+// lit_scratch (u64[P*spp], never null when lits is) stands in for a level's lit
+// plane.  albedo, sky: the grey call's (c == null).
+// Colour paths (bih_render_path_rgb*): c, a material per triangle.  palette: two
+// float4 per material (bih_material); ids: u32 per file-order triangle, or null
+// (material 0); acc3, thr3: 16 bytes per sample each; radiance: f32[3P] or null
+// (p.irradiance is not written); palette, acc3 or thr3 null: an error.
+// Mirror paths (bih_render_path_spec*): c->dk non-null, 16 bytes per sample ({D,
+// kind} of the sample's latest hit); the palette's kinds are BIH_MAT_DIFFUSE or
+// BIH_MAT_MIRROR (the caller's check).  With dk == null no kind is ever read.
 constexpr uint32_t kMaxBounces = 8;   // BIH_MAX_BOUNCES
 struct PathPlanes : DirectPlanes {
     void *bounces = nullptr;
     unsigned long long *lits = nullptr;
     unsigned long long *lit_scratch = nullptr;
 };
-int launch_path(const DeviceTree &t, const RenderArgs &a, const PathPlanes &p, const Lights &l, float albedo, float sky,
-                uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream);
-// Colour paths (bih_direct.hip; bih_render_path_rgb*): launch_path with a
-// material per triangle.  palette: two float4 per material (bih_material); ids:
-// u32 per file-order triangle, or null (material 0); acc3, thr3: 16 bytes per
-// sample each; radiance: f32[3P] or null (p.irradiance is not written).
-// Mirror paths (bih_render_path_spec*): launch_path_spec, the same with dk, 16
-// bytes per sample ({D, kind} of the sample's latest hit); the palette's kinds
-// are BIH_MAT_DIFFUSE or BIH_MAT_MIRROR (the caller's check).  launch_path_rgb
-// takes dk == null only and never reads a kind.
 struct PathRgb {
     const void *palette = nullptr;
     const uint32_t *ids = nullptr;
@@ -514,10 +504,8 @@ struct PathRgb {
     float *radiance = nullptr;
     float sky[3] = {0.0f, 0.0f, 0.0f};
 };
-int launch_path_rgb(const DeviceTree &t, const RenderArgs &a, const PathPlanes &p, const Lights &l, const PathRgb &c,
-                    uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream);
-int launch_path_spec(const DeviceTree &t, const RenderArgs &a, const PathPlanes &p, const Lights &l, const PathRgb &c,
-                     uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream);
+int launch_path(const DeviceTree &t, const RenderArgs &a, const PathPlanes &p, const Lights &l, float albedo, float sky,
+                uint32_t n_bounces, const Scratch &s, const WorkArea &wa, void *stream, const PathRgb *c);
 // Denoiser (bih_denoise.hip; bih_denoise*): the edge-avoiding a-trous filter of
 // a whole w x h frame.  scratch: kDenoisePixelBytes per pixel, four planes of
 // 16-byte records -- {Pos, valid}, {n, 0} and two colour records (pass i reads

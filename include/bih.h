@@ -696,10 +696,12 @@ int bih_area_light_sample(const bih_area_light *light, uint32_t j, uint64_t seed
  * NULL, lit2 not 8-byte aligned or the bounce plane not 16-byte aligned ->
  * BIH_ERR_INVALID; nrows == 0 -> BIH_OK, nothing launched.
  * RNG accounting, ordering (the ev_trace chain, rebuilds) and memory are
- * bih_render_direct's.  Scratch: next to its 28 bytes per sample 20 more (the
- * bounce's record and a hit-list entry), and 8 more (the lit2 word) once a call
- * passes no `lit2`.  After the first call of a shape, light count and choice
- * of planes further calls allocate nothing. */
+ * bih_render_direct's.  Scratch: next to its 28 bytes per sample 29 more (the
+ * bounce's record and a hit-list entry, 20; and, since the call runs
+ * bih_render_path's levels with n_bounces = 1, that call's 9: the sample's sum,
+ * an entry of a second live list, a hit flag), and 8 more (the lit2 word) once a
+ * call passes no `lit2`.  After the first call of a shape, light count and
+ * choice of planes further calls allocate nothing. */
 #define BIH_BOUNCE_SLOT 0x80000000u   /* the hash slot of the bounce direction: no area light index takes it */
 typedef struct bih_bounce {
     float albedo;   /* the diffuse reflectance applied to the bounced light */
@@ -786,8 +788,8 @@ int bih_bounce_sample(uint64_t seed, uint32_t pixel, uint32_t frame, uint32_t sp
  * BIH_MAX_BOUNCES -> BIH_ERR_INVALID.  The alignment checks are lit and lits
  * (8 bytes) and bounces (16 bytes).  nrows == 0 -> BIH_OK, nothing launched.
  * RNG accounting, ordering (the ev_trace chain, rebuilds) and memory are
- * bih_render_indirect's.  Scratch: next to its 48 bytes per sample 9 more (the
- * sample's sum, an entry of a second live list, a hit flag), and 8 more (one
+ * bih_render_indirect's.  Scratch: its 57 bytes per sample (48 and the 9 of
+ * the sample's sum, an entry of a second live list, a hit flag), and 8 more (one
  * lit word, reused by every level) once a call passes no `lits`; two record
  * buffers and two live lists serve every n_bounces.  All of it is counted in
  * bih_tree_info.device_bytes.  After the first call of a shape, light set,

@@ -532,7 +532,7 @@ def test_shapes(w, h, spp, gpu, bihrt_mod):
 @pytest.mark.gpu
 def test_more_hit_samples_than_the_persistent_grid(gpu, bihrt_mod):
     """A frame whose hit samples exceed the persistent grid x 64 lanes, so that
-    k_bounce's waves come back for more: its planes equal the same frame
+    the bounce walk's waves come back for more: its planes equal the same frame
     assembled from bands of 32 rows, each far below the grid (gp is global, so
     bands reassemble; the small shapes above tie a band to the oracle)."""
     import torch
@@ -561,7 +561,8 @@ def test_rows_bands_planes_and_host_entry(gpu, bihrt_mod):
     """Interleaved bands and rows that are not tile-aligned equal the same rows
     of the full frame, through both entries (the hash takes the GLOBAL pixel);
     each plane alone gives the bits of all together and leaves the others
-    untouched; no call after the first of the shape allocates."""
+    untouched; no call after the first of the shape allocates, and a fresh
+    tree's first call takes at least the header's scratch per sample."""
     exp = expect("soup20k", "K2", W, H, SPP, 1)
     g = tree("soup20k")
     r = renderer(g, "soup20k", "K2", W, H, SPP)
@@ -588,6 +589,13 @@ def test_rows_bands_planes_and_host_entry(gpu, bihrt_mod):
                   names=("irradiance",))
     after = g.info()
     assert after.device_allocs == first.device_allocs and after.device_bytes == first.device_bytes
+    # a fresh tree's first five-plane call: the header's 28 + 20 + 9 bytes of scratch per sample
+    fresh = bihrt_mod.GPUArrayManager(scene("soup20k")[0])
+    rf = renderer(fresh, "soup20k", "K2", W, H, SPP)
+    before = fresh.info()
+    assert_planes(dev_indirect(rf, dl, lp, pan, 1), exp, "fresh tree")
+    assert fresh.info().device_bytes >= before.device_bytes + W * H * SPP * 57
+    fresh.close()
 
 
 @pytest.mark.gpu
