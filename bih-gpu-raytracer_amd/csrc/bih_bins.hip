@@ -69,7 +69,7 @@ constexpr int kThreads = 256;
 
 // The camera's primary-ray records and its alive triangles (a thread per
 // Morton-ordered triangle i and per internal node i):
-//   - the triangle record (dev::tri_prim_record; bih_render.hip's k_tri_prim)
+//   - the triangle record (dev::tri_prim_record; bih_prim.hip's k_tri_prim)
 //     and the camera-relative node record (k_node_prim's, no culled set);
 //   - which triangles a primary ray from the camera can hit (tnum_alive:
 //     about half of a soup, the other half faces away): per block a 256-bit

@@ -1,5 +1,5 @@
 // bih_bound.h -- the rounding bound of the primary-ray intersector shared by
-// the any-hit walk's miss-proof boxes (bih_render.hip, miss_box) and the
+// the any-hit walk's miss-proof boxes (bih_prim.hip, miss_box) and the
 // frustum bins (bih_bins.hip).
 //
 // For one alive triangle's primary-ray record r = {e1, e2, s = O - v0,

@@ -52,7 +52,7 @@ constexpr size_t kPathSampleBytes = 4 + 4 + 1;          // pt_mem per sample: su
 constexpr size_t kPathRgbSampleBytes = 16 + 16;         // pc_mem per sample: RGB sum record, RGB throughput record
 constexpr size_t kPathSpecSampleBytes = 16;             // ps_mem per sample: {D, kind} of the latest hit
 
-// Per-camera structures (bih_render.hip / bih_bins.hip): primary-ray records,
+// Per-camera structures (bih_prim.hip / bih_bins.hip): primary-ray records,
 // frustum bins and the tile queue of one camera.  A tree keeps kCamSets of
 // them: a camera change builds into a set the latest render does not read,
 // after only the renders that read that set -- so camera k+1's structures
@@ -502,7 +502,7 @@ int wait_set_readers(bih_tree *tr, int c, hipStream_t st) {
     return BIH_OK;
 }
 
-// The any-hit walk's shortcut passes (k_render_packet_asm, bih_render.hip):
+// The any-hit walk's shortcut passes (k_render_packet_asm, bih_walk.hip):
 // 2 = hit shortcut + miss proof (default), BIH_FAST=1 the hit shortcut only,
 // BIH_FAST=0 neither (A-B).  They never change a pixel.
 int fast_enabled() {

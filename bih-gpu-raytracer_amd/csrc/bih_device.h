@@ -1,5 +1,5 @@
 // bih_device.h -- device helpers shared by the render kernels
-// (bih_render.hip) and the Whitted path (bih_whitted.hip).  Every f32
+// (bih_ray.h) and the Whitted path (bih_whitted.hip).  Every f32
 // expression is the reference's, in its order (compiled -ffp-contract=off).
 #pragma once
 #include "bih_internal.h"

@@ -249,7 +249,7 @@ struct RenderArgs {
 
 // Packet tiles of a w x nrows launch with spp samples per pixel (a power of
 // two <= 64): tw x th pixels with tw * th * spp = 64 (the kernels'
-// TileShape<log2 spp>, bih_render.hip), x across and y down.
+// TileShape<log2 spp>, bih_ray.h), x across and y down.
 struct Tiles {
     uint32_t tw, th, x, y;
     constexpr uint64_t count() const { return (uint64_t)x * y; }
@@ -355,7 +355,7 @@ struct DeviceTree {
 int build_tree_device(DeviceTree &t, void *stream, float *ms_out, bool sync = true);
 void free_tree_device(DeviceTree &t);
 
-// render (bih_render.hip)
+// render (bih_rng.hip, bih_prim.hip, bih_walk.hip, bih_render.hip)
 int upload_rng_tables(int device);
 long bins_timeline_dump(const char *path);         // diagnostic builds (BIH_BINS_TIMELINE)
 // stamped XORWOW state (RenderArgs::stamps): every tile's stamp = frame F in
@@ -533,6 +533,8 @@ int launch_rng_advance(const uint32_t *src, uint32_t *dst, uint64_t pixels, uint
 // main render kernel (bih_last_render_ms)
 int launch_render(const RenderArgs &a, uint32_t traverse, void *stream, void *ev_k0 = nullptr,
                   void *ev_k1 = nullptr);
+// launch_render's renders without frustum bins (bih_walk.hip)
+int launch_walk(const RenderArgs &a, uint32_t traverse, void *stream, void *ev_k0, void *ev_k1);
 uint32_t wave_grid_blocks(int device);     // persistent grid of the render kernels
 size_t spill_words(uint32_t blocks);
 // chunks of the packet kernel's tile queue for a w x nrows launch (0: no packet kernel)
@@ -601,7 +603,7 @@ const uint32_t *xorwow_tables_host();   // [32 seq][160][5] ++ [64 step][160][5]
 // v = M^skip v (skip draws ahead, host)
 void xorwow_skip(uint32_t v[5], uint64_t skip);
 // k_rng_init's device tables: jump bytes [4][256][160][5] ++ J, J^64 by nibbles [2][40][16][5]
-constexpr size_t kRngNibWords = 40 * 16 * 5;      // one nibble table (bih_render.hip jump_lds)
+constexpr size_t kRngNibWords = 40 * 16 * 5;      // one nibble table (bih_rng.hip jump_lds)
 // ++ nibble tables of M^(2^(7+l)), l = 0..6: kStampJumpFrames frames of 2 * 2^l draws
 // (k_rng_sync, one per spp = 2^l)
 constexpr uint32_t kStampJumpFrames = 64;

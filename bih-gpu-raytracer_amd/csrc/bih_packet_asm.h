@@ -1,4 +1,4 @@
-// bih_packet_asm.h -- the packet walk of k_render_packet2 (bih_render.hip) as
+// bih_packet_asm.h -- the packet walk of k_render_packet2 (bih_walk.hip) as
 // one hand-scheduled gfx950 loop (inline asm).
 //
 // Why asm: the walk is bound by wave-uniform issue -- one scalar ALU per CU
@@ -77,7 +77,7 @@
 //                       u >= (1+2^-20)(1-2^-24)^3 > 1: u > 1;
 // det*2^-20 is exact (det > eps, no underflow); det = inf or NaN and un =
 // NaN compare false and keep the lane.  The lanes kept run the exact test.
-// Operand order of every f32 op follows prim_hits (bih_render.hip):
+// Operand order of every f32 op follows prim_hits (bih_ray.h):
 // record = {e1 s36-38, e2 s39-41, s = O - v0 s42-44, q s45-47, tnum s48}.
 #define BIH_MT(NEXT)                                                                  \
     "v_mul_f32_e32 v33, s41, %[dy]\n\t"      /* px = dy*e2z - e2y*dz */               \
@@ -434,3 +434,13 @@
     "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", \
     "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", \
     "v60", "v61", "v62", "v63", "v64", BIH_REC_CLOBBERS "vcc", "scc", "memory"
+
+// The statement's operand lists over k_render_packet_asm's variables: outputs,
+// outputs with the per-ray counters (BIH_CNT_*), inputs.
+#define BIH_PACKET_OUT [hits] "=&s"(hits), [tmin] "+v"(tMin), [tmax] "+v"(tMax)
+#define BIH_PACKET_OUT_CNT BIH_PACKET_OUT, [cn] "+v"(c_nodes), [cl] "+v"(c_leaves), [ct] "+v"(c_tris)
+#define BIH_PACKET_IN                                                                 \
+    [nodes] "s"(nodes), [prims] "s"(prims), [dupc] "s"(dupc), [spill] "s"(wspill),    \
+    [live] "s"(live), [near] "s"(nearbits), [eps] "s"(eps), [fmax] "s"(fmax),         \
+    [snan] "v"(snan), [lane4] "v"(lane4), [dx] "v"(dx), [dy] "v"(dy), [dz] "v"(dz),   \
+    [ix] "v"(ix), [iy] "v"(iy), [iz] "v"(iz), [sgn] "v"(sg)

@@ -321,7 +321,7 @@ def _pixel_mask(K, bx, by, w, h):
     return m
 
 
-# the packet tiles of 1 .. 64 spp (TileShape, bih_render.hip); the 4 x 4 cases keep their earlier ids
+# the packet tiles of 1 .. 64 spp (TileShape, bih_ray.h); the 4 x 4 cases keep their earlier ids
 TILES = [(8, 8), (8, 4), (4, 4), (4, 2), (2, 2), (2, 1), (1, 1)]
 
 

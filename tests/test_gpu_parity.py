@@ -1009,7 +1009,7 @@ def test_ring_advance_jump_tables_match_oracle(gpu, bihrt_mod, oracle_mod):
     """Frames on two streams in turn (the XORWOW ring, not the stamped
     state) with gaps of 48 and 148 frames: the ring's advance jumps the
     powers 2^7 .. 2^13 of the step count through its nibble tables (one or
-    two of them) and steps the rest (bih_render.hip k_rng_advance); a
+    two of them) and steps the rest (bih_rng.hip k_rng_advance); a
     16-frame call advances by exactly one table.  Every frame equals the
     oracle's."""
     import torch

@@ -1,4 +1,4 @@
-"""The miss-proof boxes of the any-hit walk (csrc/bih_render.hip, miss_box)
+"""The miss-proof boxes of the any-hit walk (csrc/bih_prim.hip, miss_box)
 must contain, for every ray the exact f32 intersector accepts
 (RayTriangleIntersection, CUDAKernels.cu:17-50, in the primary-ray record
 form of prim_hits / k_tri_prim), a point of that ray's line -- as the
@@ -193,7 +193,7 @@ def test_miss_box_contains_every_accepted_ray_soup():
 
 
 def _camera_dir(cam, u, v):
-    """camera_dir (csrc/bih_render.hip), f32, no FMA: D = ((llc + u h) + v vert) - O."""
+    """camera_dir (csrc/bih_device.h), f32, no FMA: D = ((llc + u h) + v vert) - O."""
     c = np.asarray(cam, F)
     return np.stack([((c[3 + k] + u * c[6 + k]) + v * c[9 + k]) - c[k] for k in range(3)], 1).astype(F)
 
